@@ -5,6 +5,11 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N ...        # no launcher: this process starts the N workers itself (launch_workers) and relays the line
+    python bench.py ... --full          # also every figure and check beside the headline (roofline, CPU baseline, extras, N > 1 sections)
+    python bench.py ... --dump-outputs DIR   # after the timed steps: DIR/regrid_out.npy, what the last step computed
+
+A plain run sets up, warms up, times the K steps, writes its outputs when asked to and prints ONE JSON line: `metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step` (wall clock of the timed region / K), with the run's shape and set-up times.
 
 A *step* is one pass of the regrid hot path over one batch of synthetic input already resident in HBM: ONE 137-level stack on
 the O1280 octahedral grid (6 599 680 points) is interpolated to the 0.25 degree lat-lon grid (1 038 240 points) with k = 4
@@ -27,7 +32,7 @@ the N GPUs of the run (O1280 -> N320-sized, 24 stacks resident per rank, target 
 the exchange-free alternative.
 Host-side barriers and the max-over-ranks reduction run on a gloo group, stack traffic on an nccl (= RCCL) group.
 
-Also on the same JSON line:
+With --full, also on the same JSON line:
   roofline     algorithmic bytes of one launch / its average HIP-event duration against the 8 TB/s HBM3E peak
   cpu_baseline the oracle's scipy `csr_array @ x` statement (the reference's CPU path, R: filters/fields/regrid.py:310)
                timed on one host core on a bounded sample of the same workload (rank 0, N = 1 only)
@@ -109,6 +114,12 @@ def parse_args():
                          "rank 0 prints {\"launch_check\": true, ...} — what `python bench.py --gpus N` does before it touches the device")
     ap.add_argument("--share-device", action="store_true",
                     help="REHEARSAL ONLY: all ranks use cuda:0 (exercises the N > 1 code path on a 1-GPU box; needs --backend gloo)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure and check everything beside it: roofline launches, parity against the oracle, CPU "
+                         "baselines and extras (N = 1), exchange / end-to-end / config sections (N > 1); the --no-* options above trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/regrid_out.npy: the regridded stack in the run's "
+                         "dtype, field-major [levels, targets]; beyond DUMP_BYTES a fixed seeded sample of the target points (dump_targets)")
     return ap.parse_args()
 
 
@@ -273,6 +284,39 @@ def line(n_units, ms, alg_bytes):
     return {"value": n_units / (ms * 1e-3), "avg_launch_ms": ms, "achieved_GBs": gbs, "frac": gbs / HBM_PEAK_GBS}
 
 
+DUMP_BYTES = 60 * 2**20  # --dump-outputs writes at most this much
+
+
+def dump_targets(n_tgt: int, n_lev: int, itemsize: int) -> np.ndarray:
+    """The target points --dump-outputs writes, ascending: all of them when the whole stack fits in DUMP_BYTES, else a sample of
+    as many as fit, drawn with SEED — the same for every run with the same grids, levels and dtype, whatever N."""
+    n_keep = min(n_tgt, DUMP_BYTES // (n_lev * itemsize))
+    if n_keep == n_tgt:
+        return np.arange(n_tgt)
+    return np.sort(np.random.default_rng(SEED).choice(n_tgt, n_keep, replace=False))
+
+
+def dump_outputs(directory, out, lo, hi, n_tgt, rank, world, dist) -> None:
+    """DIR/regrid_out.npy: the output stack of the last timed step as its caller receives it (field-major [levels, targets], the
+    run's dtype), at the targets of dump_targets.  N > 1: every rank holds the rows [lo, hi) of the target grid; rank 0 writes."""
+    from anemoi_transform_amd.stack import COLUMNS
+
+    pick = dump_targets(n_tgt, out.n_lev, out.data.element_size())
+    rows = torch.from_numpy(pick[(pick >= lo) & (pick < hi)] - lo).to(out.device)
+    if out.layout == COLUMNS:
+        part = out.data.index_select(0, rows)[:, : out.n_lev].T
+    else:
+        part = out.data[: out.n_lev].index_select(1, rows)
+    part = np.ascontiguousarray(part.cpu().numpy())
+    if world > 1:  # the ranks' target ranges are consecutive in rank order
+        parts = [None] * world if rank == 0 else None
+        dist.gather_object(part, parts, dst=0)
+        part = np.concatenate(parts, axis=1) if rank == 0 else None
+    if rank == 0:
+        os.makedirs(directory, exist_ok=True)
+        np.save(os.path.join(directory, "regrid_out.npy"), part)
+
+
 def launch_workers(args) -> int:
     """`python bench.py --gpus N` without a launcher: this process — which has not touched the GPU and never will — starts N
     FRESH worker processes through torch.distributed.run (one per GPU, rendezvous on 127.0.0.1 at a free port), passes rank 0's
@@ -387,7 +431,6 @@ def main():
     n_src, n_tgt = len(src_grid["latitudes"]), len(tgt_grid["latitudes"])
     idx64, w64 = knn_inverse_distance(src_grid, tgt_grid, k=args.k)
     precompute_s = time.perf_counter() - t0
-    n_unique = int(np.unique(idx64).size)
     mark("grids_and_knn_table")
 
     # target-point shard of this rank: contiguous, balanced by HBM traffic (GatherPlan.bounds) — equal-count
@@ -443,33 +486,38 @@ def main():
         print(f"bench.py: value {value:.6g} grid-points/s, {elapsed / args.steps * 1e3:.4f} ms/step over {args.steps} steps on {world} GPU(s), "
               f"{wall_seconds():.1f} s after process start", file=sys.stderr, flush=True)
 
-    # ---- roofline of the dominant kernel, HIP events around single launches (N > 1: this rank's shard of the stack)
-    launch_ms = launch_times(step, min(max(args.steps, 10), 200), 2)
-    avg_ms, min_ms, median_ms = float(np.mean(launch_ms)), float(np.min(launch_ms)), float(np.median(launch_ms))
-    shard_unique = int(np.unique(idx64[lo:hi]).size)
-    alg = algorithmic_bytes(args.levels, itemsize, shard_unique, hi - lo, args.k)
-    achieved = alg / (avg_ms * 1e-3) / 1e9
-    # the same figure for the WHOLE job: the algorithmic bytes of all ranks' launches of one step over the step time the driver's value is
-    # computed from (max over ranks, wall clock of the K steps) against N x the peak — "fraction of the HBM roofline at 1, 2, 4, 8 GPUs"
-    alg_all = float(alg)
-    if multi:
-        t_alg = torch.tensor([alg_all], dtype=torch.float64)
-        dist.all_reduce(t_alg, op=dist.ReduceOp.SUM)
-        alg_all = float(t_alg.item())
-    job_gbs = alg_all / (elapsed / args.steps) / 1e9
-    traffic, traffic_source = None, None
-    tpath = os.path.join(ROOT, "profiles", "traffic.json")
-    if os.path.exists(tpath):
-        try:
-            rec = json.load(open(tpath))
-            key = f"{args.src_grid}->{args.tgt_grid} k={args.k} L={args.levels} {args.dtype} {args.layout} gpus={world}"
-            if key in rec:
-                traffic = rec[key].get("hbm_bytes_per_launch")
-                # NOT measured by this process: PMC counters need rocprofv3 around the run (tools/pmc_probe.py)
-                traffic_source = ("carried from profiles/traffic.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes over this same "
-                                  f"launch ({rec[key].get('measured', rec.get('_measured', 'round 1'))}), not re-measured in this run")
-        except Exception:
-            traffic = None
+    if args.dump_outputs:  # what the last timed step left in the output stack
+        dump_outputs(args.dump_outputs, outs[0], lo, hi, n_tgt, rank, world, dist)
+        mark("dump_outputs")
+
+    if args.full:
+        # ---- (--full) roofline of the dominant kernel, HIP events around single launches (N > 1: this rank's shard of the stack)
+        launch_ms = launch_times(step, min(max(args.steps, 10), 200), 2)
+        avg_ms, min_ms, median_ms = float(np.mean(launch_ms)), float(np.min(launch_ms)), float(np.median(launch_ms))
+        shard_unique = int(np.unique(idx64[lo:hi]).size)
+        alg = algorithmic_bytes(args.levels, itemsize, shard_unique, hi - lo, args.k)
+        achieved = alg / (avg_ms * 1e-3) / 1e9
+        # the same figure for the WHOLE job: the algorithmic bytes of all ranks' launches of one step over the step time the driver's value is
+        # computed from (max over ranks, wall clock of the K steps) against N x the peak — "fraction of the HBM roofline at 1, 2, 4, 8 GPUs"
+        alg_all = float(alg)
+        if multi:
+            t_alg = torch.tensor([alg_all], dtype=torch.float64)
+            dist.all_reduce(t_alg, op=dist.ReduceOp.SUM)
+            alg_all = float(t_alg.item())
+        job_gbs = alg_all / (elapsed / args.steps) / 1e9
+        traffic, traffic_source = None, None
+        tpath = os.path.join(ROOT, "profiles", "traffic.json")
+        if os.path.exists(tpath):
+            try:
+                rec = json.load(open(tpath))
+                key = f"{args.src_grid}->{args.tgt_grid} k={args.k} L={args.levels} {args.dtype} {args.layout} gpus={world}"
+                if key in rec:
+                    traffic = rec[key].get("hbm_bytes_per_launch")
+                    # NOT measured by this process: PMC counters need rocprofv3 around the run (tools/pmc_probe.py)
+                    traffic_source = ("carried from profiles/traffic.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes over this same "
+                                      f"launch ({rec[key].get('measured', rec.get('_measured', 'round 1'))}), not re-measured in this run")
+            except Exception:
+                traffic = None
 
     result = {
         "metric": "grid-points/sec regridded, O1280->0.25deg x137 levels",
@@ -509,7 +557,10 @@ def main():
             **({"rehearsal": "ranks share one GPU over gloo; not a scaling measurement"} if args.share_device else {}),
             **({"rehearsal": "N > 1 sections at world size 1 (RCCL code path on one GPU); not a scaling measurement"} if args.rehearse_multi else {}),
         },
-        "roofline": {
+        "precompute_s": max_over_ranks(precompute_s),  # host-side k-NN table (cKDTree or its cache file), slowest rank
+    }
+    if args.full:
+        result["roofline"] = {
             "bound": "hbm",
             "kernel": "regrid_cols_ell_direct_kernel" if layout == COLUMNS else "regrid_fields_ell_kernel",
             "achieved": achieved,
@@ -526,10 +577,8 @@ def main():
             # all ranks together, on the wall clock of the timed region (what `value` is computed from); at N = 1 the launch-gap-inclusive twin of `frac`
             "job": {"algorithmic_bytes_per_step_all_ranks": alg_all, "achieved": job_gbs, "peak": HBM_PEAK_GBS * world, "unit": "GB/s",
                     "frac": job_gbs / (HBM_PEAK_GBS * world), "ms_per_step": elapsed / args.steps * 1e3},
-        },
-        "precompute_s": max_over_ranks(precompute_s),  # host-side k-NN table (cKDTree or its cache file), slowest rank
-    }
-    mark("roofline_launches")
+        }
+        mark("roofline_launches")
     if multi:
         # where the wall clock of an N-rank command goes before the secondary sections start: the stage times of the rank that took
         # LONGEST to get here, as that rank saw them (an entry-by-entry maximum would count a slow rank's stage and the others' wait
@@ -549,7 +598,7 @@ def main():
         # sections, so that a line cut short by their budget carries it too)
         result["strong"] = {"value": value, "unit": "grid-points/s", "ms_per_step": elapsed / args.steps * 1e3, "scaling": "strong",
                             "note": "the headline itself: ONE 137-level stack (the N = 1 job), each rank its 1/N target slice; source resident on every rank"}
-    if multi and not args.no_extras:
+    if multi and args.full and not args.no_extras:
         # RCCL announces itself on stdout when its first communicator comes up (version, host, library path): the secondary sections
         # run with file descriptor 1 pointing at stderr, stdout stays reserved for the ONE JSON line
         quiet = quiet_stdout()
@@ -573,9 +622,9 @@ def main():
         finally:
             quiet.__exit__()
 
-    if rank == 0 and world == 1 and not args.rehearse_multi:
-        single_gpu_lines(args, result, dev, stacks, outs, launch, idx_d, w_d, rows_d, idx64, w64, n_src, n_tgt, n_unique, alg, src_grid, tgt_grid,
-                         tdtype, np_dtype, itemsize, plan)
+    if args.full and rank == 0 and world == 1 and not args.rehearse_multi:
+        single_gpu_lines(args, result, dev, stacks, outs, launch, idx_d, w_d, rows_d, idx64, w64, n_src, n_tgt, int(np.unique(idx64).size), alg,
+                         src_grid, tgt_grid, tdtype, np_dtype, itemsize, plan)
 
     result["wall_s"] = max_over_ranks(wall_seconds())  # process start -> this line, slowest rank
     if multi:

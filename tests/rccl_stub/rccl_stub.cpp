@@ -221,7 +221,9 @@ ncclResult_t ncclCommDestroy(ncclComm_t comm) {
     for (auto& t : c->readers)
         if (t.joinable()) t.detach();  // they end when the peers close their side
     ::unlink(path_of(c->token, c->rank).c_str());
-    // (the Comm object is leaked on purpose: detached readers may still touch it)
+    // with readers the Comm object is leaked on purpose (a detached reader may still touch it); without any (world 1) nothing
+    // can, and it is freed
+    if (c->readers.empty()) delete c;
     return 0;
 }
 

@@ -1,4 +1,4 @@
-"""bench.py's contract (one JSON line with the driver's keys plus `roofline` / `cpu_baseline`) on small grids, and the
+"""bench.py's contract (one JSON line with the driver's keys; with --full plus `roofline` / `cpu_baseline`) on small grids, and the
 N > 1 code path rehearsed with two ranks sharing the one GPU of the test box over gloo (the real N > 1 runs use RCCL,
 one GPU per rank; this keeps sharding, exchange, batched launch and max-over-ranks timing from rotting)."""
 
@@ -27,7 +27,7 @@ def last_json(stdout: str) -> dict:
 
 
 def test_single_gpu_line():
-    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *SMALL, "--cpu-seconds", "0.5", "--no-extras"],
+    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *SMALL, "--full", "--cpu-seconds", "0.5", "--no-extras"],
                          capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert run.returncode == 0, run.stderr[-2000:]
     d = last_json(run.stdout)
@@ -58,8 +58,92 @@ def test_single_gpu_line():
     assert d["parity_max_rel_err"] == 0.0  # float64: scipy's bits
 
 
+def test_plain_line_is_the_headline_alone(tmp_path):
+    """Without --full the line carries the headline and nothing measured beside it; --steps sets the timed steps, and
+    --dump-outputs writes the last step's output stack: scipy's `csr_array @ x` bits for every level of the synthetic stack."""
+    import numpy as np
+
+    from oracle import oracle
+
+    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *SMALL, "--dump-outputs", str(tmp_path)],
+                         capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert run.returncode == 0, run.stderr[-2000:]
+    d = last_json(run.stdout)
+    assert KEYS - {"roofline"} <= set(d) and d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1
+    assert d["higher_is_better"] is True and d["unit"] == "grid-points/s" and d["dtype"] == "f64" and d["value"] > 0
+    assert abs(d["value"] * d["ms_per_step"] * 1e-3 - 65160 * 7) < 1e-6 * 65160 * 7  # one step = the 1-degree grid x 7 levels
+    for moved in ("roofline", "cpu_baseline", "extras", "parity_max_rel_err"):
+        assert moved not in d, moved
+    assert "roofline_launches" not in d["setup_s"] and "dump_outputs" in d["setup_s"]
+    assert sorted(os.listdir(tmp_path)) == ["regrid_out.npy"]
+    got = np.load(tmp_path / "regrid_out.npy")
+    assert got.dtype == np.float64 and got.shape == (7, 65160)  # 3.6 MB: the whole stack, no sample
+
+    import torch
+
+    from anemoi_transform_amd.grids import lookup
+    from anemoi_transform_amd.interp import knn_inverse_distance
+    from anemoi_transform_amd.stack import COLUMNS
+
+    bench = _bench_module()
+    src, tgt = lookup("o96"), lookup("1.0")
+    n_src, n_tgt = len(src["latitudes"]), len(tgt["latitudes"])
+    idx, w = knn_inverse_distance(src, tgt, k=4)
+    fields = bench.synth_stack(src, 7, torch.float64, torch.device("cuda", 0), 0, COLUMNS).numpy()
+    indptr = np.arange(n_tgt + 1) * 4
+    want = np.stack([oracle.csr_apply(w.reshape(-1), idx.reshape(-1), indptr, (n_tgt, n_src), f) for f in fields])
+    assert np.array_equal(got, want)
+
+
+def test_dump_outputs_sample_a_large_stack(tmp_path):
+    """A stack larger than DUMP_BYTES is written as the fixed sample of target points of bench.dump_targets, every level of each,
+    and a second run with the same arguments writes the same bits."""
+    import numpy as np
+
+    bench = _bench_module()
+    args = ["--src-grid", "o96", "--tgt-grid", "0.25", "--levels", "64", "--steps", "2", "--warmup", "1", "--dump-outputs"]
+    got = []
+    for i in range(2):
+        run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args, str(tmp_path / str(i))], capture_output=True,
+                             text=True, timeout=300, cwd=ROOT)
+        assert run.returncode == 0, run.stderr[-2000:]
+        assert last_json(run.stdout)["steps"] == 2
+        path = tmp_path / str(i) / "regrid_out.npy"
+        assert os.path.getsize(path) <= 64 * 2**20
+        got.append(np.load(path))
+    pick = bench.dump_targets(1038240, 64, 8)
+    assert 0 < len(pick) < 1038240 and got[0].shape == (64, len(pick)) and got[0].dtype == np.float64
+    assert np.array_equal(got[0], got[1])
+
+
+def test_two_ranks_dump_the_outputs_of_one(tmp_path):
+    """--dump-outputs at N = 2 (two ranks sharing the GPU over gloo, no --full: no secondary section runs): rank 0 joins the two
+    target shards into the bits of the N = 1 run."""
+    import numpy as np
+
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *SMALL, "--dump-outputs", str(tmp_path / "n1")],
+                         capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
+    assert one.returncode == 0, one.stderr[-2000:]
+    two = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", *SMALL, "--backend", "gloo", "--share-device",
+                          "--dump-outputs", str(tmp_path / "n2")], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
+    assert two.returncode == 0, two.stderr[-2000:]
+    d = last_json(two.stdout)
+    assert d["n_gpus"] == 2 and d["value"] > 0 and "weak" not in d and d["config"]["multi_gpu"]["weak"] is None
+    assert np.array_equal(np.load(tmp_path / "n1" / "regrid_out.npy"), np.load(tmp_path / "n2" / "regrid_out.npy"))
+
+
+def _bench_module():
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    module = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(module)
+    return module
+
+
 def test_single_gpu_line_f32():
-    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *SMALL, "--dtype", "f32", "--cpu-seconds", "0.5", "--headline-shape-only"],
+    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *SMALL, "--full", "--dtype", "f32", "--cpu-seconds", "0.5", "--headline-shape-only"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert run.returncode == 0, run.stderr[-2000:]
     d = last_json(run.stdout)
@@ -74,7 +158,7 @@ def test_two_ranks_without_a_launcher():
     two workers (fresh processes; the parent never touches the GPU), relays rank 0's ONE line and exits 0."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", *SMALL, "--backend", "gloo", "--share-device",
-                          "--no-extras"], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
+                          "--full", "--no-extras"], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert run.returncode == 0, run.stderr[-2000:]
     d = last_json(run.stdout)
     assert KEYS <= set(d) and d["n_gpus"] == 2 and d["value"] > 0 and d["config"]["stacks_per_step"] == 1 and d["scaling"] == "strong"
@@ -126,13 +210,13 @@ def assert_wall_clock_accounted(d: dict, skipped: bool = False) -> None:
 
 
 def test_two_ranks_rehearsal_over_gloo():
-    """`--gpus 2` by default carries every N > 1 line: value (fixed total work = strong scaling, exchange excluded), the weak line of
-    rounds 1-4, the source exchanges timed and verified bit-equal, end_to_end (exchange inside), field-axis sharding — no opt-in flags."""
+    """`--gpus 2 --full` carries every N > 1 line: value (fixed total work = strong scaling, exchange excluded), the weak line of
+    rounds 1-4, the source exchanges timed and verified bit-equal, end_to_end (exchange inside), field-axis sharding — no other flags."""
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", *SMALL, "--backend", "gloo", "--share-device"]
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", *SMALL, "--backend", "gloo", "--share-device", "--full"]
     run = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert run.returncode == 0, run.stderr[-2000:]
     d = last_json(run.stdout)
@@ -164,7 +248,7 @@ def test_four_ranks_rehearsal_over_gloo():
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "4", *SMALL, "--backend", "gloo", "--share-device"]
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "4", *SMALL, "--backend", "gloo", "--share-device", "--full"]
     run = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert run.returncode == 0, run.stderr[-2000:]
     d = last_json(run.stdout)
@@ -185,7 +269,7 @@ def test_secondary_lines_cannot_cost_the_value():
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", *SMALL, "--backend", "gloo", "--share-device",
-           "--secondary-seconds", "0"]
+           "--full", "--secondary-seconds", "0"]
     run = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert run.returncode != 0  # the line is out, but a collective that never returned is a failure the launcher must see
     d = last_json(run.stdout)
@@ -201,7 +285,7 @@ def test_total_seconds_cap_skips_sections_and_keeps_the_line():
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", *SMALL, "--backend", "gloo", "--share-device",
-           "--total-seconds", "1"]
+           "--full", "--total-seconds", "1"]
     run = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert run.returncode == 0, run.stderr[-2000:]
     d = last_json(run.stdout)
@@ -219,7 +303,7 @@ def _two_ranks(extra_env: dict, *flags: str):
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", *SMALL, "--backend", "gloo", "--share-device", *flags]
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", *SMALL, "--backend", "gloo", "--share-device", "--full", *flags]
     return subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=dict(os.environ, **extra_env))
 
 
@@ -252,7 +336,7 @@ def test_multi_gpu_sections_on_real_rccl_at_world_1():
     env = dict(os.environ, MASTER_PORT=str(port), MASTER_ADDR="127.0.0.1")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "HSA_ENABLE_IPC_MODE_LEGACY"):  # bench.py sets the IPC mode itself, before HIP starts
         env.pop(k, None)
-    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *SMALL, "--rehearse-multi"], capture_output=True, text=True,
+    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *SMALL, "--full", "--rehearse-multi"], capture_output=True, text=True,
                          timeout=600, cwd=ROOT, env=env)
     assert run.returncode == 0, run.stderr[-3000:]
     d = last_json(run.stdout)

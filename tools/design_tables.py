@@ -7,7 +7,7 @@
 Blocks between `<!-- BEGIN generated: NAME (source) -->` and `<!-- END generated: NAME -->` in DESIGN.md, README.md and
 INTEGRATION.md are replaced (the newest round's record of each kind is used):
   kernel-table   profiles/rNN_kernel_bench.json   (tools/kernel_bench.py --out)
-  bench-line     profiles/rNN_bench_latest.json   (python bench.py)
+  bench-line     profiles/rNN_bench_latest.json   (python bench.py --full)
   host-fed       profiles/rNN_host_fed_path.json  (tools/host_path_bench.py) + the bench record's all-core CPU line
   filter-parity  DESIGN.md §7's table of the reference's field filters (README.md repeats it: what is pinned, what says at run time that it is not)
 `--check` exits 1 if a document is not up to date (used by tests/test_host_api.py)."""
