@@ -224,7 +224,9 @@ __device__ __forceinline__ void combine_one(int flags, const T* x, int n_in, T l
         case ATX_COMB_ATAN2: {
             T d = atan2(x[1], x[0]);
             if (flags & ATX_COMB_DEGREES) {
-                d = d * T(57.29577951308232);  // np.rad2deg: x * (180/pi)
+                // np.rad2deg: x * (180/pi) — in float32 numpy's factor is 180f / pi_f, one ulp from float32(180 / pi)
+                if constexpr (sizeof(T) == 4) d = d * (180.0f / 3.14159265358979323846f);
+                else d = d * 57.29577951308232;
                 d = (d >= T(360)) ? d - T(360) : d;
                 d = (d < T(0)) ? d + T(360) : d;
             }
@@ -313,14 +315,14 @@ __device__ __forceinline__ void combine_one(int flags, const T* x, int n_in, T l
             r = (r == T(0)) ? T(1.0e-4) : r;  // `relative_humidity_values[relative_humidity_values == 0] = EPS`
             const T e = quotient(r * es_water(x[1]), T(100));
             const T ln = atx_log(quotient(e, T(611.21)));
-            y0 = quotient(T(32.19) * ln - T(17.502) * T(273.16), ln - T(17.502));
+            y0 = quotient(T(32.19) * ln - T(17.502 * 273.16), ln - T(17.502));  // (17.502 * T0: one constant, as numpy's statement has it)
             break;
         }
         case ATX_COMB_D_TO_R: y0 = quotient(T(100) * es_water(x[0]), es_water(x[1])); break;  // (td, t); R: dewpoint.py:71
         case ATX_COMB_Q_TO_R: {  // (q, t[, p]); level = levelist in hPa when there is no pressure operand; R: q_to_r.py:72-74, q_height.py:117-121
             const T eps = T(287.0597 / 461.5250);
             const T p = n_in > 2 ? x[2] : T(100) * level;
-            const T e = quotient(p * x[0], eps + (eps * (T(1) / eps - T(1))) * x[0]);
+            const T e = quotient(p * x[0], eps + T(287.0597 / 461.5250 * (461.5250 / 287.0597 - 1.0)) * x[0]);  // the constant as numpy's
             y0 = quotient(T(100) * e, es_mixed(x[1]));
             break;
         }

@@ -431,8 +431,10 @@ def test_q_to_r_height_with_p_and_round_trip(engine):
 @pytest.mark.parametrize("np_dtype,rtol", [(np.float64, 2e-13), (np.float32, 2e-5)], ids=["f64", "f32"])
 @pytest.mark.parametrize("layout", [native.COLUMNS, native.FIELDS], ids=["columns", "fields"])
 def test_humidity_kernels_vs_oracle(dev, np_dtype, rtol, layout):
-    """Floating point with exp / log from the device library: held to the numpy restatement within a few ulp of the result
-    (float64 2e-13, float32 2e-5 relative) on the ranges the atmosphere has, all three phases of the saturation curve included."""
+    """Floating point with exp / log — float32 from the device library, float64 from the library's own atx_exp / atx_log
+    (atx_common.hpp) — and the refined-reciprocal quotients: held to the numpy restatement within a few ulp of the result
+    (float64 2e-13, float32 2e-5 relative) on the ranges the atmosphere has, all three phases of the saturation curve included.
+    The tight bounds, in ulps against exact arithmetic, are tests/test_gpu_ulp_budgets.py's."""
     from anemoi_transform_amd.stack import Stack
 
     rng = np.random.default_rng(41)

@@ -391,9 +391,9 @@ def test_random_combine_cases(dev, seed):
     back = run(native.COMB_ATAN2, [wc.astype(np_dtype), ws.astype(np_dtype)], 1, flags=native.COMB_DEGREES if deg else 0)[0]
     np.testing.assert_allclose(back, oracle.direction_from_cos_sin(wc.astype(np_dtype), ws.astype(np_dtype), deg), rtol=rtol, atol=1e-4)
     want = np.stack([oracle.w_to_wz(w[l], t[l], q[l], np_dtype(levels[l])) for l in range(n_lev)])
-    np.testing.assert_allclose(run(native.COMB_W_TO_WZ, [w, t, q], 1, with_levels=True)[0], want, rtol=rtol)
+    assert np.array_equal(run(native.COMB_W_TO_WZ, [w, t, q], 1, with_levels=True)[0], want)  # one rounding per operation, numpy's order: bit-exact
     want = np.stack([oracle.wz_to_w(w[l], t[l], q[l], np_dtype(levels[l])) for l in range(n_lev)])
-    np.testing.assert_allclose(run(native.COMB_WZ_TO_W, [w, t, q], 1, with_levels=True)[0], want, rtol=rtol)
+    assert np.array_equal(run(native.COMB_WZ_TO_W, [w, t, q], 1, with_levels=True)[0], want)  # one rounding per operation, numpy's order: bit-exact
     n_terms = int(rng.integers(1, 9))
     terms = [sd, rsn, ang, t, w, q, sd * 2, t * 3][:n_terms]
     assert np.array_equal(run(native.COMB_SUM, terms, 1)[0], np.stack([oracle.sum_fields([x[l] for x in terms]) for l in range(n_lev)]))

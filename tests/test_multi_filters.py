@@ -334,9 +334,9 @@ def test_combine_kernel_vs_oracle(dev, tdtype, np_dtype, rtol, layout):
     t = (250.0 + 40.0 * rng.random((n_lev, n_pts))).astype(np_dtype)
     w = rng.normal(0, 0.5, (n_lev, n_pts)).astype(np_dtype)
     want = np.stack([oracle.w_to_wz(w[l], t[l], c[l], np_dtype(levels[l])) for l in range(n_lev)])
-    np.testing.assert_allclose(run(native.COMB_W_TO_WZ, [w, t, c], 1, with_levels=True)[0], want, rtol=rtol)
+    assert np.array_equal(run(native.COMB_W_TO_WZ, [w, t, c], 1, with_levels=True)[0], want)  # one rounding per operation, numpy's order: bit-exact
     want = np.stack([oracle.wz_to_w(w[l], t[l], c[l], np_dtype(levels[l])) for l in range(n_lev)])
-    np.testing.assert_allclose(run(native.COMB_WZ_TO_W, [w, t, c], 1, with_levels=True)[0], want, rtol=rtol)
+    assert np.array_equal(run(native.COMB_WZ_TO_W, [w, t, c], 1, with_levels=True)[0], want)  # one rounding per operation, numpy's order: bit-exact
     terms = [a, b, c, t, w]
     assert np.array_equal(run(native.COMB_SUM, terms, 1)[0], np.stack([oracle.sum_fields([x[l] for x in terms]) for l in range(n_lev)]))
     # wind components <-> speed / direction (R: uv_to_ddff.py:93-97, 121-125)
