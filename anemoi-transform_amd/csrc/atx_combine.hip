@@ -335,6 +335,23 @@ __device__ __forceinline__ void combine_one(int flags, const T* x, int n_in, T l
             y0 = quotient(eps * e, v);
             break;
         }
+        case ATX_COMB_Q_TO_D: {  // (q, p) -> dewpoint; R: q_height.py:466-475 -> thermo.dewpoint_from_specific_humidity
+            T qv = x[0];
+            qv = (qv == T(0)) ? T(1.0e-8) : qv;  // `values[values == 0] = EPS_SPECIFIC` (q_height.py:25, :468-469), on this copy only
+            const T e = quotient(x[1] * qv, T(287.0597 / 461.5250) + T(287.0597 / 461.5250 * (461.5250 / 287.0597 - 1.0)) * qv);
+            const T ln = atx_log(quotient(e, T(611.21)));
+            y0 = quotient(T(32.19) * ln - T(17.502 * 273.16), ln - T(17.502));  // the inverse of es_water, as ATX_COMB_R_TO_D
+            break;
+        }
+        case ATX_COMB_D_TO_Q: {  // (td, p) -> specific humidity; R: q_height.py:511-514 -> thermo.specific_humidity_from_dewpoint
+            const T eps = T(287.0597 / 461.5250);
+            const T p = x[1];
+            const T e = es_water(x[0]);
+            T v = p - (T(1) - eps) * e;
+            if (p - e < T(1.0e-4)) v = quiet_nan<T>();  // specific_humidity_from_vapour_pressure's guard, as ATX_COMB_R_TO_Q
+            y0 = quotient(eps * e, v);
+            break;
+        }
         default: y0 = x[0]; break;
     }
 }
@@ -550,6 +567,8 @@ static int combine_typed(const CombArgs& a, int op, int flags, int n_in, int n_o
         ATX_COMB_CASE(ATX_COMB_D_TO_R, 2);
         ATX_COMB_CASE(ATX_COMB_Q_TO_R, 3);
         ATX_COMB_CASE(ATX_COMB_R_TO_Q, 3);
+        ATX_COMB_CASE(ATX_COMB_Q_TO_D, 2);
+        ATX_COMB_CASE(ATX_COMB_D_TO_Q, 2);
         default:  // ATX_COMB_SUM
             if (vec_ok) {
                 if (n_in <= 1) ATX_COMB_LAUNCH(VEC, 1, ATX_COMB_SUM);
@@ -577,8 +596,8 @@ using namespace atx;
 extern "C" int atx_combine_stack(int op, const void* const* inputs, int32_t n_in, void* const* outputs, int32_t n_out,
                                  int64_t n_pts, int64_t n_lev, int64_t pitch, int dtype, int layout,
                                  const double* level_param, int32_t flags, void* stream) {
-    static const int kIn[ATX_COMB_COUNT_] = {2, 2, 1, 2, 3, 3, -1, 2, 2, 2, 2, 3, 2, 1, 2, 2, -2, -2};  // -1: any number, -2: two or three
-    static const int kOut[ATX_COMB_COUNT_] = {1, 1, 2, 1, 1, 1, 1, 1, 2, 2, 2, 2, 1, 1, 1, 1, 1, 1};
+    static const int kIn[ATX_COMB_COUNT_] = {2, 2, 1, 2, 3, 3, -1, 2, 2, 2, 2, 3, 2, 1, 2, 2, -2, -2, 2, 2};  // -1: any number, -2: two or three
+    static const int kOut[ATX_COMB_COUNT_] = {1, 1, 2, 1, 1, 1, 1, 1, 2, 2, 2, 2, 1, 1, 1, 1, 1, 1, 1, 1};
     ATX_REQUIRE(op >= 0 && op < ATX_COMB_COUNT_, ATX_EINVAL, "atx_combine_stack: bad operator %d", op);
     ATX_REQUIRE(inputs && outputs, ATX_EINVAL, "atx_combine_stack: null pointer table");
     ATX_REQUIRE(n_in >= 1 && n_in <= ATX_COMB_MAX_INPUTS, ATX_EINVAL, "atx_combine_stack: n_in=%d outside [1, %d]", n_in, ATX_COMB_MAX_INPUTS);

@@ -13,6 +13,8 @@ vectors at np.allclose — second half of this file):
   r_to_d / d_to_r                                 R: filters/fields/dewpoint.py
   q_to_r / r_to_q                                 R: filters/fields/q_to_r.py
   q_to_r_height_with_p / r_to_q_height_with_p     R: filters/fields/q_height.py:57-152
+  q_to_r_height / r_to_q_height                   R: filters/fields/q_height.py:154-330   (pressure from model levels:
+  q_to_d_height / d_to_q_height                   R: filters/fields/q_height.py:333-523    atx_pressure_at_height_stack)
 
 The first four are ``MatchingFieldsFilter``s there: fields grouped by their MARS key minus ``param``, one numpy expression per group.
 Here the OPERA filters run ONE ``atx_combine_stack`` launch for all groups (``StackMatchingFilter``); ``oras6_clipping`` runs one
@@ -25,6 +27,7 @@ from __future__ import annotations
 import logging
 from typing import Any, Iterator
 
+import numpy as np
 import torch
 
 from .. import native
@@ -295,8 +298,8 @@ filter_registry.register("r_to_q", HumidityConversion.reversed)
 
 class SpecificToRelativeAtHeightLevelWithP(StackMatchingFilter):
     """The same conversion with the pressure given as a third field (Pa), e.g. on height levels
-    (R: filters/fields/q_height.py:57-152).  The two other filters of that file (``q_to_r_height``, ``q_to_d_height``) derive the
-    pressure from model levels with earthkit-meteo's ``vertical.pressure_at_height_levels`` and are not implemented."""
+    (R: filters/fields/q_height.py:57-152).  The two other filters of that file (``q_to_r_height``, ``q_to_d_height``, below) derive
+    the pressure from model levels with earthkit-meteo's ``vertical.pressure_at_height_levels``."""
 
     MATCHING = MatchingSpec(
         select="param",
@@ -338,3 +341,211 @@ class SpecificToRelativeAtHeightLevelWithP(StackMatchingFilter):
 
 filter_registry.register("q_to_r_height_with_p", SpecificToRelativeAtHeightLevelWithP)
 filter_registry.register("r_to_q_height_with_p", SpecificToRelativeAtHeightLevelWithP.reversed)
+
+
+# =================================================================================
+# humidity at a height level from model levels (R: filters/fields/q_height.py:28-54, :154-523): the pressure at the height comes
+# from one column walk per grid point (atx_pressure_at_height_stack), the humidity from one combine launch
+# =================================================================================
+#: named hybrid-coefficient tables for ``model_level_AB="<name>"``.  The reference looks names up in its constants module (IFS_137 there);
+#: those tables are not bundled with this package, so the registry starts empty — ``register_model_level_AB`` adds one.
+MODEL_LEVEL_AB: dict[str, dict[str, list[float]]] = {}
+
+
+def register_model_level_AB(name: str, A: Any, B: Any) -> None:
+    """Make ``model_level_AB=name`` (any letter case) stand for these half-level coefficients (n_lev + 1 values each)."""
+    MODEL_LEVEL_AB[name.upper()] = {"A": [float(a) for a in A], "B": [float(b) for b in B]}
+
+
+def _set_AB(model_level_AB: Any) -> tuple[np.ndarray, np.ndarray]:
+    """R: q_height.py:28-41 — same errors; an unknown name also says how to supply a table."""
+    if isinstance(model_level_AB, str):
+        model_level_AB = model_level_AB.upper()
+        try:
+            model_level_AB = MODEL_LEVEL_AB[model_level_AB]
+        except KeyError:
+            raise KeyError(
+                "%s is not in the list of predefined AB-coefficients. Possible options are %s." % (model_level_AB, ", ".join(MODEL_LEVEL_AB.keys()))
+                + " The reference's predefined tables (IFS_137) are not bundled with this package: pass model_level_AB={'A': [...], 'B': [...]}"
+                " or register a table with anemoi_transform_amd.filters.domain.register_model_level_AB(name, A, B)."
+            ) from None
+    if not isinstance(model_level_AB, dict):
+        raise TypeError("model_level_AB must be a string or a dictionary.")
+    return np.array(model_level_AB["A"]), np.array(model_level_AB["B"])
+
+
+def _check_consistency(A: np.ndarray, B: np.ndarray, model_level_fields: dict[str, Any]) -> None:
+    """R: q_height.py:44-54 — the same assertions (the level count from the FieldList, not from a download of its values)."""
+    assert A.shape == B.shape, "A and B coefficients must have same shape"
+    for name, field in model_level_fields.items():
+        assert all(item == "ml" for item in field.metadata("levtype")), "Field {} does not contain model levels".format(name)
+        assert A.shape[-1] == len(field) + 1, f"model level AB-coefficients should have one more vertical level than {name}"
+
+
+def _same_shape(stack: Any, like: Any, dtype: torch.dtype) -> Any:
+    """``stack`` in ``dtype`` with the layout and pitch of ``like`` (the kernel reads two model-level stacks with one pitch)."""
+    from ..stack import Stack
+
+    if stack.dtype != dtype:
+        stack = Stack(stack.data.to(dtype), stack.n_pts, stack.n_lev, stack.layout)
+    if stack.layout == like.layout and stack.pitch == like.pitch:
+        return stack
+    out = Stack(torch.zeros_like(like.data, dtype=dtype), like.n_pts, like.n_lev, like.layout)
+    native.relayout(stack.data, out.data, n_pts=stack.n_pts, n_lev=stack.n_lev, src_pitch=stack.pitch, dst_pitch=out.pitch,
+                    src_layout=stack.layout, dst_layout=out.layout)
+    return out
+
+
+def _one_field(field: Any, dtype: torch.dtype) -> torch.Tensor:
+    """A single field as a contiguous ``[n_pts]`` device tensor of ``dtype``."""
+    s = fields_to_stack([field])
+    if s.layout != native.FIELDS and s.pitch != 1:
+        s = s.to_layout(native.FIELDS)
+    v = s.data[0, : s.n_pts] if s.layout == native.FIELDS else s.data[:, 0]
+    return v if v.dtype == dtype else v.to(dtype)
+
+
+HEIGHT_NOTE = ("the pressure at the height level restates earthkit-meteo's vertical.pressure_at_height_levels (alpha_top='ifs', moist gas "
+               "constant Rd (1 - q) + Rv q; package absent here) and the humidity its thermo.array formulas; pinned only at the reference's "
+               "test points (tests/field_filters/test_height_level_humidity.py): the 2 m dewpoints at its rtol 1e-7, the specific humidities "
+               "from dewpoints at 5e-7 — not bit for bit, np.allclose at best")
+HEIGHT_RH_GAP = ("; the reference's 2 m relative humidity literals are NOT reproduced by the saturation-pressure restatement this filter shares "
+                 "with q_to_r (1e-4 relative at warm temperatures, 1.1 % at 250 K, 4.3 % at 238 K), whatever the pressure: a gap of that "
+                 "restatement or of the earthkit-meteo version that wrote them")
+
+
+class _HumidityAtHeightLevel(MatchingFieldsFilter):
+    """What the two filters of R: q_height.py:154-523 share: the A / B coefficients, the checks, the pressure at the height level."""
+
+    _ABSTRACT_MATCHING_BASE = True
+
+    def _set_coefficients(self, model_level_AB: Any) -> None:
+        self.A, self.B = _set_AB(model_level_AB)
+        self._device_AB: dict[Any, tuple[torch.Tensor, torch.Tensor]] = {}
+
+    def _coefficients(self, device: Any) -> tuple[torch.Tensor, torch.Tensor]:
+        if device not in self._device_AB:
+            self._device_AB[device] = tuple(torch.tensor(np.asarray(c, dtype=np.float64), device=device) for c in (self.A, self.B))
+        return self._device_AB[device]
+
+    def _pressure_at_height_level(self, temperature_at_model_levels: Any, specific_humidity_at_model_levels: Any, surface_pressure: Any,
+                                  *height_level_fields: Any) -> tuple[torch.Tensor, list[torch.Tensor]]:
+        """``(p, operands)``: the pressure at ``self.height`` as a contiguous device tensor, and the height-level fields in its dtype —
+        float64 unless every input is float32.  One ``atx_pressure_at_height_stack`` launch."""
+        _check_consistency(self.A, self.B, {self.specific_humidity_at_model_levels: specific_humidity_at_model_levels,
+                                            self.temperature_at_model_levels: temperature_at_model_levels})
+        # R: q_height.py:271-272 — the model levels ascending, the top level first
+        t = fields_to_stack(sorted(temperature_at_model_levels, key=lambda f: f.metadata("levelist")))
+        q = fields_to_stack(sorted(specific_humidity_at_model_levels, key=lambda f: f.metadata("levelist")))
+        singles = [fields_to_stack([f]) for f in (surface_pressure, *height_level_fields)]
+        dtype = torch.float32 if all(s.dtype == torch.float32 for s in [t, q, *singles]) else torch.float64
+        t = _same_shape(t, t, dtype)
+        q = _same_shape(q, t, dtype)
+        sp, *operands = (_one_field(f, dtype) for f in (surface_pressure, *height_level_fields))
+        A, B = self._coefficients(t.device)
+        p = torch.empty(t.n_pts, dtype=dtype, device=t.device)
+        native.pressure_at_height_stack(t.data, q.data, sp, A, B, p, n_pts=t.n_pts, n_lev=t.n_lev, pitch=t.pitch, layout=t.layout,
+                                        height=self.height)
+        return p, operands
+
+    def _combine(self, op: int, operands: list[torch.Tensor], template: Any, param: str) -> Any:
+        from ..stack import Stack
+
+        n_pts = operands[0].numel()
+        out = Stack.empty(n_pts, 1, operands[0].dtype, operands[0].device, native.FIELDS)
+        native.combine_stack(op, [x.view(1, n_pts) for x in operands], [out.data], n_pts=n_pts, n_lev=1, pitch=n_pts, layout=native.FIELDS)
+        return new_field_from_stack(out, 0, template=template, metadata=dict(param=param))
+
+
+class SpecificToRelativeAtHeightLevel(_HumidityAtHeightLevel):
+    """Specific humidity (kg/kg) and temperature at a height above the ground -> relative humidity (%), and back, with the pressure
+    at that height derived from the model-level temperature and humidity, the surface pressure and the hybrid coefficients
+    (R: filters/fields/q_height.py:154-330).  One column-walk launch and one combine launch per group."""
+
+    MATCHING = MatchingSpec(
+        select="param",
+        forward=("specific_humidity_at_height_level", "temperature_at_height_level", "surface_pressure",
+                 "specific_humidity_at_model_levels", "temperature_at_model_levels"),
+        backward=("relative_humidity_at_height_level", "temperature_at_height_level", "surface_pressure",
+                  "specific_humidity_at_model_levels", "temperature_at_model_levels"),
+        vertical=True,
+    )
+    PARITY_NOTE = HEIGHT_NOTE + HEIGHT_RH_GAP
+
+    def __init__(self, *, height: float = 2.0, specific_humidity_at_height_level: str = "2q", relative_humidity_at_height_level: str = "2r",
+                 temperature_at_height_level: str = "2t", surface_pressure: str = "sp", specific_humidity_at_model_levels: str = "q",
+                 temperature_at_model_levels: str = "t", model_level_AB: Any,
+                 return_inputs: Any = ["specific_humidity_at_height_level", "relative_humidity_at_height_level", "temperature_at_height_level",
+                                       "surface_pressure"]) -> None:
+        self.return_inputs = return_inputs
+        self.height = float(height)
+        self.specific_humidity_at_height_level = specific_humidity_at_height_level
+        self.relative_humidity_at_height_level = relative_humidity_at_height_level
+        self.temperature_at_height_level = temperature_at_height_level
+        self.surface_pressure = surface_pressure
+        self.specific_humidity_at_model_levels = specific_humidity_at_model_levels
+        self.temperature_at_model_levels = temperature_at_model_levels
+        self._set_coefficients(model_level_AB)
+        super().__init__()
+
+    def forward_transform(self, specific_humidity_at_height_level: Any, temperature_at_height_level: Any, surface_pressure: Any,
+                          specific_humidity_at_model_levels: Any, temperature_at_model_levels: Any) -> Iterator[Any]:
+        p, (q, t) = self._pressure_at_height_level(temperature_at_model_levels, specific_humidity_at_model_levels, surface_pressure,
+                                                   specific_humidity_at_height_level, temperature_at_height_level)
+        yield self._combine(native.COMB_Q_TO_R, [q, t, p], specific_humidity_at_height_level, self.relative_humidity_at_height_level)
+
+    def backward_transform(self, relative_humidity_at_height_level: Any, temperature_at_height_level: Any, surface_pressure: Any,
+                           specific_humidity_at_model_levels: Any, temperature_at_model_levels: Any) -> Iterator[Any]:
+        p, (r, t) = self._pressure_at_height_level(temperature_at_model_levels, specific_humidity_at_model_levels, surface_pressure,
+                                                   relative_humidity_at_height_level, temperature_at_height_level)
+        yield self._combine(native.COMB_R_TO_Q, [r, t, p], relative_humidity_at_height_level, self.specific_humidity_at_height_level)
+
+
+filter_registry.register("q_to_r_height", SpecificToRelativeAtHeightLevel)
+filter_registry.register("r_to_q_height", SpecificToRelativeAtHeightLevel.reversed)
+
+
+class SpecificToDewpointAtHeightLevel(_HumidityAtHeightLevel):
+    """Specific humidity (kg/kg) at a height above the ground -> dewpoint temperature (K), and back, with the pressure at that height
+    derived as in ``q_to_r_height`` (R: filters/fields/q_height.py:333-523).  A specific humidity of exactly 0 is taken as 1e-8
+    (``EPS_SPECIFIC``, R: q_height.py:25, :468-469) inside the operator: the reference writes the guard into the array its input field
+    hands out, here the input field is passed on as it came — the returned humidity field is never altered."""
+
+    MATCHING = MatchingSpec(
+        select="param",
+        forward=("specific_humidity_at_height_level", "surface_pressure", "specific_humidity_at_model_levels", "temperature_at_model_levels"),
+        backward=("dewpoint_temperature_at_height_level", "surface_pressure", "specific_humidity_at_model_levels",
+                  "temperature_at_model_levels"),
+        vertical=True,
+    )
+    PARITY_NOTE = HEIGHT_NOTE
+
+    def __init__(self, *, height: float = 2.0, specific_humidity_at_height_level: str = "2q", dewpoint_temperature_at_height_level: str = "2d",
+                 surface_pressure: str = "sp", specific_humidity_at_model_levels: str = "q", temperature_at_model_levels: str = "t",
+                 model_level_AB: Any,
+                 return_inputs: Any = ["specific_humidity_at_height_level", "dewpoint_temperature_at_height_level", "surface_pressure"]) -> None:
+        self.return_inputs = return_inputs
+        self.height = float(height)
+        self.specific_humidity_at_height_level = specific_humidity_at_height_level
+        self.dewpoint_temperature_at_height_level = dewpoint_temperature_at_height_level
+        self.surface_pressure = surface_pressure
+        self.specific_humidity_at_model_levels = specific_humidity_at_model_levels
+        self.temperature_at_model_levels = temperature_at_model_levels
+        self._set_coefficients(model_level_AB)
+        super().__init__()
+
+    def forward_transform(self, specific_humidity_at_height_level: Any, surface_pressure: Any, specific_humidity_at_model_levels: Any,
+                          temperature_at_model_levels: Any) -> Iterator[Any]:
+        p, (q,) = self._pressure_at_height_level(temperature_at_model_levels, specific_humidity_at_model_levels, surface_pressure,
+                                                 specific_humidity_at_height_level)
+        yield self._combine(native.COMB_Q_TO_D, [q, p], specific_humidity_at_height_level, self.dewpoint_temperature_at_height_level)
+
+    def backward_transform(self, dewpoint_temperature_at_height_level: Any, surface_pressure: Any, specific_humidity_at_model_levels: Any,
+                           temperature_at_model_levels: Any) -> Iterator[Any]:
+        p, (td,) = self._pressure_at_height_level(temperature_at_model_levels, specific_humidity_at_model_levels, surface_pressure,
+                                                  dewpoint_temperature_at_height_level)
+        yield self._combine(native.COMB_D_TO_Q, [td, p], dewpoint_temperature_at_height_level, self.specific_humidity_at_height_level)
+
+
+filter_registry.register("q_to_d_height", SpecificToDewpointAtHeightLevel)
+filter_registry.register("d_to_q_height", SpecificToDewpointAtHeightLevel.reversed)

@@ -41,7 +41,7 @@ CMP_GT, CMP_LT, CMP_EQ, CMP_NE, CMP_GE, CMP_LE, CMP_NOTNAN, CMP_ISNAN = range(8)
 RED_MIN, RED_MAX, RED_NANCOUNT, RED_MINMAX = range(4)
 (COMB_SNOW_DEPTH_M, COMB_SNOW_COVER, COMB_COS_SIN, COMB_ATAN2, COMB_W_TO_WZ, COMB_WZ_TO_W, COMB_SUM, COMB_SUB, COMB_XY_TO_POLAR,
  COMB_POLAR_TO_XY, COMB_OPERA_CLIP, COMB_OPERA_PREPROCESS, COMB_ORAS6, COMB_LOOKUP, COMB_R_TO_D, COMB_D_TO_R, COMB_Q_TO_R,
- COMB_R_TO_Q) = range(18)
+ COMB_R_TO_Q, COMB_Q_TO_D, COMB_D_TO_Q) = range(20)
 # what a level of a COMB_ORAS6 stack holds (ATX_ORAS6_* of atx.h)
 ORAS6_KEEP, ORAS6_ZERO, ORAS6_TEMPERATURE, ORAS6_CELSIUS, ORAS6_HEAT, ORAS6_SURFACE = range(6)
 COMB_DEGREES = 1
@@ -94,6 +94,10 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
         c_int,
         [c_int, POINTER(c_void_p), c_int32, POINTER(c_void_p), c_int32, c_int64, c_int64, c_int64, c_int, c_int, c_void_p,
          c_int32, c_void_p],
+    ),
+    "atx_pressure_at_height_stack": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_double, c_void_p, c_void_p],
     ),
     "atx_mask_build": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_double, c_int, c_void_p]),
     "atx_mask_count": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
@@ -397,6 +401,20 @@ def combine_stack(op: int, inputs, outputs, *, n_pts, n_lev, pitch, layout, leve
         assert level_param.numel() >= (2 if op == COMB_LOOKUP else n_lev)
     _call("atx_combine_stack", op, ins, len(inputs), outs, len(outputs), n_pts, n_lev, pitch, dtype_code(dtype), layout,
           _ptr(level_param), flags, _stream())
+
+
+def pressure_at_height_stack(t, q, sp, A, B, out, *, n_pts, n_lev, pitch, layout, height: float) -> None:
+    """``out[p]``: the pressure at ``height`` metres above the ground of every point, from the model-level stacks ``t`` and ``q`` (level 0
+    the top one, same pitch and layout), the surface pressure ``sp`` and the half-level coefficients ``A``, ``B`` (float64, n_lev + 1
+    each) — ``atx_pressure_at_height_stack``.  ``sp`` and ``out`` are contiguous ``[n_pts]`` tensors of the stacks' dtype."""
+    dtype = t.dtype
+    assert q.dtype == dtype and sp.dtype == dtype and out.dtype == dtype
+    assert q.stride(0) == t.stride(0) == pitch
+    assert sp.is_contiguous() and out.is_contiguous() and sp.numel() >= n_pts and out.numel() >= n_pts
+    for c in (A, B):
+        assert c.dtype == torch.float64 and c.is_contiguous() and c.numel() == n_lev + 1 and c.device == t.device
+    _call("atx_pressure_at_height_stack", _ptr(t), _ptr(q), _ptr(sp), _ptr(A), _ptr(B), n_pts, n_lev, pitch, dtype_code(dtype), layout,
+          float(height), _ptr(out), _stream())
 
 
 def mask_build(m, mask, *, n, stride=1, cmp, threshold=0.0) -> None:

@@ -68,7 +68,10 @@
 extern "C" {
 #endif
 
-#define ATX_VERSION 420 /* 0.4.2 — round 6: nothing changed but two relaxations — the declarations carry ATX_API (the library exports nothing else),
+#define ATX_VERSION 420 /* 0.4.2 — additions only, so the number stays: atx_pressure_at_height_stack (the first vertical reduction, one value
+                           * per model column) and two multi-input operators, ATX_COMB_Q_TO_D / ATX_COMB_D_TO_Q; no existing signature, enum
+                           * value or layout changed.
+                           * round 6: nothing changed but two relaxations — the declarations carry ATX_API (the library exports nothing else),
                            * and zero-element buffers may be NULL (see Conventions).
                            * round 5: no signature, enum or layout changed.  The float64 library functions are the library's own routines now
                            * (ATX_OP_EXP, ATX_OP_LOG, the tanh of ATX_COMB_SNOW_COVER, the polynomials of ATX_COMB_COS_SIN): results may differ from 0.4.1 in the
@@ -317,7 +320,10 @@ typedef enum {
                                   pressure operand p = 100*level_param[l] (levelist, hPa)   R: filters/fields/q_to_r.py:70-75, q_height.py:117-121 */
     ATX_COMB_R_TO_Q = 17,      /* (r, t) or (r, t, p) -> eps e/(p - (1-eps) e), e = r*es_mixed(t)/100; NaN where p - e < 1e-4
                                                                                          R: q_to_r.py:77-83, q_height.py:138-142           */
-    ATX_COMB_COUNT_ = 18
+    ATX_COMB_Q_TO_D = 18,      /* (q, p) -> dewpoint: q == 0 -> 1e-8 first (on the operand, not in the input); e = p q/(eps + (1-eps) q), then
+                                  the inverse of es_water as ATX_COMB_R_TO_D               R: q_height.py:466-475 (EPS_SPECIFIC, :25)        */
+    ATX_COMB_D_TO_Q = 19,      /* (td, p) -> eps e/(p - (1-eps) e), e = es_water(td); NaN where p - e < 1e-4   R: q_height.py:511-514      */
+    ATX_COMB_COUNT_ = 20
 } atx_comb;
 #define ATX_COMB_DEGREES 1
 #define ATX_COMB_MAX_INPUTS 8
@@ -336,6 +342,18 @@ typedef enum {
 ATX_API int atx_combine_stack(int op, const void* const* inputs, int32_t n_in, void* const* outputs, int32_t n_out,
                               int64_t n_pts, int64_t n_lev, int64_t pitch, int dtype, int layout,
                               const double* level_param, int32_t flags, void* stream);
+
+/* ---- vertical reductions ------------------------------------------------------ */
+/* out[p] = the pressure (Pa) at `height` metres above the ground of point p, from the model-level temperature `t` and specific humidity
+ * `q` (two stacks of n_lev levels sharing pitch and layout, level 0 the TOP level: the reference orders them level="ascending"
+ * first), the surface pressure `sp` (device [n_pts], dtype) and the hybrid half-level coefficients A, B (DEVICE double[n_lev + 1]).
+ * earthkit-meteo's vertical.pressure_at_height_levels with alpha_top="ifs" and the moist gas constant Rd (1 - q) + Rv q, restated:
+ * the statement is in atx_vertical.hip.  Evaluated in float64 for both dtypes; `out` is device [n_pts], dtype.  Every column is
+ * walked to the top (the level count of the statement spans the whole column).
+ *   R: filters/fields/q_height.py:203-213, :416-426 -> vertical.pressure_at_height_levels */
+ATX_API int atx_pressure_at_height_stack(const void* t, const void* q, const void* sp, const double* A, const double* B,
+                                         int64_t n_pts, int64_t n_lev, int64_t pitch, int dtype, int layout, double height,
+                                         void* out, void* stream);
 
 /* ---- masks ------------------------------------------------------------------ */
 

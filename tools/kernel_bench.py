@@ -43,6 +43,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--levels", type=int, default=137)
+    ap.add_argument("--only-vertical", action="store_true", help="only the column kernel (atx_pressure_at_height_stack) rows")
     args = ap.parse_args()
     graft.load_package()
     from anemoi_transform_amd import interp, native
@@ -55,7 +56,6 @@ def main():
     L = args.levels
     src_grid, tgt_grid = lookup("o1280"), lookup("0.25")
     n_src, n_tgt = len(src_grid["latitudes"]), len(tgt_grid["latitudes"])
-    idx, w = interp.knn_inverse_distance(src_grid, tgt_grid, k=4)
     res = {}
 
     def record(name, ms, alg_bytes, note=""):
@@ -63,7 +63,37 @@ def main():
                      "note": note}
         print(f"{name:42s} {ms:9.4f} ms  {alg_bytes / ms / 1e6:9.1f} GB/s  frac {alg_bytes / (ms * 1e-3) / PEAK:.3f}  {note}", flush=True)
 
+    def vertical_rows(tdt, B, tag):
+        """The pressure at 2 m and at 1500 m (interpolation between full levels) from L-level t and q stacks, both layouts: one column
+        walk per point, two stacks read, one field written — algorithmic bytes 2·L·N·B + 2·N·B (sp in, p out)."""
+        eta = torch.cat([torch.zeros(1, dtype=torch.float64), torch.logspace(np.log10(2e-4), 0.0, L, dtype=torch.float64)])
+        Bc = torch.clamp((eta - 0.2) / 0.8, 0.0, 1.0) ** 1.5
+        Ac, Bc = (101325.0 * (eta - Bc) * 0.9).to(dev), Bc.to(dev)
+        sp = (60000.0 + 45000.0 * torch.rand(n_src, device=dev)).to(tdt)
+        p = torch.empty(n_src, dtype=tdt, device=dev)
+        for layout, lname in ((COLUMNS, "columns"), (FIELDS, "fields")):
+            t, q = Stack.empty(n_src, L, tdt, dev, layout, zero=True), Stack.empty(n_src, L, tdt, dev, layout, zero=True)
+            tv = t.data[:, :L] if layout == COLUMNS else t.data
+            qv = q.data[:, :L] if layout == COLUMNS else q.data
+            tv.uniform_(200.0, 300.0)
+            qv.copy_(torch.pow(10.0, -6.0 + 4.0 * torch.rand(qv.shape, device=dev)))
+            for h in (2.0, 1500.0):
+                record(f"pressure_at_height {h:g} m {tag} {lname}", timeit(lambda: native.pressure_at_height_stack(
+                       t.data, q.data, sp, Ac, Bc, p, n_pts=n_src, n_lev=L, pitch=t.pitch, layout=layout, height=h)),
+                       2 * L * n_src * B + 2 * n_src * B, "q_to_r_height / q_to_d_height: one column walk per point, one log per level")
+            del t, q
+        torch.cuda.empty_cache()
+
+    if args.only_vertical:
+        for tdt, B, tag in ((torch.float32, 4, "f32"), (torch.float64, 8, "f64")):
+            vertical_rows(tdt, B, tag)
+        if args.out:
+            json.dump(res, open(args.out, "w"), indent=1)
+        return
+
+    idx, w = interp.knn_inverse_distance(src_grid, tgt_grid, k=4)
     for tdt, npdt, B, tag in ((torch.float32, np.float32, 4, "f32"), (torch.float64, np.float64, 8, "f64")):
+        vertical_rows(tdt, B, tag)
         x = bench.synth_stack(src_grid, L, tdt, dev, 0, COLUMNS)
         U4, U1 = int(np.unique(idx).size), int(np.unique(idx[:, 0]).size)
         # ---- regrid variants
