@@ -33,6 +33,7 @@ import torch
 
 from . import native
 from . import stack as _stack
+from .projections import REGULAR_LATLON
 from .stack import COLUMNS, Stack
 
 LOG = logging.getLogger(__name__)
@@ -72,8 +73,10 @@ class Geography:
     def mars_grid(self) -> None:
         return None
 
-    def projection(self) -> None:
-        return None
+    def projection(self) -> str | None:
+        """The PROJ string earthkit-data gives a regular latitude / longitude grid (an ``ArrayField`` built from distinct
+        latitudes and longitudes, and the fields derived from it on the same grid); ``None`` for every other field."""
+        return self._owner.projection()
 
 
 class _MetadataView:
@@ -149,6 +152,10 @@ class Field:
     def values(self) -> np.ndarray:
         return self.to_numpy(flatten=True)
 
+    def projection(self) -> str | None:
+        """R: rotate_winds.py:80 reads ``str(x_wind.projection())`` — see ``Geography.projection``."""
+        return None
+
     def to_latlon(self, flatten: bool = True) -> dict[str, np.ndarray]:
         lat, lon = self.grid_points()
         if not flatten:
@@ -208,8 +215,9 @@ class ArrayField(Field):
     """A host field: array + metadata dict + per-point coordinates."""
 
     def __init__(self, values: Any, metadata: dict[str, Any], latitudes: np.ndarray, longitudes: np.ndarray,
-                 mars: bool = False) -> None:
+                 mars: bool = False, regular_latlon: bool = False) -> None:
         self._values = np.asarray(values)
+        self._regular_latlon = regular_latlon  # built from distinct latitudes / longitudes: earthkit-data's eqc projection
         self._md = dict(metadata)
         # plain list-of-dicts fields expose no "mars" namespace; the reference's MarsUserMetadata
         # test fixture (R: tests/conftest.py:27-38) does — `mars=True` reproduces it
@@ -235,12 +243,13 @@ class ArrayField(Field):
             values = values.astype(np.float64)
         lat = np.asarray(spec["latitudes"], dtype=np.float64)
         lon = np.asarray(spec["longitudes"], dtype=np.float64)
-        if values.ndim == 2 and lat.ndim == 1 and lon.ndim == 1 and values.shape == (len(lat), len(lon)):
+        regular = values.ndim == 2 and lat.ndim == 1 and lon.ndim == 1 and values.shape == (len(lat), len(lon))
+        if regular:
             lat2, lon2 = np.meshgrid(lat, lon, indexing="ij")
             lat, lon = lat2.reshape(-1), lon2.reshape(-1)
         else:
             lat, lon = lat.reshape(-1), lon.reshape(-1)
-        return cls(values, spec, lat, lon, mars=mars)
+        return cls(values, spec, lat, lon, mars=mars, regular_latlon=regular)
 
     def _namespace(self, namespace: str) -> dict[str, Any]:
         if not self._mars:
@@ -252,6 +261,9 @@ class ArrayField(Field):
 
     def grid_points(self) -> tuple[np.ndarray, np.ndarray]:
         return self._latitudes, self._longitudes
+
+    def projection(self) -> str | None:
+        return REGULAR_LATLON if self._regular_latlon else None
 
     def _lookup(self, key: str) -> Any:
         return self._md.get(key, MISSING)
@@ -328,6 +340,11 @@ class DerivedField(Field):
         if self._latitudes is not None:
             return self._latitudes, self._longitudes
         return self._template.grid_points()
+
+    def projection(self) -> str | None:
+        if self._latitudes is not None or not isinstance(self._template, Field):  # a new grid, or a foreign template
+            return None
+        return self._template.projection()
 
     # ---- metadata: overrides are consulted before the template (R: fields.py:532-546) ----
     def _lookup(self, key: str) -> Any:

@@ -9,6 +9,7 @@ Registered names:
                   rodeo_opera_clipping, rodeo_opera_preprocessing, oras6_clipping, land_parameters,
                   r_to_d, d_to_r, q_to_r, r_to_q, q_to_r_height_with_p, r_to_q_height_with_p
                                                              (multi-input, filters/domain.py)
+                  rotate_winds, unrotate_winds               (vector frames, filters/winds.py)
                   rename_fields, clear_step, repeat_members, earthkitfieldlambda, empty,
                   icon_refinement_level   (re-labelling / re-listing, filters/metadata.py)
   dispatchers     mask (alias apply_mask), remove_nans (alias drop_nans),
@@ -34,6 +35,7 @@ from . import metadata as _metadata  # noqa: E402
 from . import multi as _multi  # noqa: E402
 from . import pointwise as _pointwise  # noqa: E402
 from . import regrid as _regrid  # noqa: E402
+from . import winds as _winds  # noqa: E402
 from .masks import MaskVariable, RemoveNaNs as RemoveNaNsFields
 from .pointwise import Clipper, ImputeNaNs as ImputeNaNsFields, Orography
 

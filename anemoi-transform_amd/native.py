@@ -46,6 +46,7 @@ RED_MIN, RED_MAX, RED_NANCOUNT, RED_MINMAX = range(4)
 ORAS6_KEEP, ORAS6_ZERO, ORAS6_TEMPERATURE, ORAS6_CELSIUS, ORAS6_HEAT, ORAS6_SURFACE = range(6)
 COMB_DEGREES = 1
 COMB_MAX_INPUTS = 8
+FRAME_ROTATION, FRAME_GENERAL = 0, 1  # atx_frame: the kind of an atx_rotate_vectors_stack table (2 or 4 words per point)
 
 OK, EINVAL, ESHAPE, ENOTIMPL, EHIP, EALIGN, EWORKSPACE, ECOMM = 0, -1, -2, -3, -4, -5, -6, -7
 COMM_ID_BYTES = 128
@@ -98,6 +99,9 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     "atx_pressure_at_height_stack": (
         c_int,
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_double, c_void_p, c_void_p],
+    ),
+    "atx_rotate_vectors_stack": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int, c_int, c_void_p],
     ),
     "atx_mask_build": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_double, c_int, c_void_p]),
     "atx_mask_count": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
@@ -415,6 +419,19 @@ def pressure_at_height_stack(t, q, sp, A, B, out, *, n_pts, n_lev, pitch, layout
         assert c.dtype == torch.float64 and c.is_contiguous() and c.numel() == n_lev + 1 and c.device == t.device
     _call("atx_pressure_at_height_stack", _ptr(t), _ptr(q), _ptr(sp), _ptr(A), _ptr(B), n_pts, n_lev, pitch, dtype_code(dtype), layout,
           float(height), _ptr(out), _stream())
+
+
+def rotate_vectors_stack(x, y, x_out, y_out, frame, frame_kind: int, *, n_pts, n_lev, pitch, layout) -> None:
+    """``(x_out, y_out)``: the vectors ``(x, y)`` of two stacks (same dtype, pitch and layout) mapped by the per-point table
+    ``frame`` (``[n_pts, 2]`` for ``FRAME_ROTATION``, ``[n_pts, 4]`` for ``FRAME_GENERAL``, contiguous, the stacks' dtype) —
+    ``atx_rotate_vectors_stack``.  ``x_out is x`` and ``y_out is y`` (in place) are allowed."""
+    dtype = x.dtype
+    width = 2 if frame_kind == FRAME_ROTATION else 4
+    for t in (y, x_out, y_out):
+        assert t.dtype == dtype and t.stride(0) == x.stride(0) == pitch
+    assert frame.dtype == dtype and frame.is_contiguous() and frame.numel() == n_pts * width and frame.device == x.device
+    _call("atx_rotate_vectors_stack", _ptr(x), _ptr(y), _ptr(x_out), _ptr(y_out), _ptr(frame), int(frame_kind), n_pts, n_lev, pitch,
+          dtype_code(dtype), layout, _stream())
 
 
 def mask_build(m, mask, *, n, stride=1, cmp, threshold=0.0) -> None:

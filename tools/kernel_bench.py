@@ -44,6 +44,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--levels", type=int, default=137)
     ap.add_argument("--only-vertical", action="store_true", help="only the column kernel (atx_pressure_at_height_stack) rows")
+    ap.add_argument("--only-rotate", action="store_true", help="only the vector-frame kernel (atx_rotate_vectors_stack) rows")
     args = ap.parse_args()
     graft.load_package()
     from anemoi_transform_amd import interp, native
@@ -84,6 +85,30 @@ def main():
             del t, q
         torch.cuda.empty_cache()
 
+    def rotate_rows(tdt, B, tag):
+        """rotate_winds: u / v stacks of 1 and L levels, both layouts, both frame kinds — algorithmic bytes 4·N·L·B + N·F·B (two
+        stacks in, two out, the per-point frame table of F words once)."""
+        for n_lev in (1, L):
+            for layout, lname in ((COLUMNS, "columns"), (FIELDS, "fields")):
+                x, y = Stack.empty(n_src, n_lev, tdt, dev, layout, zero=True), Stack.empty(n_src, n_lev, tdt, dev, layout, zero=True)
+                x.data.normal_()
+                y.data.normal_()
+                xo, yo = x.new_like(), y.new_like()
+                for kind, F, kname in ((native.FRAME_ROTATION, 2, "rotation"), (native.FRAME_GENERAL, 4, "general")):
+                    frame = torch.rand(n_src, F, dtype=tdt, device=dev)
+                    record(f"rotate_vectors {kname} L{n_lev} {tag} {lname}", timeit(lambda: native.rotate_vectors_stack(
+                           x.data, y.data, xo.data, yo.data, frame, kind, n_pts=n_src, n_lev=n_lev, pitch=x.pitch, layout=layout)),
+                           4 * n_src * n_lev * B + n_src * F * B, "rotate_winds / unrotate_winds: per-point frame, every level")
+                del x, y, xo, yo
+                torch.cuda.empty_cache()
+
+    if args.only_rotate:
+        for tdt, B, tag in ((torch.float32, 4, "f32"), (torch.float64, 8, "f64")):
+            rotate_rows(tdt, B, tag)
+        if args.out:
+            json.dump(res, open(args.out, "w"), indent=1)
+        return
+
     if args.only_vertical:
         for tdt, B, tag in ((torch.float32, 4, "f32"), (torch.float64, 8, "f64")):
             vertical_rows(tdt, B, tag)
@@ -94,6 +119,7 @@ def main():
     idx, w = interp.knn_inverse_distance(src_grid, tgt_grid, k=4)
     for tdt, npdt, B, tag in ((torch.float32, np.float32, 4, "f32"), (torch.float64, np.float64, 8, "f64")):
         vertical_rows(tdt, B, tag)
+        rotate_rows(tdt, B, tag)
         x = bench.synth_stack(src_grid, L, tdt, dev, 0, COLUMNS)
         U4, U1 = int(np.unique(idx).size), int(np.unique(idx[:, 0]).size)
         # ---- regrid variants
