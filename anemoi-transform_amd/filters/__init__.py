@@ -10,6 +10,7 @@ Registered names:
                   r_to_d, d_to_r, q_to_r, r_to_q, q_to_r_height_with_p, r_to_q_height_with_p
                                                              (multi-input, filters/domain.py)
                   rotate_winds, unrotate_winds               (vector frames, filters/winds.py)
+  tabular         irregular_to_grid, assign_to_grid          (observation tables onto a grid, filters/tabular.py)
                   rename_fields, clear_step, repeat_members, earthkitfieldlambda, empty,
                   icon_refinement_level   (re-labelling / re-listing, filters/metadata.py)
   dispatchers     mask (alias apply_mask), remove_nans (alias drop_nans),
@@ -17,9 +18,12 @@ Registered names:
                   clip (alias clipper), impute_nans (alias replace_nans), rename
 
 The dispatchers pick the field filter from the configuration keys exactly as the
-reference does; configurations that select the reference's *tabular* (pandas)
-filters raise ``NotImplementedError`` — observations are outside this path
-(SURVEY.md §2.1 row 16).
+reference does; configurations that select the *tabular* (pandas) half of a
+dispatcher raise ``NotImplementedError``.  Observations enter the field path
+through ``irregular_to_grid`` (with ``assign_to_grid`` before it): a table goes
+to the device once and comes out as one HBM stack of gridded fields.  The rest
+of the reference's tabular family is per-row pandas bookkeeping with no field
+output and stays out.
 """
 
 from __future__ import annotations
@@ -35,6 +39,7 @@ from . import metadata as _metadata  # noqa: E402
 from . import multi as _multi  # noqa: E402
 from . import pointwise as _pointwise  # noqa: E402
 from . import regrid as _regrid  # noqa: E402
+from . import tabular as _tabular_filters  # noqa: E402
 from . import winds as _winds  # noqa: E402
 from .masks import MaskVariable, RemoveNaNs as RemoveNaNsFields
 from .pointwise import Clipper, ImputeNaNs as ImputeNaNsFields, Orography

@@ -103,6 +103,12 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     "atx_rotate_vectors_stack": (
         c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int, c_int, c_void_p],
     ),
+    "atx_obs_best_per_cell": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int64, c_void_p, c_int32, c_int64, c_int64, c_int64, c_int, c_int, c_int64,
+         c_double, c_void_p, c_void_p, c_void_p],
+    ),
+    "atx_obs_fill_stack": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int64, c_int32, c_int64, c_void_p, c_int64, c_int, c_void_p]),
     "atx_mask_build": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_double, c_int, c_void_p]),
     "atx_mask_count": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
     "atx_mask_to_index_workspace": (c_size_t, [c_int64]),
@@ -432,6 +438,34 @@ def rotate_vectors_stack(x, y, x_out, y_out, frame, frame_kind: int, *, n_pts, n
     assert frame.dtype == dtype and frame.is_contiguous() and frame.numel() == n_pts * width and frame.device == x.device
     _call("atx_rotate_vectors_stack", _ptr(x), _ptr(y), _ptr(x_out), _ptr(y_out), _ptr(frame), int(frame_kind), n_pts, n_lev, pitch,
           dtype_code(dtype), layout, _stream())
+
+
+def obs_best_per_cell(date_ns, cell, values, target_ns, best, winner, *, n_cells: int, before_ns: int, after_ns: int,
+                      closed_before: bool, closed_after: bool, freq_ns: int, weight: float) -> None:
+    """``winner[t, c]``: the row of the observation table that target ``t`` shows in cell ``c`` (-1: none) — ``atx_obs_best_per_cell``.
+    ``date_ns`` / ``cell``: int64 ``[n_obs]``; ``values``: float64 ``[n_cols, n_obs]`` (rows may be pitched); ``target_ns``: int64
+    ``[n_time]``; ``best`` (scratch, int64) and ``winner`` (int32): contiguous ``[n_time, n_cells]``."""
+    n_cols, n_obs = values.shape
+    n_time = target_ns.numel()
+    assert date_ns.dtype == cell.dtype == target_ns.dtype == best.dtype == torch.int64 and winner.dtype == torch.int32
+    assert values.dtype == torch.float64 and (values.stride(1) == 1 or n_obs <= 1)
+    assert date_ns.is_contiguous() and cell.is_contiguous() and target_ns.is_contiguous() and date_ns.numel() == cell.numel() == n_obs
+    assert best.is_contiguous() and winner.is_contiguous() and best.numel() == winner.numel() == n_time * n_cells
+    val_pitch = values.stride(0) if n_cols > 1 else max(n_obs, 1)
+    _call("atx_obs_best_per_cell", _ptr(date_ns), _ptr(cell), _ptr(values), n_obs, n_cols, val_pitch, _ptr(target_ns), n_time, n_cells,
+          int(before_ns), int(after_ns), int(bool(closed_before)), int(bool(closed_after)), int(freq_ns), float(weight), _ptr(best),
+          _ptr(winner), _stream())
+
+
+def obs_fill_stack(winner, values, out, *, n_time: int, n_cells: int, pitch: int, layout: int) -> None:
+    """``out`` (float64 stack of ``n_time * n_cols`` levels over ``n_cells`` points): level ``t * n_cols + j`` =
+    ``values[j, winner[t, :]]``, NaN where the winner is -1 — ``atx_obs_fill_stack``."""
+    n_cols, n_obs = values.shape
+    assert winner.dtype == torch.int32 and winner.is_contiguous() and winner.numel() == n_time * n_cells
+    assert values.dtype == out.dtype == torch.float64 and (values.stride(1) == 1 or n_obs <= 1)
+    assert out.numel() == 0 or out.stride(0) == pitch
+    val_pitch = values.stride(0) if n_cols > 1 else max(n_obs, 1)
+    _call("atx_obs_fill_stack", _ptr(winner), _ptr(values), n_obs, n_cols, val_pitch, n_time, n_cells, _ptr(out), pitch, layout, _stream())
 
 
 def mask_build(m, mask, *, n, stride=1, cmp, threshold=0.0) -> None:

@@ -1,0 +1,247 @@
+"""Observation tables onto a grid, in HBM (R: filters/tabular/irregular_to_grid.py).
+
+The reference loops over the target times on the host; per target it selects the rows of the window, scores them, keeps the
+best row per ``spatial_index`` with a pandas ``groupby().idxmin()`` and writes its values into float64 grids of NaN.  Here the
+table goes to the device once (a few columns of ``n_obs`` values), ``atx_obs_best_per_cell`` chooses the winning ROW of every
+(target, cell) with two order-independent atomic minima, and ``atx_obs_fill_stack`` gathers the winners' values into ONE stack of
+``n_time * n_cols`` levels — level ``t * n_cols + c`` is target ``t``, column ``c``, the reference's field order.
+
+What this module restates on the host is the bookkeeping around those two launches: the window strings the reference hands to
+``anemoi.utils.window.Window`` (``parse_window``), ``pd.Timedelta(time_freq)`` (``parse_frequency``), datetimes as int64
+nanoseconds (``to_ns``), ``spatial_index`` as int64 cells (``to_cells``) and the targets in order of first appearance
+(``unique_in_order``).  Arrays may be numpy arrays (uploaded) or device tensors (used in place).
+"""
+
+from __future__ import annotations
+
+import datetime
+import re
+from typing import Any, NamedTuple, Sequence
+
+import numpy as np
+import torch
+
+from . import native
+from . import stack as _stack
+from .stack import COLUMNS, Stack
+
+NAT = np.iinfo(np.int64).min  # numpy's / pandas' NaT as int64
+
+_UNIT_NS = {"s": 10**9, "m": 60 * 10**9, "h": 3600 * 10**9, "d": 86400 * 10**9}
+_OFFSET = re.compile(r"^([+-]?)(\d+)([smhd])$")
+_WINDOW = re.compile(r"^([(\[])([^,]*),([^,]*)([)\]])$")
+
+
+class Window(NamedTuple):
+    """``target + before_ns  <(=)  date  <(=)  target + after_ns``; an end is ``<=`` when its ``closed_*`` is true."""
+
+    before_ns: int
+    after_ns: int
+    closed_before: bool
+    closed_after: bool
+
+
+def _offset_ns(text: str, whole: str) -> int:
+    text = text.strip()
+    if text in ("0", "+0", "-0"):
+        return 0
+    m = _OFFSET.match(text)
+    if m is None:
+        raise ValueError(f"window {whole!r}: cannot read the offset {text!r} (expected <+-n><s|m|h|d> or 0)")
+    ns = int(m.group(2)) * _UNIT_NS[m.group(3)]
+    return -ns if m.group(1) == "-" else ns
+
+
+def parse_window(text: str) -> Window:
+    """``"(-6h, 0]"``, ``"[-3h, +3h)"`` ...: the subset ``( | [  <+-n><unit>, <+-n><unit>  ) | ]`` with units s / m / h / d of the
+    strings the reference passes to ``anemoi.utils.window.Window`` (R: irregular_to_grid.py:107-108).  A bare ``0`` is allowed;
+    anything else raises ``ValueError`` naming the string."""
+    if not isinstance(text, str):
+        raise ValueError(f"window {text!r}: expected a string such as '(-6h, 0]'")
+    m = _WINDOW.match(text.strip())
+    if m is None:
+        raise ValueError(f"window {text!r}: expected '(' or '[', two offsets separated by a comma, then ')' or ']'")
+    before, after = _offset_ns(m.group(2), text), _offset_ns(m.group(3), text)
+    if before > after:
+        raise ValueError(f"window {text!r}: the first offset lies after the second")
+    return Window(before, after, m.group(1) == "[", m.group(4) == "]")
+
+
+def parse_frequency(freq: Any) -> int:
+    """``pd.Timedelta(time_freq)`` in nanoseconds for ``"6h"``, ``"30m"``, ``"1d"``, ``"90s"`` (a ``timedelta`` /
+    ``np.timedelta64`` is taken as it is).  Must be positive."""
+    if isinstance(freq, datetime.timedelta):
+        ns = (freq.days * 86400 + freq.seconds) * 10**9 + freq.microseconds * 1000
+    elif isinstance(freq, np.timedelta64):
+        ns = int(freq.astype("timedelta64[ns]").astype(np.int64))
+    else:
+        m = re.match(r"^\s*(\d+)\s*([smhd]|min)\s*$", str(freq), flags=re.I)
+        if m is None:
+            raise ValueError(f"time_freq {freq!r}: expected <n><s|m|h|d>")
+        ns = int(m.group(1)) * _UNIT_NS[m.group(2).lower()[0]]
+    if ns <= 0:
+        raise ValueError(f"time_freq {freq!r} must be positive")
+    return ns
+
+
+def _host_array(column: Any) -> np.ndarray:
+    if hasattr(column, "dt") and getattr(column.dt, "tz", None) is not None:  # a tz-aware pandas Series: all times are UTC
+        column = column.dt.tz_convert(None)
+    if hasattr(column, "to_numpy"):
+        return column.to_numpy()
+    return np.asarray(column)
+
+
+def to_ns(column: Any) -> np.ndarray | torch.Tensor:
+    """A column of datetimes as int64 nanoseconds since the epoch, NaT = ``INT64_MIN``.  datetime64 arrays of any unit, pandas
+    Series, lists of datetimes or ISO strings; an int64 array or tensor is taken to BE nanoseconds already."""
+    if isinstance(column, torch.Tensor):
+        if column.dtype != torch.int64:
+            raise ValueError(f"a date tensor must hold int64 nanoseconds, got {column.dtype}")
+        return column.reshape(-1)
+    a = _host_array(column)
+    if a.dtype.kind == "i":
+        return np.ascontiguousarray(a.reshape(-1), dtype=np.int64)
+    try:
+        return np.ascontiguousarray(a.astype("datetime64[ns]").reshape(-1)).view(np.int64)
+    except (ValueError, TypeError) as e:
+        raise ValueError(f"cannot read a date column of dtype {a.dtype} as datetimes: {e}") from None
+
+
+def to_cells(column: Any) -> np.ndarray | torch.Tensor:
+    """``spatial_index`` as int64.  An integer column is taken as it is; a float column must hold whole numbers, its missing
+    (non-finite) entries become -1, which no grid has: ``groupby`` drops them in the reference."""
+    if isinstance(column, torch.Tensor):
+        c = column.reshape(-1)
+        if c.dtype in (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8):
+            return c.to(torch.int64)
+        if not c.dtype.is_floating_point:
+            raise ValueError(f"spatial_index must be an integer or float column, got {c.dtype}")
+        ok = torch.isfinite(c) & (c.abs() < 2.0**62)
+        if bool((ok & (c != torch.floor(c))).any()):
+            raise ValueError("spatial_index holds values that are not whole numbers")
+        return torch.where(ok, c, torch.full_like(c, -1.0)).to(torch.int64)
+    a = _host_array(column).reshape(-1)
+    if a.dtype.kind in "iu":
+        return np.ascontiguousarray(a, dtype=np.int64)
+    try:
+        a = a.astype(np.float64)
+    except (ValueError, TypeError):
+        raise ValueError(f"spatial_index must be an integer or float column, got {a.dtype}") from None
+    ok = np.isfinite(a) & (np.abs(a) < 2.0**62)
+    if np.any(a[ok] != np.floor(a[ok])):
+        raise ValueError("spatial_index holds values that are not whole numbers")
+    return np.where(ok, a, -1.0).astype(np.int64)
+
+
+def to_values(columns: Any) -> np.ndarray | torch.Tensor:
+    """The value columns as ONE float64 ``[n_cols, n_obs]`` array (a device tensor if any column is one)."""
+    if isinstance(columns, torch.Tensor):
+        v = columns.reshape(1, -1) if columns.dim() == 1 else columns
+        return v.to(torch.float64)
+    if isinstance(columns, np.ndarray) and columns.ndim == 2:
+        return np.ascontiguousarray(columns, dtype=np.float64)
+    columns = list(columns)
+    if any(isinstance(c, torch.Tensor) for c in columns):
+        dev = next(c.device for c in columns if isinstance(c, torch.Tensor))
+        rows = [c if isinstance(c, torch.Tensor) else torch.from_numpy(np.asarray(_host_array(c), dtype=np.float64)) for c in columns]
+        return torch.stack([r.reshape(-1).to(device=dev, dtype=torch.float64) for r in rows])
+    try:
+        rows = [np.asarray(_host_array(c), dtype=np.float64).reshape(-1) for c in columns]
+    except (ValueError, TypeError) as e:
+        raise ValueError(f"value columns must be numeric (they are read as float64): {e}") from None
+    if len({r.size for r in rows}) > 1:
+        raise ValueError(f"value columns differ in length: {[r.size for r in rows]}")
+    return np.stack(rows) if rows else np.zeros((0, 0))
+
+
+def unique_in_order(ns: np.ndarray | torch.Tensor) -> np.ndarray:
+    """The distinct values of an int64 column in order of FIRST APPEARANCE (``Series.unique()``), as a host array."""
+    if isinstance(ns, torch.Tensor):
+        if ns.numel() == 0:
+            return np.zeros(0, dtype=np.int64)
+        uniq, inverse = torch.unique(ns, sorted=True, return_inverse=True)
+        first = torch.full((uniq.numel(),), ns.numel(), dtype=torch.int64, device=ns.device)
+        first.scatter_reduce_(0, inverse, torch.arange(ns.numel(), device=ns.device), reduce="amin")
+        return uniq[torch.argsort(first)].cpu().numpy()
+    uniq, first = np.unique(ns, return_index=True)
+    return uniq[np.argsort(first, kind="stable")]
+
+
+def _device(x: np.ndarray | torch.Tensor, dev: torch.device) -> torch.Tensor:
+    t = torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x
+    return t.to(dev).contiguous()
+
+
+def _prepare(date_ns, cell, values, target_ns, window, freq, weight, dev):
+    dev = _stack.device() if dev is None else dev
+    window = parse_window(window) if isinstance(window, str) else Window(*window)
+    freq_ns = freq if isinstance(freq, (int, np.integer)) else parse_frequency(freq)
+    if not 0.0 <= float(weight) <= 1.0:
+        raise ValueError("nan_score_weight must be in the range [0.0, 1.0]")
+    date_ns, cell, target_ns = _device(to_ns(date_ns), dev), _device(to_cells(cell), dev), _device(to_ns(target_ns), dev)
+    values = to_values(values)
+    values = _device(values, dev) if values.shape[1] > 0 else torch.empty(tuple(values.shape), dtype=torch.float64, device=dev)
+    n_cols, n_obs = values.shape
+    if n_cols == 0:
+        raise ValueError("At least one column must be specified")
+    if date_ns.numel() != n_obs or cell.numel() != n_obs:
+        raise ValueError(f"columns differ in length: date {date_ns.numel()}, spatial_index {cell.numel()}, values {n_obs}")
+    return date_ns, cell, values, target_ns, window, int(freq_ns), float(weight), dev
+
+
+def _winners(date_ns, cell, values, target_ns, window, freq_ns, weight, n_cells, dev) -> torch.Tensor:
+    n_time = target_ns.numel()
+    best = torch.empty((n_time, n_cells), dtype=torch.int64, device=dev)
+    winner = torch.empty((n_time, n_cells), dtype=torch.int32, device=dev)
+    native.obs_best_per_cell(date_ns, cell, values, target_ns, best, winner, n_cells=n_cells, before_ns=window.before_ns,
+                             after_ns=window.after_ns, closed_before=window.closed_before, closed_after=window.closed_after,
+                             freq_ns=freq_ns, weight=weight)
+    return winner
+
+
+def best_per_cell(date_ns: Any, cell: Any, values: Any, target_ns: Any, *, n_cells: int, window: Any = "(-6h, 0]", freq: Any = "6h",
+                  weight: float = 0.0, dev: torch.device | None = None) -> torch.Tensor:
+    """``winner[t, c]`` (device int32 ``[n_time, n_cells]``): the row that target ``t`` shows in cell ``c``, -1 for none — the
+    row of smallest score ``|date - target| / freq`` (``weight`` > 0: ``(1 - w) * that + w * nan_count / n_cols``) among the rows
+    of the cell whose date lies in ``window`` around the target and whose values are not all NaN; among equal scores the first
+    row of the table (R: irregular_to_grid.py:209-317)."""
+    date_ns, cell, values, target_ns, window, freq_ns, weight, dev = _prepare(date_ns, cell, values, target_ns, window, freq, weight, dev)
+    return _winners(date_ns, cell, values, target_ns, window, freq_ns, weight, int(n_cells), dev)
+
+
+def grid_observations(date_ns: Any, cell: Any, values: Any, target_ns: Any, *, n_cells: int, window: Any = "(-6h, 0]",
+                      freq: Any = "6h", weight: float = 0.0, layout: int = COLUMNS, dev: torch.device | None = None,
+                      return_winner: bool = False) -> Stack | tuple[Stack, torch.Tensor]:
+    """The float64 stack of ``n_time * n_cols`` levels over ``n_cells`` points whose level ``t * n_cols + c`` is column ``c`` of the
+    best observation per cell for target ``t``, NaN where nothing was observed (R: irregular_to_grid.py:113-161).
+
+    ``date_ns`` / ``target_ns``: datetimes or int64 nanoseconds; ``cell``: the grid index of every row; ``values``: the columns
+    (a sequence of 1-D arrays or one ``[n_cols, n_obs]`` array).  numpy arrays are uploaded, device tensors used in place.
+    ``window``: a string for ``parse_window`` or a ``Window``; ``freq``: a string for ``parse_frequency`` or nanoseconds."""
+    date_ns, cell, values, target_ns, window, freq_ns, weight, dev = _prepare(date_ns, cell, values, target_ns, window, freq, weight, dev)
+    n_cells, n_time, n_cols = int(n_cells), target_ns.numel(), values.shape[0]
+    winner = _winners(date_ns, cell, values, target_ns, window, freq_ns, weight, n_cells, dev)
+    out = Stack.empty(n_cells, n_time * n_cols, torch.float64, dev, layout)
+    native.obs_fill_stack(winner, values, out.data, n_time=n_time, n_cells=n_cells, pitch=out.pitch, layout=layout)
+    return (out, winner) if return_winner else out
+
+
+def nearest_grid_index(grid_lat: np.ndarray, grid_lon: np.ndarray, lat: Any, lon: Any) -> tuple[np.ndarray, np.ndarray]:
+    """``cKDTree(column_stack([grid_lat, grid_lon])).query(column_stack([lat, lon]))`` on the device: ``(distances, indices)`` of
+    the nearest grid point in the PLANE of (latitude, longitude) degrees, not on the sphere (R: assign_to_grid.py:54-60).
+
+    ``interp.device_knn`` searches points of [-1, 1]^3: both sets go in as ``(lat / 512, lon / 512, 0)``.  Scaling by a power of
+    two is exact, so ``sqrt(d2) * 512`` is cKDTree's distance bit for bit, and rows with exactly equidistant grid points are handed
+    to cKDTree itself (``ties="ckdtree"``)."""
+    from .interp import device_knn
+
+    def plane(a: Any, b: Any) -> np.ndarray:
+        a, b = (np.asarray(_host_array(x), dtype=np.float64).reshape(-1) for x in (a, b))
+        return np.column_stack([a / 512.0, b / 512.0, np.zeros_like(a)])
+
+    grid, points = plane(grid_lat, grid_lon), plane(lat, lon)
+    if np.abs(grid).max(initial=0.0) > 1.0 or np.abs(points[np.isfinite(points)]).max(initial=0.0) > 1.0:
+        raise ValueError("latitudes / longitudes beyond +-512 degrees")
+    indices, d2, _ = device_knn(grid, points, 1)
+    return np.sqrt(d2[:, 0]) * 512.0, indices[:, 0]

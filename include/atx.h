@@ -68,7 +68,8 @@
 extern "C" {
 #endif
 
-#define ATX_VERSION 420 /* 0.4.2 — additions only, so the number stays: atx_rotate_vectors_stack (vector components between projection
+#define ATX_VERSION 420 /* 0.4.2 — additions only, so the number stays: atx_obs_best_per_cell / atx_obs_fill_stack (observation tables
+                           * onto a grid: a keyed arg-min and the gather that fills the stack); atx_rotate_vectors_stack (vector components between projection
                            * frames, a per-point table shared by every level) with its atx_frame enum; atx_pressure_at_height_stack (the
                            * first vertical reduction, one value per model column) and two multi-input operators, ATX_COMB_Q_TO_D /
                            * ATX_COMB_D_TO_Q; no existing signature, enum value or layout changed.
@@ -372,6 +373,33 @@ ATX_API int atx_pressure_at_height_stack(const void* t, const void* q, const voi
 typedef enum { ATX_FRAME_ROTATION = 0, ATX_FRAME_GENERAL = 1 } atx_frame;
 ATX_API int atx_rotate_vectors_stack(const void* x, const void* y, void* x_out, void* y_out, const void* frame, int frame_kind,
                                      int64_t n_pts, int64_t n_lev, int64_t pitch, int dtype, int layout, void* stream);
+
+/* ---- observation gridding ---------------------------------------------------- */
+/* winner[t * n_cells + c] = the row of the observation table that target time t shows in grid cell c, -1 when none: a keyed
+ * arg-min over scattered rows (irregular_to_grid).  Row r takes part in target t when
+ *   date_ns[r] and target_ns[t] are not NaT (INT64_MIN), not every one of its n_cols values is NaN, 0 <= cell[r] < n_cells, and
+ *   target_ns[t] + before_ns  <  date_ns[r]  <  target_ns[t] + after_ns     (<= at an end whose closed_* flag is non-zero);
+ * its score is  s = (double)|date_ns[r] - target_ns[t]| / (double)freq_ns,  and for w > 0
+ *   (1.0 - w) * s + w * ((double)nan_count / (double)n_cols)                (two products, one sum, no contraction);
+ * the winner of a cell is the row of smallest score, the SMALLEST ROW INDEX among equal scores (pandas idxmin on a table in
+ * row order).  A row may win in several targets.  Cells outside [0, n_cells) are skipped, never used as an address.
+ * Two order-independent atomic minima (the score's bit pattern, then the row index): the result is deterministic.
+ *   date_ns, cell   device int64 [n_obs]           values      device double, n_cols columns of n_obs, column j at values + j * val_pitch
+ *   target_ns       device int64 [n_time]          best        device scratch, n_time * n_cells uint64 (initialised by the call)
+ *   winner          device int32 [n_time * n_cells] (initialised by the call: n_obs == 0 leaves it all -1)
+ * n_obs >= 2^31, freq_ns <= 0 or w outside [0, 1]: ATX_EINVAL.
+ *   R: filters/tabular/irregular_to_grid.py:139-159 -> select_window :209-254, get_nearest_obs :256-317 */
+ATX_API int atx_obs_best_per_cell(const int64_t* date_ns, const int64_t* cell, const double* values, int64_t n_obs, int32_t n_cols,
+                                  int64_t val_pitch, const int64_t* target_ns, int32_t n_time, int64_t n_cells, int64_t before_ns,
+                                  int64_t after_ns, int closed_before, int closed_after, int64_t freq_ns, double w,
+                                  uint64_t* best, int32_t* winner, void* stream);
+
+/* Level t * n_cols + j of the float64 stack `out` (n_time * n_cols levels over n_cells points, either layout) at point c =
+ * values[j * val_pitch + winner[t * n_cells + c]], NaN where the winner is not a row of the table (-1).  The padding of `out` is
+ * written with zeros.
+ *   R: filters/tabular/irregular_to_grid.py:135 (grids of NaN), :190-207 (_fill_grids), :163-188 (fields time-major, then column) */
+ATX_API int atx_obs_fill_stack(const int32_t* winner, const double* values, int64_t n_obs, int32_t n_cols, int64_t val_pitch,
+                               int32_t n_time, int64_t n_cells, double* out, int64_t pitch, int layout, void* stream);
 
 /* ---- masks ------------------------------------------------------------------ */
 

@@ -45,6 +45,7 @@ def main():
     ap.add_argument("--levels", type=int, default=137)
     ap.add_argument("--only-vertical", action="store_true", help="only the column kernel (atx_pressure_at_height_stack) rows")
     ap.add_argument("--only-rotate", action="store_true", help="only the vector-frame kernel (atx_rotate_vectors_stack) rows")
+    ap.add_argument("--only-obs", action="store_true", help="only the observation-gridding rows (atx_obs_best_per_cell, atx_obs_fill_stack)")
     args = ap.parse_args()
     graft.load_package()
     from anemoi_transform_amd import interp, native
@@ -101,6 +102,79 @@ def main():
                            4 * n_src * n_lev * B + n_src * F * B, "rotate_winds / unrotate_winds: per-point frame, every level")
                 del x, y, xo, yo
                 torch.cuda.empty_cache()
+
+    def pandas_route_ms(date, cell, values, targets, n_cells, freq_ns):
+        """The reference's method for one table on this host, one process: a loop over targets with a groupby().idxmin() in each
+        (R: filters/tabular/irregular_to_grid.py:139-159), window (-time_freq, 0], weight 0."""
+        try:
+            import pandas as pd
+        except ImportError:
+            return None
+        names = [f"v{j}" for j in range(len(values))]
+        df = pd.DataFrame({"date": pd.to_datetime(date), "spatial_index": cell, **{n: v for n, v in zip(names, values)}})
+        freq = pd.Timedelta(freq_ns, "ns")
+        t0 = time.perf_counter()
+        grids = {n: np.full((len(targets), n_cells), np.nan) for n in names}
+        for t, target in enumerate(pd.to_datetime(targets)):
+            part = df[df["date"].gt(target - freq) & df["date"].le(target)]
+            part = part[~part[names].isna().all(axis=1)].copy()
+            if len(part) == 0:
+                continue
+            part["_score"] = (part["date"] - target).abs() / freq
+            best = part.loc[part.groupby("spatial_index")["_score"].idxmin()]
+            index = best["spatial_index"].values.astype(np.intp)
+            ok = (index >= 0) & (index < n_cells)
+            for n in names:
+                grids[n][t, index[ok]] = best[n].values[ok]
+        return (time.perf_counter() - t0) * 1e3
+
+    def obs_rows():
+        """irregular_to_grid: the keyed arg-min (memsets + score pass + row pass, one entry point) and the fill pass, for rows spread
+        uniformly over the cells and for a swath (half the rows in 1 % of the cells: contended atomics).  The fill pass is rated on
+        n_time·n_cols·N·8 + n_time·N·4 bytes; the arg-min on what it must read, n_obs·(16 + 8·n_cols) bytes, for orientation only:
+        it is bound by scattered atomics, not by bandwidth."""
+        hour = 3600 * 10**9
+        for gname, n_time, n_cols, n_obs, host_too in (("o96", 4, 4, 1_000_000, True), ("o1280", 8, 8, 20_000_000, False)):
+            n_cells = len(lookup(gname)["latitudes"])
+            gen = torch.Generator(device=dev).manual_seed(n_obs)
+            base = 1_700_000_000 * 10**9
+            targets = base + torch.arange(1, n_time + 1, dtype=torch.int64, device=dev) * 6 * hour
+            date = base + torch.randint(0, (n_time + 1) * 360, (n_obs,), generator=gen, device=dev) * 60 * 10**9
+            values = torch.rand((n_cols, n_obs), dtype=torch.float64, generator=gen, device=dev)
+            values[torch.rand((n_cols, n_obs), generator=gen, device=dev) < 0.1] = float("nan")
+            uniform = torch.randint(0, n_cells, (n_obs,), generator=gen, device=dev)
+            swath = uniform.clone()
+            swath[: n_obs // 2] = torch.randint(0, max(1, n_cells // 100), (n_obs // 2,), generator=gen, device=dev)
+            swath = swath[torch.randperm(n_obs, generator=gen, device=dev)]
+            best = torch.empty((n_time, n_cells), dtype=torch.int64, device=dev)
+            winner = torch.empty((n_time, n_cells), dtype=torch.int32, device=dev)
+            for cname, cell in (("uniform", uniform), ("swath", swath)):
+                shape = f"{gname} T{n_time} C{n_cols} {n_obs:.0e} rows {cname}"
+                record(f"obs_best_per_cell {shape}", timeit(lambda: native.obs_best_per_cell(
+                       date, cell, values, targets, best, winner, n_cells=n_cells, before_ns=-6 * hour, after_ns=0, closed_before=False,
+                       closed_after=True, freq_ns=6 * hour, weight=0.3)), n_obs * (16 + 8 * n_cols),
+                       f"two memsets + score pass + row pass; {float((winner >= 0).float().mean()):.3f} of the slots filled")
+                for layout, lname in ((COLUMNS, "columns"), (FIELDS, "fields")):
+                    out = Stack.empty(n_cells, n_time * n_cols, torch.float64, dev, layout)
+                    record(f"obs_fill_stack {shape} {lname}", timeit(lambda: native.obs_fill_stack(
+                           winner, values, out.data, n_time=n_time, n_cells=n_cells, pitch=out.pitch, layout=layout)),
+                           n_time * n_cols * n_cells * 8 + n_time * n_cells * 4, "gather of 8-byte words by winner, 16-byte non-temporal stores")
+                    del out
+                if host_too:
+                    ms = pandas_route_ms(date.cpu().numpy().view("datetime64[ns]"), cell.cpu().numpy(), values.cpu().numpy(),
+                                         targets.cpu().numpy().view("datetime64[ns]"), n_cells, 6 * hour)
+                    if ms is not None:
+                        res[f"pandas route {shape}"] = {"ms": ms, "note": "the reference's method on this host, one process: per target a "
+                                                        "window selection and groupby().idxmin(); the NaN grids it fills stay on the host"}
+                        print(f"{'pandas route ' + shape:42s} {ms:9.1f} ms  (host)", flush=True)
+            del date, values, uniform, swath, best, winner
+            torch.cuda.empty_cache()
+
+    if args.only_obs:
+        obs_rows()
+        if args.out:
+            json.dump(res, open(args.out, "w"), indent=1)
+        return
 
     if args.only_rotate:
         for tdt, B, tag in ((torch.float32, 4, "f32"), (torch.float64, 8, "f64")):
