@@ -440,8 +440,9 @@ combine_kernel(CombArgs a, int flags, int n_in, int n_out, int64_t n_rows, int64
     constexpr bool kShared1 = OP == ATX_COMB_ORAS6;  // operand 1 is ONE field [n_pts] shared by every level, not a stack
     const bool small_rows = vec_per_row < (1 << 20);  // columns layout: (row, col) from 32-bit arithmetic
     const float inv_vec_per_row = __builtin_amdgcn_rcpf((float)vec_per_row);
-    // a workgroup takes a contiguous run of chunks, not every gridDim.x-th one: under the 65536-workgroup cap the grid stride is a
-    // power of two (1 GiB for f64) and drifting workgroups alias onto the same HBM channels (atx_pointwise.hip, ATX_PW_ASSIGN)
+    // ATX_COMB_ASSIGN 1: a workgroup takes a contiguous run of chunks, not every gridDim.x-th one — under the 65536-workgroup cap the grid
+    // stride is a power of two (1 GiB for f64) and drifting workgroups were suspected of aliasing onto the same HBM channels.  The same
+    // experiment on the per-point chunked kernel measured contiguous runs 10 % slower (profiles/r03_pointwise_ab_README.md), so 0 stays.
 #ifndef ATX_COMB_ASSIGN
 #define ATX_COMB_ASSIGN 0
 #endif

@@ -70,6 +70,28 @@ struct alignas(sizeof(T) * N) Pack {
     T v[N];
 };
 
+// Non-temporal load / store of a Pack, for data a kernel touches once (the per-point kernels pick them per launch, the vector
+// reduction always loads this way).
+template <typename T, int N>
+struct PwNative {
+    typedef T type __attribute__((ext_vector_type(N)));
+};
+template <typename T>
+struct PwNative<T, 1> {
+    typedef T type;
+};
+template <typename T, int N>
+__device__ __forceinline__ Pack<T, N> pw_load_nt(const T* p) {
+    using NV = typename PwNative<T, N>::type;
+    NV v = __builtin_nontemporal_load(reinterpret_cast<const NV*>(p));
+    return *reinterpret_cast<Pack<T, N>*>(&v);
+}
+template <typename T, int N>
+__device__ __forceinline__ void pw_store_nt(T* p, const Pack<T, N>& v) {
+    using NV = typename PwNative<T, N>::type;
+    __builtin_nontemporal_store(*reinterpret_cast<const NV*>(&v), reinterpret_cast<NV*>(p));
+}
+
 // Workgroups are dealt round-robin to the 8 XCDs (blocks b and b+8 share an L2).
 // Give every XCD one contiguous range of tiles so that neighbouring targets —
 // which read the same or adjacent source columns — meet in the same L2.
@@ -612,6 +634,29 @@ __device__ __forceinline__ void apply_program_vec(const LevelOp<T>* __restrict__
             for (int e = 0; e < VEC; ++e) {
                 const int l = c * VEC + e;
                 if (l < n_lev) v.v[e] = apply_level_op<T, TRANS>(load_level_op<T>(prog, (int64_t)s * n_lev + l), v.v[e], masked);
+            }
+        }
+    }
+}
+
+// The same with column c's entries of the HOST-BUILT table (atx_vector_program) already in registers: the loop over the kMaxStages
+// possible stages is fully unrolled, so `ops` is never indexed at run time (that would put it in scratch memory).  (Written out
+// rather than shared with apply_program_vec stage by stage: through a common per-stage helper the table and sparse kernels of
+// atx_pointwise.hip came out with other register counts.)
+constexpr int kMaxStages = 8;
+template <typename T, int VEC>
+__device__ __forceinline__ void apply_vector_ops(const LevelOp<T> (&ops)[kMaxStages], const atx_level_op* prog, int n_stage, int n_lev,
+                                                 int c, Pack<T, VEC>& v, bool masked) {
+#pragma unroll
+    for (int s = 0; s < kMaxStages; ++s) {
+        if (s >= n_stage) break;
+        if (ops[s].op != kOpMixed) {
+            apply_level_op_vec<T, VEC>(ops[s], v, masked);
+        } else {
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) {
+                const int l = c * VEC + e;
+                if (l < n_lev) v.v[e] = apply_level_op(load_level_op<T>(prog, (int64_t)s * n_lev + l), v.v[e], masked);
             }
         }
     }

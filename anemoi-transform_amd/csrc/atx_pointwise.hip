@@ -8,14 +8,38 @@
 //   R: filters/fields/apply_mask.py:183-185, glacier_mask.py:33  values[mask] = nan
 // by ONE streaming pass over the stack: level l gets prog[s][l] for each stage s.
 // HBM-bound: 16-byte loads/stores, grid-strided over up to kStreamGrid short workgroups; levels whose program is all-COPY are not touched when the
-// operation is in place.
+// operation is in place.  Nine kernels, each the fastest on some program shape; pointwise_columns lists them in the order they are tried.
 #include "atx_common.hpp"
 #include <algorithm>
+#include <optional>
 #include <type_traits>
 
 namespace atx {
 
-constexpr int64_t kMaxGrid = kStreamGrid;
+// Independent 16-byte loads a lane of the chunked kernels has in flight.  2: -13 %, 8: +-1 % (f32, 137 levels).
+constexpr int kPwUnroll = 4;
+
+template <typename T, int N>
+__device__ __forceinline__ Pack<T, N> pw_load(const T* p) {
+    return *reinterpret_cast<const Pack<T, N>*>(p);
+}
+template <typename T, int N>
+__device__ __forceinline__ void pw_store(T* p, const Pack<T, N>& v) {
+    *reinterpret_cast<Pack<T, N>*>(p) = v;
+}
+
+// (row, vector column) of vector slot vi in rows of `cols` slots.  The branch is uniform over the launch: a 32-bit division when
+// every slot index fits.
+__device__ __forceinline__ void split_row_col(int64_t vi, int64_t n_vec, int cols, int64_t& row, int& c) {
+    if (n_vec <= 0xffffffffll) {
+        const unsigned r = (unsigned)vi / (unsigned)cols;
+        row = r;
+        c = (int)((unsigned)vi - r * (unsigned)cols);
+    } else {
+        row = vi / cols;
+        c = (int)(vi - row * cols);
+    }
+}
 
 // ATX_COLUMNS.  A workgroup sweeps CONTIGUOUS chunks of rows (points).  Its lanes are laid over
 // (row-in-pass, vector column): lane = r*Cg + c with Cg = min(C, 256) columns per pass and
@@ -24,54 +48,6 @@ constexpr int64_t kMaxGrid = kStreamGrid;
 // the same chunk (NOT megabytes apart: a fixed large power-of-two distance between a lane's
 // concurrent streams aliases onto the same HBM channels and cost 25 % here).  HBM-bound; what the
 // kernel needs is memory-level parallelism: 4 independent 16-byte loads per lane.
-#ifndef ATX_PW_UNROLL
-#define ATX_PW_UNROLL 4  // 2: -13 %, 8: +-1 % (f32 137 levels); non-temporal stores (ATX_PW_NT): -15 %
-#endif
-constexpr int kPwUnroll = ATX_PW_UNROLL;
-#ifndef ATX_PW_NT
-#define ATX_PW_NT 0  // 0: plain, 1: nt stores, 2: nt loads + nt stores
-#endif
-template <typename T, int N>
-struct PwNative {
-    typedef T type __attribute__((ext_vector_type(N)));
-};
-template <typename T>
-struct PwNative<T, 1> {
-    typedef T type;
-};
-template <typename T, int N>
-__device__ __forceinline__ Pack<T, N> pw_load(const T* p) {
-#if ATX_PW_NT >= 2
-    using NV = typename PwNative<T, N>::type;
-    NV v = __builtin_nontemporal_load(reinterpret_cast<const NV*>(p));
-    return *reinterpret_cast<Pack<T, N>*>(&v);
-#else
-    return *reinterpret_cast<const Pack<T, N>*>(p);
-#endif
-}
-template <typename T, int N>
-__device__ __forceinline__ void pw_store(T* p, const Pack<T, N>& v) {
-#if ATX_PW_NT >= 1
-    using NV = typename PwNative<T, N>::type;
-    __builtin_nontemporal_store(*reinterpret_cast<const NV*>(&v), reinterpret_cast<NV*>(p));
-#else
-    *reinterpret_cast<Pack<T, N>*>(p) = v;
-#endif
-}
-
-// explicit non-temporal forms (whatever ATX_PW_NT says) for kernels that pick per launch
-template <typename T, int N>
-__device__ __forceinline__ Pack<T, N> pw_load_nt(const T* p) {
-    using NV = typename PwNative<T, N>::type;
-    NV v = __builtin_nontemporal_load(reinterpret_cast<const NV*>(p));
-    return *reinterpret_cast<Pack<T, N>*>(&v);
-}
-template <typename T, int N>
-__device__ __forceinline__ void pw_store_nt(T* p, const Pack<T, N>& v) {
-    using NV = typename PwNative<T, N>::type;
-    __builtin_nontemporal_store(*reinterpret_cast<const NV*>(&v), reinterpret_cast<NV*>(p));
-}
-
 template <typename T, int VEC>
 __global__ void __launch_bounds__(kBlock)
 pointwise_cols_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t n_pts, int n_lev, int C,
@@ -146,23 +122,9 @@ pointwise_cols_flat_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t n
 
     const int64_t n_vec = n_pts * C;
     constexpr int64_t kChunk = (int64_t)kBlock * kPwUnroll;
-    // A workgroup takes a CONTIGUOUS run of chunks (ATX_PW_ASSIGN 1), not every gridDim.x-th one: under the 65536-workgroup cap the
-    // grid stride is 65536 * 16 KB = exactly 1 GiB, and workgroups that drift apart then stream from addresses a power of two
-    // apart — on boxes whose allocations are physically contiguous these alias onto the same HBM channels / banks (the same kernel
-    // binary measured 2.37 ms on one box and 2.63 ms on another for 137 float64 levels of O1280 while atx_stream_copy stayed at
-    // 2.33 ms on both; profiles/r03_pointwise_ab.log, r03_pointwise_placement.log).
-#ifndef ATX_PW_ASSIGN
-#define ATX_PW_ASSIGN 0
-#endif
-#if ATX_PW_ASSIGN == 1
-    const int64_t n_chunks = (n_vec + kChunk - 1) / kChunk;
-    const int64_t per = (n_chunks + gridDim.x - 1) / gridDim.x;
-    const int64_t first = (int64_t)blockIdx.x * per * kChunk;
-    const int64_t last = first + per * kChunk < n_vec ? first + per * kChunk : n_vec;
-    for (int64_t base = first; base < last; base += kChunk) {
-#else
+    // A workgroup takes every gridDim.x-th chunk: under the 65536-workgroup cap the stride is exactly 1 GiB, but a contiguous run of
+    // chunks per workgroup measured 10 % SLOWER (2.68 against 2.43 ms, 137 float64 levels of O1280; profiles/r03_pointwise_ab_README.md).
     for (int64_t base = (int64_t)blockIdx.x * kChunk; base < n_vec; base += (int64_t)gridDim.x * kChunk) {
-#endif
         const int64_t row_b = base / C;  // uniform: scalar unit
         const int col_b = (int)(base - row_b * C);
         V v[kPwUnroll];
@@ -267,18 +229,11 @@ pointwise_cols_table_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t 
     if (vi >= n_vec) return;
     int64_t row;
     int c;
-    if (n_vec <= 0xffffffffll) {  // uniform: 32-bit division
-        const unsigned r = (unsigned)vi / (unsigned)C;
-        row = r;
-        c = (int)((unsigned)vi - r * (unsigned)C);
-    } else {
-        row = vi / C;
-        c = (int)(vi - row * C);
-    }
-    LevelOp<T> ops[8];
+    split_row_col(vi, n_vec, C, row, c);
+    LevelOp<T> ops[kMaxStages];
     bool act = false, need_mask = false;
 #pragma unroll
-    for (int s = 0; s < 8; ++s) {
+    for (int s = 0; s < kMaxStages; ++s) {
         if (s < n_stage) {
             ops[s] = load_level_op<T>(vec_prog, (int64_t)s * C + c);
             act = act || ops[s].op != ATX_OP_COPY || ops[s].use_mask != 0;
@@ -289,19 +244,7 @@ pointwise_cols_table_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t 
     V v = pw_load<T, VEC>(x + vi * VEC);
     if (act) {
         const bool masked = (need_mask && point_mask) ? (point_mask[row] != 0) : false;
-#pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            if (s >= n_stage) break;
-            if (ops[s].op != kOpMixed) {
-                apply_level_op_vec<T, VEC>(ops[s], v, masked);
-            } else {
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) {
-                    const int l = c * VEC + e;
-                    if (l < n_lev) v.v[e] = apply_level_op(load_level_op<T>(prog, (int64_t)s * n_lev + l), v.v[e], masked);
-                }
-            }
-        }
+        apply_vector_ops<T, VEC>(ops, prog, n_stage, n_lev, c, v, masked);
     }
     pw_store<T, VEC>(y + vi * VEC, v);
 }
@@ -315,13 +258,15 @@ pointwise_cols_table_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t 
 // kernel touches is touched again — measured 2.32 -> 2.22 ms f64 out of place, 2.43 -> 2.23 ms in place, f32 1.19 -> 1.13 and
 // 1.24 -> 1.12 ms (0.80-0.81 of the peak, above the plain copy); with a point mask they cost 2-6 % instead (the mask bytes, shared
 // by the ~35-69 lanes of a point, live in the same caches), so masked programs keep plain accesses; profiles/r03_pointwise_ab.log.
-template <typename T, int VEC, bool TRANS, int U, bool NT>
+template <typename T, int VEC, bool TRANS, bool NT>
 __global__ void __launch_bounds__(kBlock)
 pointwise_cols_uniform_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t n_vec, int C, int Cp, UniformOps<T> u,
                               const uint8_t* __restrict__ point_mask, int need_rc, int in_place, unsigned act_bits) {
     // Cp >= C: vector slots per row (pitch / VEC); n_vec = n_pts * Cp; slots beyond C are padding (need_rc is set when Cp > C)
     using V = Pack<T, VEC>;
-    // U vectors per lane, kBlock apart: a workgroup covers kBlock * U consecutive vectors (no loop)
+    // One vector per lane (2-8 stream slower, tools/experiments/stream_shapes.hip).  The body keeps the shape it had when that
+    // was a parameter: written out for scalars the compiler spends one more scalar register on it.
+    constexpr int U = 1;
     const int64_t base = (int64_t)blockIdx.x * (kBlock * U) + threadIdx.x;
     V v[U];
     int c[U];
@@ -334,14 +279,7 @@ pointwise_cols_uniform_kernel(const T* __restrict__ x, T* __restrict__ y, int64_
         masked[k] = false;
         if (go[k] && need_rc) {  // uniform: a two-piece stage or the point mask — the lane needs its (row, vector column)
             int64_t row;
-            if (n_vec <= 0xffffffffll) {
-                const unsigned r = (unsigned)vi / (unsigned)Cp;
-                row = r;
-                c[k] = (int)((unsigned)vi - r * (unsigned)Cp);
-            } else {
-                row = vi / Cp;
-                c[k] = (int)(vi - row * Cp);
-            }
+            split_row_col(vi, n_vec, Cp, row, c[k]);
             if (c[k] >= C) go[k] = false;  // padding slot of a loose pitch
             if (in_place) {  // untouched columns of an in-place call: nothing to move.  `act_bits` (host-built): bit s = the first
                 // piece of stage s does something, bit 4 + s = its second piece.  (Selecting between u.stage[s].op and u.second[s].op
@@ -352,28 +290,7 @@ pointwise_cols_uniform_kernel(const T* __restrict__ x, T* __restrict__ y, int64_
                 for (int s = 0; s < kMaxUniform; ++s) act |= (c[k] >= u.split[s]) ? (act_bits >> (4 + s)) : (act_bits >> s);
                 go[k] = go[k] && (act & 1u) != 0;
             }
-#ifndef ATX_PW_MASK_WAVE
-#define ATX_PW_MASK_WAVE 0
-#endif
-            if (point_mask) {
-                // The mask byte of a point is shared by the Cp lanes of its row: a per-lane byte load is one more vector-memory instruction
-                // per wave on a kernel that has two (ATX_PW_MASK_WAVE=1: the wave fetches the 8 bytes from its first row on with ONE scalar
-                // load and every lane picks its own — possible when a wave spans at most 8 rows and the 8 bytes lie inside the mask).
-                bool wave_path = false;
-                if (ATX_PW_MASK_WAVE && Cp >= 10 && n_vec <= 0xffffffffll) {
-                    const unsigned first_vi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(vi - (threadIdx.x & (kWave - 1))));
-                    const unsigned row0 = (first_vi / (unsigned)Cp) & ~7u;  // 8-byte aligned start
-                    const int64_t n_rows = n_vec / Cp;
-                    if ((int64_t)row0 + 8 <= n_rows && (reinterpret_cast<uintptr_t>(point_mask) & 7u) == 0) {
-                        wave_path = true;
-                        const unsigned long long bits = *reinterpret_cast<const unsigned long long*>(point_mask + row0);
-                        const unsigned off = (unsigned)row - row0;  // < 8 + 64 / Cp
-                        if (off < 8u) masked[k] = go[k] && ((bits >> (8u * off)) & 0xffull) != 0;
-                        else masked[k] = go[k] && point_mask[row] != 0;
-                    }
-                }
-                if (!wave_path && go[k]) masked[k] = point_mask[row] != 0;
-            }
+            if (point_mask && go[k]) masked[k] = point_mask[row] != 0;  // a byte load per lane
         }
         if (go[k]) v[k] = NT ? pw_load_nt<T, VEC>(x + vi * VEC) : pw_load<T, VEC>(x + vi * VEC);
     }
@@ -408,14 +325,7 @@ pointwise_cols_runs_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t n
     if (vi >= n_vec) return;
     int64_t row;
     int c;
-    if (n_vec <= 0xffffffffll) {
-        const unsigned r = (unsigned)vi / (unsigned)Cp;
-        row = r;
-        c = (int)((unsigned)vi - r * (unsigned)Cp);
-    } else {
-        row = vi / Cp;
-        c = (int)(vi - row * Cp);
-    }
+    split_row_col(vi, n_vec, Cp, row, c);
     if (c >= C) return;  // padding slot of a loose pitch
     const bool masked = point_mask ? point_mask[row] != 0 : false;
     V v = NT ? pw_load_nt<T, VEC>(x + vi * VEC) : pw_load<T, VEC>(x + vi * VEC);
@@ -440,14 +350,7 @@ pointwise_cols_typed_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t 
     if (vi >= n_vec) return;
     int64_t row;
     int c;
-    if (n_vec <= 0xffffffffll) {  // uniform: 32-bit division
-        const unsigned r = (unsigned)vi / (unsigned)C;
-        row = r;
-        c = (int)((unsigned)vi - r * (unsigned)C);
-    } else {
-        row = vi / C;
-        c = (int)(vi - row * C);
-    }
+    split_row_col(vi, n_vec, C, row, c);
     const int Lp = C * VEC;
     const T* tp0 = reinterpret_cast<const T*>(level_tables);
     const T* tp1 = tp0 + Lp;
@@ -489,10 +392,10 @@ pointwise_cols_sparse_kernel(T* __restrict__ y, int64_t n_items, int n_lev, int 
     int c = active.col[0];
 #pragma unroll
     for (int i = 1; i < kMaxActive; ++i) c = (a == i) ? active.col[i] : c;  // the list lives in scalar registers: select, do not index
-    LevelOp<T> ops[8];
+    LevelOp<T> ops[kMaxStages];
     bool need_mask = false;
 #pragma unroll
-    for (int s = 0; s < 8; ++s) {
+    for (int s = 0; s < kMaxStages; ++s) {
         if (s < n_stage) {
             ops[s] = load_level_op<T>(vec_prog, (int64_t)s * C + c);
             need_mask = need_mask || ops[s].use_mask != 0;
@@ -501,19 +404,7 @@ pointwise_cols_sparse_kernel(T* __restrict__ y, int64_t n_items, int n_lev, int 
     T* at = y + p * pitch + (int64_t)c * VEC;
     V v = pw_load<T, VEC>(at);
     const bool masked = (need_mask && point_mask) ? (point_mask[p] != 0) : false;
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-        if (s >= n_stage) break;
-        if (ops[s].op != kOpMixed) {
-            apply_level_op_vec<T, VEC>(ops[s], v, masked);
-        } else {
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) {
-                const int l = c * VEC + e;
-                if (l < n_lev) v.v[e] = apply_level_op(load_level_op<T>(prog, (int64_t)s * n_lev + l), v.v[e], masked);
-            }
-        }
-    }
+    apply_vector_ops<T, VEC>(ops, prog, n_stage, n_lev, c, v, masked);
     pw_store<T, VEC>(at, v);
 }
 
@@ -525,18 +416,9 @@ pointwise_cols_sparse_kernel(T* __restrict__ y, int64_t n_items, int n_lev, int 
 // Measured on 137 fields of O1280 (profiles/r03_fields_pointwise.log; run-to-run noise ~3 %): requesting the data before the field's
 // operators are known (out of place only — in place an untouched field must not be read) f32 0.78 -> 0.83, f64 neutral; two vectors
 // per lane f64 0.75-0.77 -> 0.78-0.80 (and an in-place call that skips two fields in three 1.25 -> 0.95 ms), f32 in place 0.78 -> 0.75.
-#ifndef ATX_PW_FIELDS_U32
-#define ATX_PW_FIELDS_U32 1  // vectors per lane (kBlock apart), float32
-#endif
-#ifndef ATX_PW_FIELDS_U64
-#define ATX_PW_FIELDS_U64 2  // float64
-#endif
-#ifndef ATX_PW_FIELDS_EARLY
-#define ATX_PW_FIELDS_EARLY 1
-#endif
 template <typename T>
-constexpr int fields_vectors_per_lane() {
-    return sizeof(T) == 4 ? ATX_PW_FIELDS_U32 : ATX_PW_FIELDS_U64;
+constexpr int fields_vectors_per_lane() {  // kBlock apart
+    return sizeof(T) == 4 ? 1 : 2;
 }
 template <typename T, int VEC, bool TRANS, bool NT>
 __global__ void __launch_bounds__(kBlock)
@@ -552,7 +434,7 @@ pointwise_fields_rows_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t
     const int64_t n_vec = n_pts / VEC;
     const int64_t base = (int64_t)blockIdx.x * (kBlock * U) + threadIdx.x;
     V v[U];
-    const bool early = ATX_PW_FIELDS_EARLY && !in_place;
+    const bool early = !in_place;
     if (early) {
 #pragma unroll
         for (int k = 0; k < U; ++k)
@@ -625,683 +507,292 @@ pointwise_fields_rows_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t
     }
 }
 
-// ---- masks -----------------------------------------------------------------------
-template <typename T>
-__device__ __forceinline__ bool compare(T m, T thr, int cmp) {
-    switch (cmp) {
-        case ATX_CMP_GT: return m > thr;
-        case ATX_CMP_LT: return m < thr;
-        case ATX_CMP_EQ: return m == thr;
-        case ATX_CMP_NE: return m != thr;  // true for NaN, like np.not_equal
-        case ATX_CMP_GE: return m >= thr;
-        case ATX_CMP_LE: return m <= thr;
-        case ATX_CMP_NOTNAN: return m == m;
-        case ATX_CMP_ISNAN: return m != m;
-        default: return false;
-    }
+// ---- dispatch -----------------------------------------------------------------------------------------------------------------
+
+// f(std::true_type{}) or f(std::false_type{}): a run-time flag becomes a template argument of the launch inside f, and only the
+// combinations a caller spells out are instantiated.
+template <typename F>
+static void with_flag(bool flag, F&& f) {
+    if (flag) f(std::true_type{});
+    else f(std::false_type{});
+}
+template <typename F>
+static void with_trans_nt(bool trans, bool nt, F&& f) {
+    with_flag(trans, [&](auto tr) { with_flag(nt, [&](auto n) { f(tr, n); }); });
 }
 
-template <typename T>
-__global__ void __launch_bounds__(kBlock)
-mask_build_kernel(const T* __restrict__ m, int64_t m_stride, uint8_t* __restrict__ mask, int64_t n, int cmp, T thr) {
-    // 4 points per lane -> one 32-bit store of 4 mask bytes
-    const int64_t n4 = n / 4;
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n4; i += (int64_t)gridDim.x * kBlock) {
-        uint32_t packed = 0;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) packed |= (compare<T>(m[(i * 4 + e) * m_stride], thr, cmp) ? 1u : 0u) << (8 * e);
-        *reinterpret_cast<uint32_t*>(mask + i * 4) = packed;
-    }
-    if (blockIdx.x == 0 && threadIdx.x < 4) {
-        const int64_t i = n4 * 4 + threadIdx.x;
-        if (i < n) mask[i] = compare<T>(m[i * m_stride], thr, cmp) ? 1 : 0;
-    }
-}
-
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
-    return v;
-}
-
-__global__ void __launch_bounds__(kBlock)
-mask_count_kernel(const uint8_t* __restrict__ mask, int64_t n, unsigned long long* count) {
-    unsigned long long c = 0;
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
-        c += mask[i] != 0;
-    c = wave_sum(c);
-    if ((threadIdx.x & (kWave - 1)) == 0 && c) atomicAdd(count, c);
-}
-
-// ---- stable compaction: mask -> ascending index list ------------------------------
-constexpr int kPerLane = 16;                     // mask bytes per lane
-constexpr int kChunk = kBlock * kPerLane;        // mask bytes per workgroup
-
-__device__ __forceinline__ int lane_count(const uint8_t* __restrict__ mask, int64_t base, int64_t n, uint32_t& bits) {
-    bits = 0;
-#pragma unroll
-    for (int e = 0; e < kPerLane; ++e) {
-        const int64_t i = base + e;
-        if (i < n && mask[i] != 0) bits |= 1u << e;
-    }
-    return __popc(bits);
-}
-
-__global__ void __launch_bounds__(kBlock)
-compact_count_kernel(const uint8_t* __restrict__ mask, int64_t n, int32_t* __restrict__ block_counts) {
-    __shared__ unsigned long long wsum[kBlock / kWave];
-    uint32_t bits;
-    const int64_t base = (int64_t)blockIdx.x * kChunk + (int64_t)threadIdx.x * kPerLane;
-    unsigned long long c = wave_sum((unsigned long long)lane_count(mask, base, n, bits));
-    if ((threadIdx.x & (kWave - 1)) == 0) wsum[threadIdx.x / kWave] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long t = 0;
-        for (int i = 0; i < kBlock / kWave; ++i) t += wsum[i];
-        block_counts[blockIdx.x] = (int32_t)t;
-    }
-}
-
-// single workgroup: exclusive scan of the per-block counts, in place
-__global__ void __launch_bounds__(1024)
-compact_scan_kernel(int32_t* __restrict__ block_counts, int n_blocks, long long* __restrict__ total) {
-    __shared__ long long part[1024];
-    const int tid = threadIdx.x;
-    const int per = (n_blocks + 1023) / 1024;
-    const int b0 = tid * per, b1 = min(n_blocks, b0 + per);
-    long long s = 0;
-    for (int b = b0; b < b1; ++b) s += block_counts[b];
-    part[tid] = s;
-    __syncthreads();
-    // Hillis-Steele inclusive scan over 1024 partials
-    for (int off = 1; off < 1024; off <<= 1) {
-        long long v = (tid >= off) ? part[tid - off] : 0;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    long long run = part[tid] - s;  // exclusive prefix of this lane's range
-    for (int b = b0; b < b1; ++b) {
-        const int32_t cnt = block_counts[b];
-        block_counts[b] = (int32_t)run;
-        run += cnt;
-    }
-    if (tid == 1023) *total = part[1023];
-}
-
-// SELF_SCAN (few thousand workgroups at most): `block_offsets` holds the raw per-workgroup COUNTS and every workgroup sums the counts before
-// its own by itself (a few KB out of L2) — the single-workgroup scan launch between count and scatter goes away (three launches -> two);
-// the last workgroup writes the total.
-template <bool SELF_SCAN>
-__global__ void __launch_bounds__(kBlock)
-compact_scatter_kernel(const uint8_t* __restrict__ mask, int64_t n, const int32_t* __restrict__ block_offsets,
-                       int32_t* __restrict__ index, long long* __restrict__ total) {
-    __shared__ int wsum[kBlock / kWave];
-    __shared__ long long before_s;
-    long long before = 0;
-    if (SELF_SCAN) {
-        __shared__ unsigned long long psum[kBlock / kWave];
-        unsigned long long mine = 0;
-        for (int b = threadIdx.x; b < (int)blockIdx.x; b += kBlock) mine += (unsigned long long)block_offsets[b];
-        mine = wave_sum(mine);
-        if ((threadIdx.x & (kWave - 1)) == 0) psum[threadIdx.x / kWave] = mine;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            unsigned long long t = 0;
-            for (int i = 0; i < kBlock / kWave; ++i) t += psum[i];
-            before_s = (long long)t;
-            if (blockIdx.x == gridDim.x - 1) *total = (long long)t + block_offsets[blockIdx.x];
+// Does vector column c (levels c*vec .. c*vec+vec-1) hold a level that some stage does not plainly COPY?
+static bool vector_column_active(const atx_level_op* host_prog, int n_stage, int n_lev, int c, int vec) {
+    for (int s = 0; s < n_stage; ++s)
+        for (int l = c * vec; l < n_lev && l < (c + 1) * vec; ++l) {
+            const atx_level_op& o = host_prog[(int64_t)s * n_lev + l];
+            if (o.op != ATX_OP_COPY || o.use_mask != 0) return true;
         }
-        __syncthreads();
-        before = before_s;
-    } else {
-        before = block_offsets[blockIdx.x];
-    }
-    uint32_t bits;
-    const int64_t base = (int64_t)blockIdx.x * kChunk + (int64_t)threadIdx.x * kPerLane;
-    const int cnt = lane_count(mask, base, n, bits);
-    // inclusive wave scan by shuffles
-    const int lane = threadIdx.x & (kWave - 1);
-    int incl = cnt;
-#pragma unroll
-    for (int off = 1; off < kWave; off <<= 1) {
-        const int v = __shfl_up(incl, off, kWave);
-        if (lane >= off) incl += v;
-    }
-    if (lane == kWave - 1) wsum[threadIdx.x / kWave] = incl;
-    __syncthreads();
-    int wave_base = 0;
-    for (int i = 0; i < (int)(threadIdx.x / kWave); ++i) wave_base += wsum[i];
-    int64_t o = (int64_t)before + wave_base + (incl - cnt);
-    while (bits) {
-        const int e = __ffs(bits) - 1;
-        bits &= bits - 1;
-        index[o++] = (int32_t)(base + e);
-    }
+    return false;
 }
 
-// ---- reductions -------------------------------------------------------------------
-__device__ __forceinline__ void atomic_minmax(double* addr, double v, bool is_max) {
-    unsigned long long* a = reinterpret_cast<unsigned long long*>(addr);
-    unsigned long long old = *a;
-    while (true) {
-        const double cur = __longlong_as_double((long long)old);
-        if (cur != cur) return;  // already NaN: np.min/np.max propagate it
-        double nv;
-        if (v != v) nv = v;
-        else nv = is_max ? (v > cur ? v : cur) : (v < cur ? v : cur);
-        const unsigned long long nb = (unsigned long long)__double_as_longlong(nv);
-        if (nb == old) return;
-        const unsigned long long prev = atomicCAS(a, old, nb);
-        if (prev == old) return;
-        old = prev;
+// One ATX_COLUMNS call and what every route wants to know about it.
+template <typename T>
+struct ColumnsCall {
+    static constexpr int VEC = Vec16<T>::N;
+    const T* x;
+    T* y;
+    int64_t n_pts;
+    int n_lev;
+    int64_t xp, yp;
+    const atx_level_op *prog, *vec_prog, *host_prog;
+    int n_stage;
+    const uint8_t* mask;
+    hipStream_t st;
+    int in_place;
+    bool wide;  // 16-byte vectors: bases and pitches aligned, the last (partial) vector of a row inside both pitches
+    int C;      // columns of a row: vectors when wide, levels otherwise
+    // One run of vector slots — a tight pitch, or (round 3) equal loose pitches (columns aligned to 128 bytes, a spare vector): the
+    // no-loop and chunked kernels walk the Cp = pitch / VEC slots of a row and leave the padding slots alone (the row-chunk kernel:
+    // 0.51-0.57 f32, 0.69 f64 on such stacks).  Cp, n_vec and one_launch mean something only when `slots` is set.
+    bool slots, tight;
+    int Cp;
+    int64_t n_vec;    // n_pts * Cp
+    bool one_launch;  // one vector per lane fits the grid
+
+    bool transcendental() const { return program_has_transcendental(host_prog, n_stage, n_lev); }
+    dim3 vector_grid() const { return dim3((unsigned)((n_vec + kBlock - 1) / kBlock)); }
+    dim3 chunk_grid() const {  // contiguous runs of `per` chunks of kBlock * kPwUnroll vectors: no workgroup without work
+        const int64_t n_chunks = (n_vec + (int64_t)kBlock * kPwUnroll - 1) / ((int64_t)kBlock * kPwUnroll);
+        const int64_t blocks = n_chunks > kStreamGrid ? kStreamGrid : n_chunks;
+        const int64_t per = (n_chunks + blocks - 1) / blocks;
+        return dim3((unsigned)((n_chunks + per - 1) / per));
     }
-}
-
-__global__ void reduce_init_kernel(double* result, int red) {
-    if (red == ATX_RED_MINMAX) {
-        result[0] = INFINITY;
-        result[1] = -INFINITY;
-        return;
-    }
-    *result = red == ATX_RED_MIN ? INFINITY : (red == ATX_RED_MAX ? -INFINITY : 0.0);
-}
-
-// One partial per lane over a grid-stride sweep (4 independent loads in flight), 64-lane shuffle, one LDS combine per
-// workgroup, ONE atomic per workgroup (a per-wave atomic on a single address serialised 100 k of them on large inputs).
-constexpr int kRedUnroll = 4;
-#ifndef ATX_RED_GRID
-#define ATX_RED_GRID 32768  // workgroup cap = partial slots of the two-level finish.  Round 3 compared 8192 with SMALLER caps only; round 4, 137 levels of O1280, two
-#endif                      // interleaved rounds: 32768 f64 min+max 0.707 -> 0.74, NaN count f32 0.70 -> 0.74, f64 0.715 -> 0.76; f32 min+max unchanged (0.68);
-                            // 65536 loses (f32 min+max 0.60).  One field: unchanged (its grid is far below either cap).  profiles/r04_reduce_grid.log
-constexpr int64_t kRedGrid = ATX_RED_GRID;
-
-__device__ __forceinline__ double red_combine(double a, double b, int red) {
-    if (red == ATX_RED_NANCOUNT) return a + b;
-    if (a != a || b != b) return NAN;  // np.min / np.max propagate NaN
-    if (red == ATX_RED_MIN) return b < a ? b : a;
-    return b > a ? b : a;
-}
-
-// Two-level finish WITHOUT one atomic per workgroup on the result (a CAS loop on one address: 1 600 workgroups over one 26 MB
-// field spent 10 us of a 43 us call in it, min AND max 30 us) and without an initialisation launch: with a caller-provided workspace
-// every workgroup stores its partial(s) with plain stores, and a second, one-workgroup launch (reduce_final_kernel) combines them and
-// writes `result` — which may then be a pinned HOST cell: no copy back either.  The kernel boundary is the only synchronisation.
-// (Round 3 first tried a single launch with a ticket — the last workgroup to arrive combines — and measured it SLOWER than the
-// atomics: the device-scope release every workgroup needs before taking its ticket writes the XCD's L2 back; 43 -> 60 us for one
-// field, 0.66 -> 1.0 ms for a 137-level stack.  profiles/r03_small_calls.log.)
-struct RedWorkspace {
-    double a[kRedGrid];
-    double b[kRedGrid];
 };
 
-__global__ void __launch_bounds__(kBlock)
-reduce_final_kernel(const RedWorkspace* __restrict__ ws, int n, int ra, int red, double* result) {
-    __shared__ double fa[kBlock / kWave], fb[kBlock / kWave];
-    const double id_a = ra == ATX_RED_MIN ? INFINITY : (ra == ATX_RED_MAX ? -INFINITY : 0.0);
-    double a = id_a, b = -INFINITY;
-    for (int i = threadIdx.x; i < n; i += kBlock) {
-        a = red_combine(a, ws->a[i], ra);
-        if (red == ATX_RED_MINMAX) b = red_combine(b, ws->b[i], ATX_RED_MAX);
+// A route launches and returns a status (ATX_OK, an error, ATX_SPLIT_PROGRAM), or declines with no value.
+using Routed = std::optional<int>;
+
+// In place with few active levels: visit their columns only.
+template <typename T>
+static Routed route_sparse(const ColumnsCall<T>& k) {
+    constexpr int VEC = ColumnsCall<T>::VEC;
+    if (!(k.in_place && k.wide && k.host_prog && k.vec_prog)) return std::nullopt;
+    ActiveCols active{};
+    for (int c = 0; c < k.C; ++c) {
+        if (!vector_column_active(k.host_prog, k.n_stage, k.n_lev, c, VEC)) continue;
+        if (active.n == kMaxActive) return std::nullopt;
+        active.col[active.n++] = c;
     }
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) {
-        a = red_combine(a, __shfl_down(a, off, kWave), ra);
-        if (red == ATX_RED_MINMAX) b = red_combine(b, __shfl_down(b, off, kWave), ATX_RED_MAX);
+    if (active.n == 0) return ATX_OK;  // nothing to do at all
+    if (3 * active.n > k.C) return std::nullopt;
+    for (int i = active.n; i < kMaxActive; ++i) active.col[i] = active.col[0];
+    const int64_t n_items = k.n_pts * active.n;
+    const int64_t blocks = (n_items + kBlock - 1) / kBlock;
+    ATX_REQUIRE(blocks <= 0x7fffffffll, ATX_ENOTIMPL, "pointwise: %lld items exceed one launch", (long long)n_items);
+    hipLaunchKernelGGL((pointwise_cols_sparse_kernel<T, VEC>), dim3((unsigned)blocks), dim3(kBlock), 0, k.st, k.y, n_items, k.n_lev, k.C, k.yp,
+                       active, k.prog, k.vec_prog, k.n_stage, k.mask);
+    ATX_LAUNCH_CHECK("pointwise_stack_sparse");
+    return ATX_OK;
+}
+
+// Programs uniform over the levels: operators by value, one vector per lane, no loop.  Non-temporal unless the point mask is read
+// (with it: 2-6 % slower, profiles/r04_apply_mask_experiment.log), programs with exp / log included.
+template <typename T>
+static Routed route_uniform(const ColumnsCall<T>& k) {
+    constexpr int VEC = ColumnsCall<T>::VEC;
+    UniformOps<T> uni{};
+    if (!(k.slots && k.one_launch && uniform_level_program<T>(k.host_prog, k.n_stage, k.mask != nullptr, k.n_lev, VEC, uni))) return std::nullopt;
+    bool two_pieces = false, uses_mask = false;
+    unsigned act_bits = 0;
+    for (int s = 0; s < k.n_stage; ++s) {
+        two_pieces = two_pieces || uni.split[s] < k.C;
+        uses_mask = uses_mask || uni.stage[s].use_mask || uni.second[s].use_mask;
+        if (uni.stage[s].op != ATX_OP_COPY || uni.stage[s].use_mask) act_bits |= 1u << s;
+        if (uni.second[s].op != ATX_OP_COPY || uni.second[s].use_mask) act_bits |= 1u << (4 + s);
     }
-    if ((threadIdx.x & (kWave - 1)) == 0) {
-        fa[threadIdx.x / kWave] = a;
-        fb[threadIdx.x / kWave] = b;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double xa = fa[0], xb = fb[0];
-        for (int w = 1; w < kBlock / kWave; ++w) {
-            xa = red_combine(xa, fa[w], ra);
-            xb = red_combine(xb, fb[w], ATX_RED_MAX);
+    const int need_rc = (two_pieces || (uses_mask && k.mask) || !k.tight) ? 1 : 0;
+    const bool nt = !(uses_mask && k.mask);
+    with_trans_nt(k.transcendental(), nt, [&](auto tr, auto n) {
+        hipLaunchKernelGGL((pointwise_cols_uniform_kernel<T, VEC, decltype(tr)::value, decltype(n)::value>), k.vector_grid(), dim3(kBlock), 0, k.st,
+                           k.x, k.y, k.n_vec, k.C, k.Cp, uni, uses_mask ? k.mask : nullptr, need_rc, k.in_place, act_bits);
+    });
+    ATX_LAUNCH_CHECK("pointwise_stack_uniform");
+    return ATX_OK;
+}
+
+// Runs of levels with boundaries anywhere (several variables in one column), out of place or in place: by value as well.
+// Measured against the routes below (tools/experiments/runs_probe.py, profiles/r04_runs_probe.log): evaluating every run's operator and
+// selecting costs a streaming kernel more than it saves — one stage of 3 runs 0.72 / 0.67 (f32 / f64) here against 0.76 / 0.72 on the
+// table and per-level kernels — except for float32 programs of two or more stages, which those kernels run at 0.52-0.58 and this one
+// at 0.65-0.66.  So only they take it.
+template <typename T>
+static Routed route_runs(const ColumnsCall<T>& k) {
+    constexpr int VEC = ColumnsCall<T>::VEC;
+    RunOps<T> runs{};
+    if (!(k.slots && sizeof(T) == 4 && k.n_stage >= 2 && k.one_launch && runs_level_program<T>(k.host_prog, k.n_stage, k.mask != nullptr, k.n_lev, runs)))
+        return std::nullopt;
+    bool uses_mask = false;
+    for (int s = 0; s < k.n_stage; ++s)
+        for (int r = 0; r < runs.n_run[s]; ++r) uses_mask = uses_mask || runs.op[s][r].use_mask != 0;
+    const bool nt = !(uses_mask && k.mask);
+    with_trans_nt(k.transcendental(), nt, [&](auto tr, auto n) {
+        hipLaunchKernelGGL((pointwise_cols_runs_kernel<T, VEC, decltype(tr)::value, decltype(n)::value>), k.vector_grid(), dim3(kBlock), 0, k.st,
+                           k.x, k.y, k.n_vec, k.C, k.Cp, runs, uses_mask ? k.mask : nullptr);
+    });
+    ATX_LAUNCH_CHECK("pointwise_stack_runs");
+    return ATX_OK;
+}
+
+// Operators differing from level to level.  Measured (137 levels of O1280, profiles/r03_pointwise_ab.log): the table kernel (one
+// vector per lane, no loop, operators from the host-built per-vector table) wins for one-stage f32 programs without a mask, out of
+// place (1.21 ms both) AND in place (1.22 vs 1.36 ms chunked); it loses in f64 (2.48 vs 2.37 ms), with two stages (f32 1.56 vs 1.28,
+// f64 3.38 vs 2.58 ms: 24-32 B of operators per stage and vector) and with a point mask in f64 (2.74 vs 2.43 ms).
+template <typename T>
+static Routed route_table(const ColumnsCall<T>& k) {
+    constexpr int VEC = ColumnsCall<T>::VEC;
+    if (!(k.slots && k.tight && k.vec_prog && !k.mask && sizeof(T) == 4 && k.n_stage == 1 && k.one_launch &&
+          !program_has_mixed_vectors<T>(k.host_prog, k.n_stage, k.n_lev, VEC)))  // (mixed vectors: the chunked kernel serves them better)
+        return std::nullopt;
+    hipLaunchKernelGGL((pointwise_cols_table_kernel<T, VEC>), k.vector_grid(), dim3(kBlock), 0, k.st, k.x, k.y, k.n_vec, k.n_lev, k.C, k.prog,
+                       k.vec_prog, k.n_stage, k.mask, k.in_place);
+    ATX_LAUNCH_CHECK("pointwise_stack");
+    return ATX_OK;
+}
+
+// One stage, one operator kind per vector (a scale per level), float64 or in place: the no-loop kernel on the typed per-level part
+// of vec_prog (everything else measured faster on the per-level LDS kernel below, profiles/r03_per_level_programs.log).
+template <typename T>
+static Routed route_typed(const ColumnsCall<T>& k) {
+    constexpr int VEC = ColumnsCall<T>::VEC;
+    if (!(k.slots && k.tight && k.n_stage == 1 && (sizeof(T) == 8 || k.in_place) && k.vec_prog && aligned16(k.vec_prog) && k.host_prog && k.one_launch))
+        return std::nullopt;
+    bool one_kind = true, uses_mask = false;
+    for (int l0 = 0; l0 < k.n_lev && one_kind; l0 += VEC)
+        for (int l = l0; l < k.n_lev && l < l0 + VEC; ++l) {
+            one_kind = one_kind && k.host_prog[l].op == k.host_prog[l0].op && (k.host_prog[l].use_mask != 0) == (k.host_prog[l0].use_mask != 0);
+            uses_mask = uses_mask || k.host_prog[l].use_mask != 0;
         }
-        result[0] = xa;
-        if (red == ATX_RED_MINMAX) result[1] = xb;
-        __threadfence_system();  // `result` may live in pinned host memory
-    }
+    if (!(one_kind && (sizeof(T) == 8 || !(uses_mask && k.mask)))) return std::nullopt;  // (float32 with the point mask: 0.69 here against 0.71-0.75)
+    const unsigned char* level_tables = reinterpret_cast<const unsigned char*>(k.vec_prog) +
+                                        level_tables_layout(1, k.n_lev, sizeof(T) == 4 ? ATX_F32 : ATX_F64).levels_offset;
+    const bool nt = !(uses_mask && k.mask);
+    with_trans_nt(k.transcendental(), nt, [&](auto tr, auto n) {
+        hipLaunchKernelGGL((pointwise_cols_typed_kernel<T, VEC, decltype(tr)::value, decltype(n)::value>), k.vector_grid(), dim3(kBlock), 0, k.st,
+                           k.x, k.y, k.n_vec, k.C, level_tables, uses_mask ? k.mask : nullptr, k.in_place);
+    });
+    ATX_LAUNCH_CHECK("pointwise_stack_typed");
+    return ATX_OK;
+}
+
+// Everything else on tight pitches whose per-level tables fit the LDS: the chunked sweep.  (Loose pitches measured slower here than
+// on the row-chunk kernel — f64 0.57 against 0.69 — so only the by-value kernels take them; tools/experiments/loose_pitch.py.)
+// Non-temporal for float32 programs the host can see, when every vector is touched; never with exp / log.
+template <typename T>
+static Routed route_levels(const ColumnsCall<T>& k) {
+    constexpr int VEC = ColumnsCall<T>::VEC;
+    if (!(k.slots && k.tight)) return std::nullopt;
+    const size_t lds_levels = level_tables_lds_bytes<T>(k.n_stage, k.C, VEC) + (size_t)k.C;
+    if (lds_levels > 64 * 1024) return std::nullopt;
+    bool nt = sizeof(T) == 4 && k.host_prog != nullptr;
+    if (nt && k.in_place)  // every vector must be touched
+        for (int c = 0; c < k.C && nt; ++c) nt = vector_column_active(k.host_prog, k.n_stage, k.n_lev, c, VEC);
+    auto launch = [&](auto tr, auto n) {
+        hipLaunchKernelGGL((pointwise_cols_levels_kernel<T, VEC, decltype(tr)::value, decltype(n)::value>), k.chunk_grid(), dim3(kBlock), lds_levels, k.st,
+                           k.x, k.y, k.n_pts, k.n_lev, k.C, k.Cp, k.prog, k.n_stage, k.mask, k.in_place);
+    };
+    if (k.transcendental()) launch(std::true_type{}, std::false_type{});
+    else with_flag(nt, [&](auto n) { launch(std::false_type{}, n); });
+    ATX_LAUNCH_CHECK("pointwise_stack_levels");
+    return ATX_OK;
+}
+
+// Very tall stacks: round 2's chunked kernel, whose per-VECTOR table is smaller (tight pitches only).
+template <typename T>
+static Routed route_flat(const ColumnsCall<T>& k) {
+    constexpr int VEC = ColumnsCall<T>::VEC;
+    if (!(k.slots && k.tight)) return std::nullopt;
+    const size_t lds_flat = (size_t)k.n_stage * k.C * sizeof(LevelOp<T>) + (size_t)k.C;
+    if (lds_flat > 64 * 1024 && k.n_stage > 1) return ATX_SPLIT_PROGRAM;  // the entry point runs the stages in two halves
+    ATX_REQUIRE(lds_flat <= 64 * 1024, ATX_ENOTIMPL, "pointwise: one stage over %d levels needs %zu B of LDS", k.n_lev, lds_flat);
+    with_flag(k.transcendental(), [&](auto tr) {  // no exp / log anywhere: the low-register instantiation (8 instead of 4 waves per SIMD in float64)
+        hipLaunchKernelGGL((pointwise_cols_flat_kernel<T, VEC, decltype(tr)::value>), k.chunk_grid(), dim3(kBlock), lds_flat, k.st, k.x, k.y, k.n_pts,
+                           k.n_lev, k.C, k.prog, k.n_stage, k.mask, k.in_place);
+    });
+    ATX_LAUNCH_CHECK("pointwise_stack");
+    return ATX_OK;
+}
+
+// Any pitches, any alignment: contiguous chunks of rows.
+template <typename T>
+static Routed route_row_chunk(const ColumnsCall<T>& k) {
+    constexpr int VEC = ColumnsCall<T>::VEC;
+    const size_t lds_rows = level_tables_lds_bytes<T>(k.n_stage, k.C, k.wide ? VEC : 1);
+    if (lds_rows > 64 * 1024 && k.n_stage > 1) return ATX_SPLIT_PROGRAM;  // the entry point runs the stages in two halves
+    ATX_REQUIRE(lds_rows <= 64 * 1024, ATX_ENOTIMPL, "pointwise: one stage over %d levels needs %zu B of LDS", k.n_lev, lds_rows);
+    const int Cg = k.C < kBlock ? k.C : kBlock;
+    const int64_t chunk = (int64_t)(kBlock / Cg) * kPwUnroll;  // rows one workgroup moves per iteration
+    int64_t blocks = (k.n_pts + chunk - 1) / chunk;
+    if (blocks > kStreamGrid) blocks = kStreamGrid;
+    if (k.wide)
+        hipLaunchKernelGGL((pointwise_cols_kernel<T, VEC>), dim3((unsigned)blocks), dim3(kBlock), lds_rows, k.st, k.x, k.y, k.n_pts, k.n_lev, k.C, k.xp,
+                           k.yp, k.prog, k.n_stage, k.mask, k.in_place);
+    else
+        hipLaunchKernelGGL((pointwise_cols_kernel<T, 1>), dim3((unsigned)blocks), dim3(kBlock), lds_rows, k.st, k.x, k.y, k.n_pts, k.n_lev, k.C, k.xp,
+                           k.yp, k.prog, k.n_stage, k.mask, k.in_place);
+    ATX_LAUNCH_CHECK("pointwise_stack");
+    return ATX_OK;
 }
 
 template <typename T>
-__global__ void __launch_bounds__(kBlock)
-reduce_kernel(const T* __restrict__ x, int64_t n_rows, int64_t row_len, int64_t pitch, int red, double* result, double* partials) {
-    const double identity = red == ATX_RED_MIN ? INFINITY : (red == ATX_RED_MAX ? -INFINITY : 0.0);
-    double acc = identity;
-    // rows of `row_len` elements `pitch` apart; (row, col) advances by the grid stride without a division per element
-    const int64_t first = (int64_t)blockIdx.x * kBlock + threadIdx.x, stride = (int64_t)gridDim.x * kBlock;
-    const int64_t d_row = stride / row_len, d_col = stride - d_row * row_len;
-    int64_t row = first / row_len, col = first - row * row_len;
-    while (row < n_rows) {
-        T v[kRedUnroll];
-        bool ok[kRedUnroll];
-#pragma unroll
-        for (int u = 0; u < kRedUnroll; ++u) {
-            ok[u] = row < n_rows;
-            v[u] = ok[u] ? x[row * pitch + col] : T(0);
-            row += d_row;
-            col += d_col;
-            if (col >= row_len) {
-                col -= row_len;
-                ++row;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < kRedUnroll; ++u) {
-            if (!ok[u]) continue;
-            const double d = (double)v[u];
-            if (red == ATX_RED_NANCOUNT) acc += (d != d) ? 1.0 : 0.0;
-            else acc = red_combine(acc, d, red);
-        }
+static int pointwise_columns(const void* x_, void* y_, int64_t n_pts, int n_lev, int64_t xp, int64_t yp, const atx_level_op* prog,
+                             const atx_level_op* vec_prog, const atx_level_op* host_prog, int n_stage, const uint8_t* mask, hipStream_t st) {
+    constexpr int VEC = Vec16<T>::N;
+    ColumnsCall<T> k{static_cast<const T*>(x_), static_cast<T*>(y_), n_pts, n_lev, xp, yp, prog, vec_prog, host_prog, n_stage, mask, st};
+    k.in_place = (x_ == y_ && xp == yp) ? 1 : 0;
+    const int64_t covered = ((int64_t)(n_lev + VEC - 1) / VEC) * VEC;
+    k.wide = aligned16(x_) && aligned16(y_) && (xp % VEC == 0) && (yp % VEC == 0) && covered <= xp && covered <= yp;
+    k.C = k.wide ? (n_lev + VEC - 1) / VEC : n_lev;
+    k.slots = k.wide && yp == xp && xp % VEC == 0 && xp / VEC <= 0x7fffffffll / 2;
+    k.tight = xp == (int64_t)k.C * VEC;
+    k.Cp = k.slots ? (int)(xp / VEC) : 0;
+    k.n_vec = n_pts * k.Cp;
+    k.one_launch = (k.n_vec + kBlock - 1) / kBlock <= 0x7fffffffll;
+    Routed (*const routes[])(const ColumnsCall<T>&) = {route_sparse<T>, route_uniform<T>, route_runs<T>,  route_table<T>,
+                                                     route_typed<T>,  route_levels<T>,  route_flat<T>};
+    for (auto route : routes) {
+        if (const Routed rc = route(k)) return *rc;
     }
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) acc = red_combine(acc, __shfl_down(acc, off, kWave), red);
-    __shared__ double partial[kBlock / kWave];
-    if ((threadIdx.x & (kWave - 1)) == 0) partial[threadIdx.x / kWave] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double total = partial[0];
-        for (int w = 1; w < kBlock / kWave; ++w) total = red_combine(total, partial[w], red);
-        if (partials) {  // one slot per workgroup of the caller's workspace (a[] — or b[] for the MAX pass of a two-pass MINMAX)
-            partials[blockIdx.x] = total;
-        } else if (red == ATX_RED_NANCOUNT) {
-            if (total != 0.0) atomicAdd(result, total);
-        } else {
-            atomic_minmax(result, total, red == ATX_RED_MAX);
-        }
-    }
-}
-
-// The same sweep with 16-byte loads — one (row, vector) item per step, the elements of a row's last vector beyond row_len
-// masked — and with ATX_RED_MINMAX both extremes in ONE pass: the range check of cos_sin_from_rad (R: cos_sin_from_rad.py:73-76,
-// `data.min()` then `data.max()`) read the stack twice at 4.7 TB/s (4-byte loads); this reads it once.
-template <typename T, int VEC>
-__global__ void __launch_bounds__(kBlock)
-reduce_vec_kernel(const T* __restrict__ x, int64_t n_rows, int64_t row_len, int C, int64_t pitch, int red, double* result, RedWorkspace* ws) {
-    using V = Pack<T, VEC>;
-    const bool want_min = red == ATX_RED_MIN || red == ATX_RED_MINMAX, want_max = red == ATX_RED_MAX || red == ATX_RED_MINMAX;
-    double lo = INFINITY, hi = -INFINITY, count = 0.0;
-    bool seen_nan = false;
-    const int64_t n_items = n_rows * C;
-    const int64_t first = (int64_t)blockIdx.x * kBlock + threadIdx.x, stride = (int64_t)gridDim.x * kBlock;
-    const int64_t d_row = stride / C;
-    const int d_col = (int)(stride - d_row * C);
-    int64_t row = first / C;
-    int col = (int)(first - row * C);
-    for (int64_t i = first; i < n_items; i += stride * kRedUnroll) {
-        V v[kRedUnroll];
-        int valid[kRedUnroll];
-#pragma unroll
-        for (int u = 0; u < kRedUnroll; ++u) {
-            const bool ok = row < n_rows;
-            valid[u] = ok ? (int)min((int64_t)VEC, row_len - (int64_t)col * VEC) : 0;
-            if (ok) v[u] = pw_load_nt<T, VEC>(x + row * pitch + (int64_t)col * VEC);  // read once: non-temporal (0.73 -> 0.66 ms f32, 1.33 -> 1.19 ms f64)
-            row += d_row;
-            col += d_col;
-            if (col >= C) {
-                col -= C;
-                ++row;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < kRedUnroll; ++u) {
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) {
-                if (e < valid[u]) {
-                    const double d = (double)v[u].v[e];
-                    if (d != d) {
-                        seen_nan = true;
-                        count += 1.0;
-                    } else {
-                        lo = d < lo ? d : lo;
-                        hi = d > hi ? d : hi;
-                    }
-                }
-            }
-        }
-    }
-    if (seen_nan) lo = hi = NAN;  // np.min / np.max propagate NaN
-    double a = red == ATX_RED_NANCOUNT ? count : (want_min ? lo : hi), b = hi;
-    const int ra = red == ATX_RED_NANCOUNT ? ATX_RED_NANCOUNT : (want_min ? ATX_RED_MIN : ATX_RED_MAX);
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) {
-        a = red_combine(a, __shfl_down(a, off, kWave), ra);
-        if (red == ATX_RED_MINMAX) b = red_combine(b, __shfl_down(b, off, kWave), ATX_RED_MAX);
-    }
-    __shared__ double pa[kBlock / kWave], pb[kBlock / kWave];
-    if ((threadIdx.x & (kWave - 1)) == 0) {
-        pa[threadIdx.x / kWave] = a;
-        pb[threadIdx.x / kWave] = b;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double ta = pa[0], tb = pb[0];
-        for (int w = 1; w < kBlock / kWave; ++w) {
-            ta = red_combine(ta, pa[w], ra);
-            tb = red_combine(tb, pb[w], ATX_RED_MAX);
-        }
-        if (ws) {
-            ws->a[blockIdx.x] = ta;
-            ws->b[blockIdx.x] = tb;
-        } else if (red == ATX_RED_NANCOUNT) {
-            if (ta != 0.0) atomicAdd(result, ta);
-        } else {
-            atomic_minmax(result, ta, !want_min);
-            if (red == ATX_RED_MINMAX) atomic_minmax(result + 1, tb, true);
-        }
-    }
-    (void)want_max;
-}
-
-// The <= 3 elements a flat array leaves after its last whole 16-byte vector, as ONE more pair of partials in the workspace
-// (slot `slot`), so that the two-level finish serves this shape too: no atomics on `result`, which may be a pinned host cell.
-template <typename T>
-__global__ void reduce_tail_kernel(const T* __restrict__ x, int n, int red, RedWorkspace* ws, int slot) {
-    double lo = INFINITY, hi = -INFINITY, count = 0.0;
-    bool seen_nan = false;
-    for (int i = 0; i < n; ++i) {
-        const double d = (double)x[i];
-        if (d != d) {
-            seen_nan = true;
-            count += 1.0;
-        } else {
-            lo = d < lo ? d : lo;
-            hi = d > hi ? d : hi;
-        }
-    }
-    if (seen_nan) lo = hi = NAN;
-    const bool want_min = red == ATX_RED_MIN || red == ATX_RED_MINMAX;
-    ws->a[slot] = red == ATX_RED_NANCOUNT ? count : (want_min ? lo : hi);
-    ws->b[slot] = hi;
-}
-
-static unsigned grid_for(int64_t items) {
-    int64_t b = (items + kBlock - 1) / kBlock;
-    if (b > kMaxGrid) b = kMaxGrid;
-    if (b < 1) b = 1;
-    return (unsigned)b;
+    return *route_row_chunk<T>(k);
 }
 
 template <typename T>
-static int pointwise_typed(const void* x_, void* y_, int64_t n_pts, int n_lev, int64_t xp, int64_t yp, int layout,
-                           const atx_level_op* prog, const atx_level_op* vec_prog, const atx_level_op* host_prog, int n_stage,
-                           const uint8_t* mask, hipStream_t st) {
+static int pointwise_fields(const void* x_, void* y_, int64_t n_pts, int n_lev, int64_t xp, int64_t yp, const atx_level_op* prog,
+                            const atx_level_op* host_prog, int n_stage, const uint8_t* mask, hipStream_t st) {
     const T* x = static_cast<const T*>(x_);
     T* y = static_cast<T*>(y_);
     const int in_place = (x_ == y_ && xp == yp) ? 1 : 0;
     constexpr int VEC = Vec16<T>::N;
     const bool vec_ok = aligned16(x_) && aligned16(y_) && (xp % VEC == 0) && (yp % VEC == 0);
-    if (layout == ATX_COLUMNS) {
-        const int64_t covered = ((int64_t)(n_lev + VEC - 1) / VEC) * VEC;
-        const bool wide = vec_ok && covered <= xp && covered <= yp;
-        const int C = wide ? (n_lev + VEC - 1) / VEC : n_lev;
-        const size_t lds = (size_t)n_stage * C * sizeof(LevelOp<T>);  // (the older chunked kernel's per-vector table)
-#ifndef ATX_PW_SPARSE
-#define ATX_PW_SPARSE 1
-#endif
-        if (ATX_PW_SPARSE && in_place && wide && host_prog && vec_prog) {  // few active levels, in place: visit their columns only
-            ActiveCols active{};
-            bool fits = true;
-            for (int c = 0; c < C && fits; ++c) {
-                bool act = false;
-                for (int s = 0; s < n_stage && !act; ++s)
-                    for (int l = c * VEC; l < n_lev && l < (c + 1) * VEC && !act; ++l) {
-                        const atx_level_op& o = host_prog[(int64_t)s * n_lev + l];
-                        act = o.op != ATX_OP_COPY || o.use_mask != 0;
-                    }
-                if (!act) continue;
-                if (active.n == kMaxActive) fits = false;
-                else active.col[active.n++] = c;
-            }
-            if (fits && active.n == 0) return ATX_OK;  // nothing to do at all
-            if (fits && 3 * active.n <= C) {
-                for (int i = active.n; i < kMaxActive; ++i) active.col[i] = active.col[0];
-                const int64_t n_items = n_pts * active.n;
-                const int64_t blocks = (n_items + kBlock - 1) / kBlock;
-                ATX_REQUIRE(blocks <= 0x7fffffffll, ATX_ENOTIMPL, "pointwise: %lld items exceed one launch", (long long)n_items);
-                hipLaunchKernelGGL((pointwise_cols_sparse_kernel<T, VEC>), dim3((unsigned)blocks), dim3(kBlock), 0, st, y, n_items, n_lev, C, yp,
-                                   active, prog, vec_prog, n_stage, mask);
-                ATX_LAUNCH_CHECK("pointwise_stack_sparse");
-                return ATX_OK;
-            }
-        }
-#ifndef ATX_PW_FLAT
-#define ATX_PW_FLAT 1
-#endif
-        // one contiguous run of vector slots (tight pitch), or — round 3 — equal loose pitches (columns aligned to 128 bytes, a spare
-        // vector): the same kernels walk the pitch / VEC slots of a row and leave the padding slots alone (the row-chunk kernel below:
-        // 0.51-0.57 f32, 0.69 f64 on such stacks)
-        const bool tight = xp == (int64_t)C * VEC;
-        if (ATX_PW_FLAT && wide && yp == xp && xp % VEC == 0 && xp / VEC <= 0x7fffffffll / 2) {
-            const int Cp = (int)(xp / VEC);
-            const int64_t n_vec = n_pts * Cp;
-            // (1) programs uniform over the levels: operators by value, one vector per lane, no loop (pointwise_cols_uniform_kernel)
-#ifndef ATX_PW_UNIFORM
-#define ATX_PW_UNIFORM 1
-#endif
-            UniformOps<T> uni{};
-            if (ATX_PW_UNIFORM && (n_vec + kBlock - 1) / kBlock <= 0x7fffffffll && uniform_level_program<T>(host_prog, n_stage, mask != nullptr, n_lev, VEC, uni)) {
-                bool two_pieces = false, uses_mask = false;
-                unsigned act_bits = 0;
-                for (int s = 0; s < n_stage; ++s) {
-                    two_pieces = two_pieces || uni.split[s] < C;
-                    uses_mask = uses_mask || uni.stage[s].use_mask || uni.second[s].use_mask;
-                    if (uni.stage[s].op != ATX_OP_COPY || uni.stage[s].use_mask) act_bits |= 1u << s;
-                    if (uni.second[s].op != ATX_OP_COPY || uni.second[s].use_mask) act_bits |= 1u << (4 + s);
-                }
-                const int need_rc = (two_pieces || (uses_mask && mask) || !tight) ? 1 : 0;
-                const bool trans = program_has_transcendental(host_prog, n_stage, n_lev);
-#ifndef ATX_PW_UNIFORM_U_IN
-#define ATX_PW_UNIFORM_U_IN 1
-#endif
-#ifndef ATX_PW_UNIFORM_U_OUT
-#define ATX_PW_UNIFORM_U_OUT 1
-#endif
-#ifndef ATX_PW_UNIFORM_NT
-#define ATX_PW_UNIFORM_NT 1
-#endif
-#ifndef ATX_PW_TRANS_U
-#define ATX_PW_TRANS_U 1  // vectors per lane of programs with exp / log (A/B knob, tools/experiments/trans_ab.py)
-#endif
-#ifndef ATX_PW_TRANS_NT
-#define ATX_PW_TRANS_NT 1  // non-temporal accesses for programs with exp / log too
-#endif
-#define ATX_PW_UNIFORM_LAUNCH(TR_, U_, NT_)                                                                                                \
-    hipLaunchKernelGGL((pointwise_cols_uniform_kernel<T, VEC, TR_, U_, NT_>), dim3((unsigned)((n_vec + kBlock * U_ - 1) / (kBlock * U_))), \
-                       dim3(kBlock), 0, st, x, y, n_vec, C, Cp, uni, uses_mask ? mask : nullptr, need_rc, in_place, act_bits)
-#ifndef ATX_PW_MASK_NT
-#define ATX_PW_MASK_NT 0
-#endif
-                const bool nt = ATX_PW_UNIFORM_NT && (ATX_PW_MASK_NT || !(uses_mask && mask));
-                if (in_place) {
-                    if (trans && nt && ATX_PW_TRANS_NT) ATX_PW_UNIFORM_LAUNCH(true, ATX_PW_TRANS_U, true);
-                    else if (trans) ATX_PW_UNIFORM_LAUNCH(true, ATX_PW_TRANS_U, false);
-                    else if (nt) ATX_PW_UNIFORM_LAUNCH(false, ATX_PW_UNIFORM_U_IN, true);
-                    else ATX_PW_UNIFORM_LAUNCH(false, ATX_PW_UNIFORM_U_IN, false);
-                } else {
-                    if (trans && nt && ATX_PW_TRANS_NT) ATX_PW_UNIFORM_LAUNCH(true, ATX_PW_TRANS_U, true);
-                    else if (trans) ATX_PW_UNIFORM_LAUNCH(true, ATX_PW_TRANS_U, false);
-                    else if (nt) ATX_PW_UNIFORM_LAUNCH(false, ATX_PW_UNIFORM_U_OUT, true);
-                    else ATX_PW_UNIFORM_LAUNCH(false, ATX_PW_UNIFORM_U_OUT, false);
-                }
-#undef ATX_PW_UNIFORM_LAUNCH
-                ATX_LAUNCH_CHECK("pointwise_stack_uniform");
-                return ATX_OK;
-            }
-            // (1b) runs of levels with boundaries anywhere (several variables in one column), out of place or in place: by value as well
-#ifndef ATX_PW_RUNS
-#define ATX_PW_RUNS 1
-#endif
-            // Measured against the routes below (tools/experiments/runs_probe.py, profiles/r04_runs_probe.log): evaluating every run's operator and
-            // selecting costs a streaming kernel more than it saves — one stage of 3 runs 0.72 / 0.67 (f32 / f64) here against 0.76 / 0.72 on the
-            // table and per-level kernels — except for float32 programs of two or more stages, which those kernels run at 0.52-0.58 and this one
-            // at 0.65-0.66.  So only they take it.
-            RunOps<T> runs{};
-#ifndef ATX_PW_RUNS_ALL
-#define ATX_PW_RUNS_ALL 0  // A/B: every run-structured program on the runs kernel
-#endif
-            if (ATX_PW_RUNS && (ATX_PW_RUNS_ALL || (sizeof(T) == 4 && n_stage >= 2)) && (n_vec + kBlock - 1) / kBlock <= 0x7fffffffll &&
-                runs_level_program<T>(host_prog, n_stage, mask != nullptr, n_lev, runs)) {
-                bool uses_mask = false;
-                for (int s = 0; s < n_stage; ++s)
-                    for (int r = 0; r < runs.n_run[s]; ++r) uses_mask = uses_mask || runs.op[s][r].use_mask != 0;
-                const bool trans = program_has_transcendental(host_prog, n_stage, n_lev);
-                const bool nt = !(uses_mask && mask);
-                const dim3 grid((unsigned)((n_vec + kBlock - 1) / kBlock));
-#define ATX_PW_RUNS_LAUNCH(TR_, NT_) \
-    hipLaunchKernelGGL((pointwise_cols_runs_kernel<T, VEC, TR_, NT_>), grid, dim3(kBlock), 0, st, x, y, n_vec, C, Cp, runs, uses_mask ? mask : nullptr)
-                if (trans) { if (nt) ATX_PW_RUNS_LAUNCH(true, true); else ATX_PW_RUNS_LAUNCH(true, false); }
-                else { if (nt) ATX_PW_RUNS_LAUNCH(false, true); else ATX_PW_RUNS_LAUNCH(false, false); }
-#undef ATX_PW_RUNS_LAUNCH
-                ATX_LAUNCH_CHECK("pointwise_stack_runs");
-                return ATX_OK;
-            }
-            // (2) operators differing from level to level.  Measured (137 levels of O1280, profiles/r03_pointwise_ab.log): the table
-            // kernel (one vector per lane, no loop, operators from the host-built per-vector table) wins for
-            // one-stage f32 programs without a mask, out of place (1.21 ms both) AND in place (1.22 vs 1.36 ms chunked); it loses in f64
-            // (2.48 vs 2.37 ms), with two stages (f32 1.56 vs 1.28, f64 3.38 vs 2.58 ms: 24-32 B of operators per stage and vector) and
-            // with a point mask in f64 (2.74 vs 2.43 ms).  ATX_PW_TABLE_RULE: 0 = round 2's rule (out of place only), 1 = this rule.
-#ifndef ATX_PW_TABLE_RULE
-#define ATX_PW_TABLE_RULE 1
-#endif
-            const bool table_narrow = !mask && sizeof(T) == 4 && n_stage == 1 && !in_place;
-            const bool table_wide = ATX_PW_TABLE_RULE == 1 && !mask && sizeof(T) == 4 && n_stage == 1;
-            if (tight && vec_prog && (table_narrow || table_wide) && (n_vec + kBlock - 1) / kBlock <= 0x7fffffffll &&
-                !program_has_mixed_vectors<T>(host_prog, n_stage, n_lev, VEC)) {  // (mixed vectors: the chunked kernel serves them better)
-                hipLaunchKernelGGL((pointwise_cols_table_kernel<T, VEC>), dim3((unsigned)((n_vec + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
-                                   x, y, n_vec, n_lev, C, prog, vec_prog, n_stage, mask, in_place);
-                ATX_LAUNCH_CHECK("pointwise_stack");
-                return ATX_OK;
-            }
-            // (3) one stage, one operator kind per vector (a scale per level), float64 or in place: the no-loop kernel on the typed
-            // per-level part of vec_prog (pointwise_cols_typed_kernel; everything else measured faster on the per-level LDS kernel below)
-#ifndef ATX_PW_TYPED
-#define ATX_PW_TYPED 1
-#endif
-            if (ATX_PW_TYPED && tight && n_stage == 1 && (sizeof(T) == 8 || in_place) && vec_prog && aligned16(vec_prog) && host_prog &&
-                (n_vec + kBlock - 1) / kBlock <= 0x7fffffffll) {
-                bool one_kind = true, uses_mask = false;
-                for (int l0 = 0; l0 < n_lev && one_kind; l0 += VEC)
-                    for (int l = l0; l < n_lev && l < l0 + VEC; ++l) {
-                        one_kind = one_kind && host_prog[l].op == host_prog[l0].op && (host_prog[l].use_mask != 0) == (host_prog[l0].use_mask != 0);
-                        uses_mask = uses_mask || host_prog[l].use_mask != 0;
-                    }
-                if (one_kind && (sizeof(T) == 8 || !(uses_mask && mask))) {  // (float32 with the point mask: 0.69 here against 0.71-0.75)
-                    const unsigned char* level_tables = reinterpret_cast<const unsigned char*>(vec_prog) +
-                                                        level_tables_layout(1, n_lev, sizeof(T) == 4 ? ATX_F32 : ATX_F64).levels_offset;
-                    const bool trans = program_has_transcendental(host_prog, n_stage, n_lev);
-                    const bool nt = !(uses_mask && mask);
-                    const dim3 grid((unsigned)((n_vec + kBlock - 1) / kBlock));
-#define ATX_PW_TYPED_LAUNCH(TR_, NT_)                                                                                               \
-    hipLaunchKernelGGL((pointwise_cols_typed_kernel<T, VEC, TR_, NT_>), grid, dim3(kBlock), 0, st, x, y, n_vec, C, level_tables, \
-                       uses_mask ? mask : nullptr, in_place)
-                    if (trans) { if (nt) ATX_PW_TYPED_LAUNCH(true, true); else ATX_PW_TYPED_LAUNCH(true, false); }
-                    else { if (nt) ATX_PW_TYPED_LAUNCH(false, true); else ATX_PW_TYPED_LAUNCH(false, false); }
-#undef ATX_PW_TYPED_LAUNCH
-                    ATX_LAUNCH_CHECK("pointwise_stack_typed");
-                    return ATX_OK;
-                }
-            }
-            const int64_t n_chunks = (n_vec + (int64_t)kBlock * kPwUnroll - 1) / ((int64_t)kBlock * kPwUnroll);
-            int64_t blocks = n_chunks > kMaxGrid ? kMaxGrid : n_chunks;
-            const int64_t per = (n_chunks + blocks - 1) / blocks;
-            blocks = (n_chunks + per - 1) / per;  // contiguous runs of `per` chunks: no workgroup without work
-#ifndef ATX_PW_LEVELS
-#define ATX_PW_LEVELS 1  // 0: round 2's chunked kernel (per-vector operators in LDS, mixed vectors from the global program)
-#endif
-            const size_t lds_levels = level_tables_lds_bytes<T>(n_stage, C, VEC) + (size_t)C;
-            // (loose pitches: measured slower here than on the row-chunk kernel below — f64 0.57 against 0.69 — so only the by-value
-            // kernel above takes them; tools/experiments/loose_pitch.py)
-            if (ATX_PW_LEVELS && tight && lds_levels <= 64 * 1024) {
-#ifndef ATX_PW_LEVELS_NT
-#define ATX_PW_LEVELS_NT 1
-#endif
-                bool nt = ATX_PW_LEVELS_NT && sizeof(T) == 4 && host_prog != nullptr;
-                if (nt && in_place) {  // every vector must be touched
-                    for (int c = 0; c < C && nt; ++c) {
-                        bool act = false;
-                        for (int s = 0; s < n_stage && !act; ++s)
-                            for (int l = c * VEC; l < n_lev && l < (c + 1) * VEC && !act; ++l)
-                                act = host_prog[(int64_t)s * n_lev + l].op != ATX_OP_COPY || host_prog[(int64_t)s * n_lev + l].use_mask != 0;
-                        nt = act;
-                    }
-                }
-                if (program_has_transcendental(host_prog, n_stage, n_lev))
-                    hipLaunchKernelGGL((pointwise_cols_levels_kernel<T, VEC, true, false>), dim3((unsigned)blocks), dim3(kBlock), lds_levels, st, x, y,
-                                       n_pts, n_lev, C, Cp, prog, n_stage, mask, in_place);
-                else if (nt)
-                    hipLaunchKernelGGL((pointwise_cols_levels_kernel<T, VEC, false, true>), dim3((unsigned)blocks), dim3(kBlock), lds_levels, st, x, y,
-                                       n_pts, n_lev, C, Cp, prog, n_stage, mask, in_place);
-                else
-                    hipLaunchKernelGGL((pointwise_cols_levels_kernel<T, VEC, false, false>), dim3((unsigned)blocks), dim3(kBlock), lds_levels, st, x, y,
-                                       n_pts, n_lev, C, Cp, prog, n_stage, mask, in_place);
-                ATX_LAUNCH_CHECK("pointwise_stack_levels");
-                return ATX_OK;
-            }
-            if (tight) {  // very tall stacks: round 2's chunked kernel, whose per-VECTOR table is smaller (tight pitches only)
-                const size_t lds_flat = lds + (size_t)C;
-                if (lds_flat > 64 * 1024 && n_stage > 1) return ATX_SPLIT_PROGRAM;  // the entry point runs the stages in two halves
-                ATX_REQUIRE(lds_flat <= 64 * 1024, ATX_ENOTIMPL, "pointwise: one stage over %d levels needs %zu B of LDS", n_lev, lds_flat);
-                if (program_has_transcendental(host_prog, n_stage, n_lev))
-                    hipLaunchKernelGGL((pointwise_cols_flat_kernel<T, VEC, true>), dim3((unsigned)blocks), dim3(kBlock), lds_flat, st, x, y, n_pts,
-                                       n_lev, C, prog, n_stage, mask, in_place);
-                else  // no exp / log anywhere in the program: the low-register instantiation (8 instead of 4 waves per SIMD in float64)
-                    hipLaunchKernelGGL((pointwise_cols_flat_kernel<T, VEC, false>), dim3((unsigned)blocks), dim3(kBlock), lds_flat, st, x, y, n_pts,
-                                       n_lev, C, prog, n_stage, mask, in_place);
-                ATX_LAUNCH_CHECK("pointwise_stack");
-                return ATX_OK;
-            }
-        }
-        const size_t lds_rows = level_tables_lds_bytes<T>(n_stage, C, wide ? VEC : 1);
-        if (lds_rows > 64 * 1024 && n_stage > 1) return ATX_SPLIT_PROGRAM;  // the entry point runs the stages in two halves
-        ATX_REQUIRE(lds_rows <= 64 * 1024, ATX_ENOTIMPL, "pointwise: one stage over %d levels needs %zu B of LDS", n_lev, lds_rows);
-        const int Cg = C < kBlock ? C : kBlock;
-        const int64_t chunk = (int64_t)(kBlock / Cg) * kPwUnroll;  // rows one workgroup moves per iteration
-        int64_t blocks = (n_pts + chunk - 1) / chunk;
-        if (blocks > kMaxGrid) blocks = kMaxGrid;
-        if (wide)
-            hipLaunchKernelGGL((pointwise_cols_kernel<T, VEC>), dim3((unsigned)blocks), dim3(kBlock), lds_rows, st, x, y, n_pts, n_lev, C, xp,
-                               yp, prog, n_stage, mask, in_place);
-        else
-            hipLaunchKernelGGL((pointwise_cols_kernel<T, 1>), dim3((unsigned)blocks), dim3(kBlock), lds_rows, st, x, y, n_pts, n_lev, C, xp,
-                               yp, prog, n_stage, mask, in_place);
-    } else {
-        ATX_REQUIRE(n_lev <= 65535, ATX_ENOTIMPL, "pointwise: n_lev=%d exceeds grid.y", n_lev);
-        {
-            const int vec = vec_ok ? VEC : 1;
-            const int64_t per_block = (int64_t)kBlock * fields_vectors_per_lane<T>();
-            const int64_t gx_rows = (std::max<int64_t>(n_pts / vec, 1) + per_block - 1) / per_block;
-            ATX_REQUIRE(gx_rows <= 0x7fffffffll, ATX_ENOTIMPL, "pointwise: %lld points per field exceed one launch", (long long)n_pts);
-            {
-                bool uses_mask = mask != nullptr;  // unknown program: assume it reads the mask it was given
-                if (host_prog && mask) {
-                    uses_mask = false;
-                    for (int64_t i = 0; i < (int64_t)n_stage * n_lev; ++i) uses_mask = uses_mask || host_prog[i].use_mask != 0;
-                }
-                const bool trans = program_has_transcendental(host_prog, n_stage, n_lev);
-                const bool nt = !uses_mask;
-                const int mask_vec = (reinterpret_cast<uintptr_t>(mask) % (uintptr_t)vec) == 0 ? 1 : 0;
-                const dim3 grid((unsigned)gx_rows, (unsigned)n_lev);
-#define ATX_PW_ROWS_LAUNCH(V_, TR_, NT_)                                                                                                 \
-    hipLaunchKernelGGL((pointwise_fields_rows_kernel<T, V_, TR_, NT_>), grid, dim3(kBlock), 0, st, x, y, n_pts, n_lev, xp, yp, prog, n_stage, \
-                       mask, in_place, mask_vec)
-                if (vec_ok) {
-                    if (trans) { if (nt) ATX_PW_ROWS_LAUNCH(VEC, true, true); else ATX_PW_ROWS_LAUNCH(VEC, true, false); }
-                    else { if (nt) ATX_PW_ROWS_LAUNCH(VEC, false, true); else ATX_PW_ROWS_LAUNCH(VEC, false, false); }
-                } else {
-                    if (trans) ATX_PW_ROWS_LAUNCH(1, true, false);
-                    else ATX_PW_ROWS_LAUNCH(1, false, false);
-                }
-#undef ATX_PW_ROWS_LAUNCH
-                ATX_LAUNCH_CHECK("pointwise_stack_fields");
-                return ATX_OK;
-            }
-        }
+    ATX_REQUIRE(n_lev <= 65535, ATX_ENOTIMPL, "pointwise: n_lev=%d exceeds grid.y", n_lev);
+    const int vec = vec_ok ? VEC : 1;
+    const int64_t per_block = (int64_t)kBlock * fields_vectors_per_lane<T>();
+    const int64_t gx_rows = (std::max<int64_t>(n_pts / vec, 1) + per_block - 1) / per_block;
+    ATX_REQUIRE(gx_rows <= 0x7fffffffll, ATX_ENOTIMPL, "pointwise: %lld points per field exceed one launch", (long long)n_pts);
+    bool uses_mask = mask != nullptr;  // unknown program: assume it reads the mask it was given
+    if (host_prog && mask) {
+        uses_mask = false;
+        for (int64_t i = 0; i < (int64_t)n_stage * n_lev; ++i) uses_mask = uses_mask || host_prog[i].use_mask != 0;
     }
-    ATX_LAUNCH_CHECK("pointwise_stack");
+    const bool trans = program_has_transcendental(host_prog, n_stage, n_lev);
+    const int mask_vec = (reinterpret_cast<uintptr_t>(mask) % (uintptr_t)vec) == 0 ? 1 : 0;
+    const dim3 grid((unsigned)gx_rows, (unsigned)n_lev);
+    if (vec_ok)  // non-temporal when no mask is read
+        with_trans_nt(trans, !uses_mask, [&](auto tr, auto n) {
+            hipLaunchKernelGGL((pointwise_fields_rows_kernel<T, VEC, decltype(tr)::value, decltype(n)::value>), grid, dim3(kBlock), 0, st, x, y, n_pts,
+                               n_lev, xp, yp, prog, n_stage, mask, in_place, mask_vec);
+        });
+    else
+        with_flag(trans, [&](auto tr) {
+            hipLaunchKernelGGL((pointwise_fields_rows_kernel<T, 1, decltype(tr)::value, false>), grid, dim3(kBlock), 0, st, x, y, n_pts, n_lev, xp, yp,
+                               prog, n_stage, mask, in_place, mask_vec);
+        });
+    ATX_LAUNCH_CHECK("pointwise_stack_fields");
     return ATX_OK;
 }
 
@@ -1324,9 +815,14 @@ extern "C" int atx_pointwise_stack(const void* x, void* y, int64_t n_pts, int64_
                 (long long)x_pitch, (long long)y_pitch, (long long)need);
     if (n_pts == 0) return ATX_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int rc = dtype == ATX_F32
-        ? pointwise_typed<float>(x, y, n_pts, (int)n_lev, x_pitch, y_pitch, layout, prog, vec_prog, host_prog, n_stage, point_mask, s)
-        : pointwise_typed<double>(x, y, n_pts, (int)n_lev, x_pitch, y_pitch, layout, prog, vec_prog, host_prog, n_stage, point_mask, s);
+    const int L = (int)n_lev;
+    int rc;
+    if (layout == ATX_COLUMNS)
+        rc = dtype == ATX_F32 ? pointwise_columns<float>(x, y, n_pts, L, x_pitch, y_pitch, prog, vec_prog, host_prog, n_stage, point_mask, s)
+                              : pointwise_columns<double>(x, y, n_pts, L, x_pitch, y_pitch, prog, vec_prog, host_prog, n_stage, point_mask, s);
+    else
+        rc = dtype == ATX_F32 ? pointwise_fields<float>(x, y, n_pts, L, x_pitch, y_pitch, prog, host_prog, n_stage, point_mask, s)
+                              : pointwise_fields<double>(x, y, n_pts, L, x_pitch, y_pitch, prog, host_prog, n_stage, point_mask, s);
     if (rc != ATX_SPLIT_PROGRAM) return rc;
     // The program's per-level tables exceed the LDS budget (n_stage > 1 here): stages compose, y = s_{n-1}( ... s_0(x)), so the first
     // half goes x -> y and the second half y -> y in place — same statements in the same order, same bits.  vec_prog is laid out for the
@@ -1336,176 +832,4 @@ extern "C" int atx_pointwise_stack(const void* x, void* y, int64_t n_pts, int64_
     if (rc_first != ATX_OK) return rc_first;
     return atx_pointwise_stack(y, y, n_pts, n_lev, y_pitch, y_pitch, dtype, layout, prog + (int64_t)first * n_lev, nullptr,
                                host_prog ? host_prog + (int64_t)first * n_lev : nullptr, n_stage - first, point_mask, stream);
-}
-
-extern "C" int atx_mask_build(const void* m, int64_t m_stride, uint8_t* mask, int64_t n, int cmp, double threshold,
-                              int dtype, void* stream) {
-    ATX_REQUIRE((m && mask) || n == 0, ATX_EINVAL, "atx_mask_build: null pointer");
-    ATX_REQUIRE(n >= 0 && m_stride >= 1, ATX_EINVAL, "atx_mask_build: bad n=%lld / stride=%lld", (long long)n, (long long)m_stride);
-    ATX_REQUIRE(cmp >= ATX_CMP_GT && cmp <= ATX_CMP_ISNAN, ATX_EINVAL, "atx_mask_build: bad comparison %d", cmp);
-    ATX_REQUIRE(dtype == ATX_F32 || dtype == ATX_F64, ATX_EINVAL, "atx_mask_build: bad dtype %d", dtype);
-    ATX_REQUIRE((reinterpret_cast<uintptr_t>(mask) & 3u) == 0, ATX_EALIGN, "atx_mask_build: mask must be 4-byte aligned");
-    if (n == 0) return ATX_OK;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const unsigned g = grid_for((n + 3) / 4);
-    if (dtype == ATX_F32)
-        hipLaunchKernelGGL(mask_build_kernel<float>, dim3(g), dim3(kBlock), 0, s, static_cast<const float*>(m), m_stride, mask, n, cmp, (float)threshold);
-    else
-        hipLaunchKernelGGL(mask_build_kernel<double>, dim3(g), dim3(kBlock), 0, s, static_cast<const double*>(m), m_stride, mask, n, cmp, threshold);
-    ATX_LAUNCH_CHECK("mask_build");
-    return ATX_OK;
-}
-
-extern "C" int atx_mask_count(const uint8_t* mask, int64_t n, int64_t* count, void* stream) {
-    ATX_REQUIRE(count && (mask || n == 0), ATX_EINVAL, "atx_mask_count: null pointer");
-    ATX_REQUIRE(n >= 0, ATX_EINVAL, "atx_mask_count: negative n");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    int st = hip_status(hipMemsetAsync(count, 0, sizeof(int64_t), s), "atx_mask_count memset");
-    if (st != ATX_OK) return st;
-    if (n == 0) return ATX_OK;
-    const unsigned count_grid = grid_for(n) > 2048u ? 2048u : grid_for(n);  // one atomic per wave on one address: keep them few
-    hipLaunchKernelGGL(mask_count_kernel, dim3(count_grid), dim3(kBlock), 0, s, mask, n, reinterpret_cast<unsigned long long*>(count));
-    ATX_LAUNCH_CHECK("mask_count");
-    return ATX_OK;
-}
-
-extern "C" size_t atx_mask_to_index_workspace(int64_t n) {
-    if (n < 0) return 0;
-    const int64_t n_blocks = (n + kChunk - 1) / kChunk;
-    return (size_t)((n_blocks + 1) * sizeof(int32_t) + 15) & ~size_t(15);
-}
-
-extern "C" int atx_mask_to_index(const uint8_t* mask, int64_t n, int32_t* index, int64_t* count, void* workspace,
-                                 size_t workspace_bytes, void* stream) {
-    ATX_REQUIRE(count && workspace && ((mask && index) || n == 0), ATX_EINVAL, "atx_mask_to_index: null pointer");
-    ATX_REQUIRE(n >= 0 && n <= INT32_MAX, ATX_EINVAL, "atx_mask_to_index: n=%lld outside int32", (long long)n);
-    ATX_REQUIRE(workspace_bytes >= atx_mask_to_index_workspace(n), ATX_EWORKSPACE, "atx_mask_to_index: workspace %zu < %zu",
-                workspace_bytes, atx_mask_to_index_workspace(n));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (n == 0) return hip_status(hipMemsetAsync(count, 0, sizeof(int64_t), s), "atx_mask_to_index memset");
-    const int n_blocks = (int)((n + kChunk - 1) / kChunk);
-    int32_t* block_counts = static_cast<int32_t*>(workspace);
-    hipLaunchKernelGGL(compact_count_kernel, dim3(n_blocks), dim3(kBlock), 0, s, mask, n, block_counts);
-    ATX_LAUNCH_CHECK("compact_count");
-#ifndef ATX_COMPACT_SELF_SCAN
-#define ATX_COMPACT_SELF_SCAN 4096  // workgroups up to which the scatter sums the counts before it by itself (16 M points); 0: never
-#endif
-    if (n_blocks <= ATX_COMPACT_SELF_SCAN) {
-        hipLaunchKernelGGL(compact_scatter_kernel<true>, dim3(n_blocks), dim3(kBlock), 0, s, mask, n, block_counts, index, reinterpret_cast<long long*>(count));
-        ATX_LAUNCH_CHECK("compact_scatter");
-        return ATX_OK;
-    }
-    hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(1024), 0, s, block_counts, n_blocks, reinterpret_cast<long long*>(count));
-    ATX_LAUNCH_CHECK("compact_scan");
-    hipLaunchKernelGGL(compact_scatter_kernel<false>, dim3(n_blocks), dim3(kBlock), 0, s, mask, n, block_counts, index, nullptr);
-    ATX_LAUNCH_CHECK("compact_scatter");
-    return ATX_OK;
-}
-
-static int reduce_rows(const void* x, int64_t n_rows, int64_t row_len, int64_t pitch, int red, double* result, int dtype,
-                       void* workspace, size_t workspace_bytes, void* stream, const char* who) {
-    ATX_REQUIRE(n_rows >= 0 && row_len >= 0, ATX_EINVAL, "%s: negative size", who);
-    ATX_REQUIRE(result && (x || n_rows == 0 || row_len == 0), ATX_EINVAL, "%s: null pointer", who);  // (an empty array may have no storage)
-    ATX_REQUIRE(pitch >= row_len, ATX_ESHAPE, "%s: pitch %lld shorter than a row of %lld", who, (long long)pitch, (long long)row_len);
-    ATX_REQUIRE(red >= ATX_RED_MIN && red <= ATX_RED_MINMAX, ATX_EINVAL, "%s: bad reduction %d", who, red);
-    ATX_REQUIRE(dtype == ATX_F32 || dtype == ATX_F64, ATX_EINVAL, "%s: bad dtype %d", who, dtype);
-    ATX_REQUIRE(!workspace || workspace_bytes >= sizeof(RedWorkspace), ATX_EWORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes,
-                sizeof(RedWorkspace));
-    ATX_REQUIRE(!workspace || (reinterpret_cast<uintptr_t>(workspace) & 7u) == 0, ATX_EALIGN, "%s: workspace must be 8-byte aligned", who);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    // 16-byte loads when every row starts on a 16-byte boundary and its last (partial) vector lies inside the pitch (a flat array is
-    // one row: only the base must be aligned); MINMAX exists in this form only and falls back to two scalar passes otherwise
-    const int vec = dtype == ATX_F32 ? 4 : 2;
-    // a flat array (one row, no pitch to hide a partial vector in): whole vectors through the vector kernel, the <= 3 elements
-    // left over through the scalar one — the library never reads past x[n)
-    const int64_t tail = (n_rows == 1) ? row_len % vec : 0;
-    const int64_t vec_len = row_len - tail;
-    const int64_t C = (vec_len + vec - 1) / vec;
-    const bool vec_ok = aligned16(x) && (n_rows == 1 || (pitch % vec == 0 && C * vec <= pitch)) && C <= 0x7fffffff;
-    // With a workspace EVERY shape finishes in two levels — partials with plain stores, one combining workgroup, a plain store of the
-    // result, which may therefore be a pinned host cell: the single-pass case, a flat array's tail after its last whole vector (one
-    // more slot), the scalar fallback's two MINMAX passes (MIN into a[], MAX into b[]) and empty input (the identities).  Without
-    // one the workgroups combine through atomics on `result`, which must then be device memory (round 3 dropped the workspace for
-    // every shape but the first and ran up to 8192 CAS loops over PCIe on the caller's pinned cell — the advisor's finding).
-    RedWorkspace* ws = static_cast<RedWorkspace*>(workspace);
-    const int ra = red == ATX_RED_NANCOUNT ? ATX_RED_NANCOUNT : ((red == ATX_RED_MIN || red == ATX_RED_MINMAX) ? ATX_RED_MIN : ATX_RED_MAX);
-    if (!ws) {
-        hipLaunchKernelGGL(reduce_init_kernel, dim3(1), dim3(1), 0, s, result, red);
-        ATX_LAUNCH_CHECK("reduce_init");
-    }
-    if (n_rows == 0 || row_len == 0) {
-        if (ws) {  // nothing to combine: the identities (min +inf, max -inf, count 0), as reduce_init writes them
-            hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(kBlock), 0, s, ws, 0, ra, red, result);
-            ATX_LAUNCH_CHECK("reduce_final");
-        }
-        return ATX_OK;
-    }
-    const int64_t grid_cap = kRedGrid - (tail > 0 ? 1 : 0);  // a tail takes one slot of the workspace
-    if (vec_ok) {
-        unsigned grid = 0;
-        if (C > 0) {
-            int64_t blocks = (n_rows * C + (int64_t)kBlock * kRedUnroll - 1) / ((int64_t)kBlock * kRedUnroll);
-            grid = (unsigned)(blocks > grid_cap ? grid_cap : (blocks < 1 ? 1 : blocks));
-            if (dtype == ATX_F32)
-                hipLaunchKernelGGL((reduce_vec_kernel<float, 4>), dim3(grid), dim3(kBlock), 0, s, static_cast<const float*>(x), n_rows, vec_len, (int)C, pitch, red, result, ws);
-            else
-                hipLaunchKernelGGL((reduce_vec_kernel<double, 2>), dim3(grid), dim3(kBlock), 0, s, static_cast<const double*>(x), n_rows, vec_len, (int)C, pitch, red, result, ws);
-            ATX_LAUNCH_CHECK("reduce_vec");
-        }
-        if (tail > 0) {
-            const size_t esz = dtype == ATX_F32 ? 4 : 8;
-            const void* xt = static_cast<const char*>(x) + (size_t)vec_len * esz;
-            if (ws) {
-                if (dtype == ATX_F32)
-                    hipLaunchKernelGGL(reduce_tail_kernel<float>, dim3(1), dim3(1), 0, s, static_cast<const float*>(xt), (int)tail, red, ws, (int)grid);
-                else
-                    hipLaunchKernelGGL(reduce_tail_kernel<double>, dim3(1), dim3(1), 0, s, static_cast<const double*>(xt), (int)tail, red, ws, (int)grid);
-                grid += 1;
-            } else {  // combines into the same result cells (atomics): MINMAX as min -> result[0], max -> result[1]
-                for (int pass = 0; pass < (red == ATX_RED_MINMAX ? 2 : 1); ++pass) {
-                    const int r = red == ATX_RED_MINMAX ? (pass == 0 ? ATX_RED_MIN : ATX_RED_MAX) : red;
-                    if (dtype == ATX_F32)
-                        hipLaunchKernelGGL(reduce_kernel<float>, dim3(1), dim3(kBlock), 0, s, static_cast<const float*>(xt), (int64_t)1, tail, tail, r, result + pass, (double*)nullptr);
-                    else
-                        hipLaunchKernelGGL(reduce_kernel<double>, dim3(1), dim3(kBlock), 0, s, static_cast<const double*>(xt), (int64_t)1, tail, tail, r, result + pass, (double*)nullptr);
-                }
-            }
-            ATX_LAUNCH_CHECK("reduce_tail");
-        }
-        if (ws) {
-            hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(kBlock), 0, s, ws, (int)grid, ra, red, result);
-            ATX_LAUNCH_CHECK("reduce_final");
-        }
-        return ATX_OK;
-    }
-    // scalar form (unaligned base or pitch): one pass, or MIN then MAX for MINMAX
-    int64_t blocks = (n_rows * row_len + (int64_t)kBlock * kRedUnroll - 1) / ((int64_t)kBlock * kRedUnroll);
-    const unsigned grid = (unsigned)(blocks > kRedGrid ? kRedGrid : (blocks < 1 ? 1 : blocks));
-    for (int pass = 0; pass < (red == ATX_RED_MINMAX ? 2 : 1); ++pass) {
-        const int r = red == ATX_RED_MINMAX ? (pass == 0 ? ATX_RED_MIN : ATX_RED_MAX) : red;
-        double* partials = ws ? (pass == 0 ? ws->a : ws->b) : nullptr;
-        if (dtype == ATX_F32)
-            hipLaunchKernelGGL(reduce_kernel<float>, dim3(grid), dim3(kBlock), 0, s, static_cast<const float*>(x), n_rows, row_len, pitch, r, result + pass, partials);
-        else
-            hipLaunchKernelGGL(reduce_kernel<double>, dim3(grid), dim3(kBlock), 0, s, static_cast<const double*>(x), n_rows, row_len, pitch, r, result + pass, partials);
-    }
-    ATX_LAUNCH_CHECK("reduce");
-    if (ws) {
-        hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(kBlock), 0, s, ws, (int)grid, ra, red, result);
-        ATX_LAUNCH_CHECK("reduce_final");
-    }
-    return ATX_OK;
-}
-
-extern "C" size_t atx_reduce_workspace(void) { return sizeof(RedWorkspace); }
-
-extern "C" int atx_reduce(const void* x, int64_t n, int red, double* result, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
-    return reduce_rows(x, 1, n, n, red, result, dtype, workspace, workspace_bytes, stream, "atx_reduce");
-}
-
-extern "C" int atx_reduce_stack(const void* x, int64_t n_pts, int64_t n_lev, int64_t pitch, int red, double* result,
-                                int dtype, int layout, void* workspace, size_t workspace_bytes, void* stream) {
-    ATX_REQUIRE(layout == ATX_COLUMNS || layout == ATX_FIELDS, ATX_EINVAL, "atx_reduce_stack: bad layout %d", layout);
-    if (layout == ATX_COLUMNS) return reduce_rows(x, n_pts, n_lev, pitch, red, result, dtype, workspace, workspace_bytes, stream, "atx_reduce_stack");
-    return reduce_rows(x, n_lev, n_pts, pitch, red, result, dtype, workspace, workspace_bytes, stream, "atx_reduce_stack");
 }

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """apply_mask over a 137-level O1280 column stack (the by-value kernel with a point mask): time and parity, for an A/B of library builds
-(ATX_LIBRARY=...): the mask byte per lane against ONE scalar fetch per wave (-DATX_PW_MASK_WAVE=1)."""
+(ATX_LIBRARY=...).  Round 4 used it for the mask byte per lane (kept) against one scalar fetch per wave and non-temporal data accesses
+(profiles/r04_apply_mask_experiment.log)."""
 from __future__ import annotations
 
 import os

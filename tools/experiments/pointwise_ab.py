@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
 """Interleaved A/B of `atx_pointwise_stack` across builds of libatx in ONE process on ONE GPU (round 3: the f64 per-point
-"regression" the round-2 judge traced to commit 702e31f).
+"regression" the round-2 judge traced to commit 702e31f).  The per-point dispatch has no build-time knobs any more (HISTORY.md,
+"The per-point kernels' A/B knobs, frozen"): the other side of a comparison is an earlier commit or the grid cap.
 
-    bash tools/build_variant.sh pre702e31f --rev 702e31f~1
-    bash tools/build_variant.sh table0 -DATX_PW_TABLE_STAGES=0          # round 2's dispatch rule, today's sources
-    bash tools/build_variant.sh nocap  -DATX_PW_TABLE_STAGES=0 -DATX_MAX_GRID=2147483647
+    bash tools/build_variant.sh parent --rev HEAD~1
+    bash tools/build_variant.sh nocap  -DATX_MAX_GRID=2147483647
     python tools/experiments/pointwise_ab.py --libs head=anemoi-transform_amd/lib/libatx.so \
-        pre=anemoi-transform_amd/lib/variants/libatx_pre702e31f.so:old table0=... nocap=...
+        parent=anemoi-transform_amd/lib/variants/libatx_parent.so nocap=...
 
 A `:old` suffix marks a build with the 13-argument entry point (before `host_prog` was added).  Cases: one- and two-stage affine
 programs, f32 / f64, out of place / in place, with and without the point mask; the library's fixed `atx_stream_copy` of the same

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """atx_reduce_stack (min+max in one pass, min, NaN count) over 137 levels of O1280 and over one field, for an A/B of library builds
-(ATX_LIBRARY=...; -DATX_RED_GRID=<workgroup cap>: the partials of the two-level finish scale with it)."""
+(ATX_LIBRARY=...).  Round 4 chose the workgroup cap of the reduction with it (kRedGrid in atx_reduce.hip, profiles/r04_reduce_grid.log)."""
 from __future__ import annotations
 
 import os

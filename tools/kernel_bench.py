@@ -46,6 +46,8 @@ def main():
     ap.add_argument("--only-vertical", action="store_true", help="only the column kernel (atx_pressure_at_height_stack) rows")
     ap.add_argument("--only-rotate", action="store_true", help="only the vector-frame kernel (atx_rotate_vectors_stack) rows")
     ap.add_argument("--only-obs", action="store_true", help="only the observation-gridding rows (atx_obs_best_per_cell, atx_obs_fill_stack)")
+    ap.add_argument("--only-pointwise", action="store_true", help="only the per-point, mask and reduction rows (atx_pointwise.hip, atx_mask.hip, "
+                    "atx_reduce.hip), each with a checksum of what it computed on the seeded stack")
     args = ap.parse_args()
     graft.load_package()
     from anemoi_transform_amd import interp, native
@@ -170,6 +172,88 @@ def main():
             del date, values, uniform, swath, best, winner
             torch.cuda.empty_cache()
 
+    def checksum(out):
+        """Order-sensitive 128-bit checksum of a tensor's bytes, summed on the device in wrapping int64; anything else by its repr."""
+        if not torch.is_tensor(out):
+            return repr(out)
+        w = out.contiguous().view(-1).view(torch.int32 if out.element_size() == 4 else (torch.int64 if out.element_size() == 8 else torch.uint8))
+        a = b = 0
+        for i in range(0, w.numel(), 1 << 26):
+            c = w[i:i + (1 << 26)].to(torch.int64)
+            a += int(c.sum())
+            b += int((c * (torch.arange(i, i + c.numel(), device=c.device) | 1)).sum())
+        return f"{a & (2**64 - 1):016x}{b & (2**64 - 1):016x}"
+
+    def pointwise_rows(tdt, B, tag, x=None):
+        """The rows that run kernels of atx_pointwise.hip, atx_mask.hip and atx_reduce.hip, on the seeded stack `x` (made here when
+        the caller has none).  `digest` is the checksum of what ONE call of the row computes: an in-place row starts from a copy of x."""
+        x = x if x is not None else bench.synth_stack(src_grid, L, tdt, dev, 0, COLUMNS)
+        y = x.new_like()
+        y.data.zero_()  # padding slots are never written: a known value under the checksum
+        kw = dict(n_pts=n_src, n_lev=L, x_pitch=x.pitch, y_pitch=y.pitch, layout=COLUMNS)
+        stack_bytes = n_src * L * B
+        aff, cp = (native.OP_AFFINE, 0, 1.0, -273.15), (native.OP_COPY, 0, 0.0, 0.0)
+        pm = (torch.rand(n_src + 8, device=dev, generator=torch.Generator(device=dev).manual_seed(1)) < 0.3).to(torch.uint8)
+
+        def row(name, stages, src, alg_bytes, note="", mask=None):
+            prog = native.level_program(stages, dev)
+            fn = lambda: native.pointwise_stack(src.data, y.data, prog=prog, n_stage=len(stages), point_mask=mask, **kw)  # noqa: E731
+            if src is y:
+                y.data.copy_(x.data)
+            record(name, timeit(fn), alg_bytes, note)
+            if src is y:  # the timed calls compounded: the digest is of one call
+                y.data.copy_(x.data)
+                fn()
+            res[name]["digest"] = checksum(y.data)
+
+        row(f"pointwise affine {tag} out-of-place", [[aff] * L], x, 2 * stack_bytes)
+        row(f"pointwise affine {tag} in-place", [[aff] * L], y, 2 * stack_bytes)
+        row(f"pointwise 2 stages, uniform over the levels {tag} out-of-place", [[(native.OP_MUL, 0, 9.80665, 0.0)] * L, [aff] * L], x, 2 * stack_bytes,
+            "operators by value")
+        row(f"pointwise affine, a different operator per level {tag} out-of-place", [[(native.OP_AFFINE, 0, 1.0 + 0.001 * l, -273.15) for l in range(L)]], x,
+            2 * stack_bytes, "per-level tables: LDS kernel (f32 out of place), typed no-loop kernel (f64)")
+        row(f"pointwise log then exp (sp_to_lnsp | lnsp_to_sp) {tag} out-of-place", [[(native.OP_LOG, 0, 0.0, 0.0)] * L, [(native.OP_EXP, 0, 0.0, 0.0)] * L], x,
+            2 * stack_bytes, "log and exp (the library's own routines in float64, atx_common.hpp) on every element")
+        row(f"apply_mask {tag}", [[(native.OP_COPY, 1, 0.0, 0.0)] * L], x, 2 * stack_bytes + n_src, mask=pm)
+        row(f"pointwise 1 of {L} levels selected {tag} in-place", [[(native.OP_AFFINE, 0, 2.0, 1.0)] + [cp] * (L - 1)], y, 2 * n_src * B,
+            "untouched levels are skipped; 16-B vector granularity")
+        minmax = lambda: native.reduce_stack(x.data, native.RED_MINMAX, n_pts=n_src, n_lev=L, pitch=x.pitch, layout=COLUMNS)  # noqa: E731
+        name = f"reduce min+max of the stack {tag} (one pass)"
+        record(name, timeit(minmax), stack_bytes, "the range check of cos_sin_from_rad; includes the device->host read (round 1: two passes of 0.79 ms)")
+        res[name]["digest"] = checksum(minmax())
+        del y
+        f = Stack.empty(n_src, L, tdt, dev, FIELDS)
+        native.relayout(x.data, f.data, n_pts=n_src, n_lev=L, src_pitch=x.pitch, dst_pitch=f.pitch, src_layout=COLUMNS, dst_layout=FIELDS)
+        g = f.new_like()
+        g.data.zero_()
+        pf = native.level_program([[(native.OP_AFFINE, 0, 1.0 + 0.001 * l, -273.15) for l in range(L)]], dev)
+        name = f"pointwise affine, a scale per field {tag} fields (the reference's array order)"
+        record(name, timeit(lambda: native.pointwise_stack(f.data, g.data, prog=pf, n_stage=1, n_pts=n_src, n_lev=L, x_pitch=f.pitch, y_pitch=g.pitch, layout=FIELDS)),
+               2 * stack_bytes, "one vector per lane, grid.y = field")
+        res[name]["digest"] = checksum(g.data)
+        first = f.data[0].contiguous()
+        mask = torch.zeros(n_src + 8, dtype=torch.uint8, device=dev)
+        name = f"mask_build {tag} (1 field)"
+        record(name, timeit(lambda: native.mask_build(first, mask, n=n_src, cmp=native.CMP_GT, threshold=280.0)), n_src * (B + 1))
+        res[name]["digest"] = checksum(mask)
+        name = f"reduce min {tag} (1 field)"
+        record(name, timeit(lambda: native.reduce(first, native.RED_MIN)), n_src * B, "includes the device->host read of the result")
+        res[name]["digest"] = checksum(native.reduce(first, native.RED_MIN))
+        if B == 8:  # once per table
+            m = (torch.rand(n_src, device=dev, generator=torch.Generator(device=dev).manual_seed(2)) < 0.7).to(torch.uint8)
+            name = "mask_to_index (6.6M points, 70% kept)"
+            record(name, timeit(lambda: native.mask_to_index(m, n_src)), 2 * n_src + 4 * int(m.sum().item()), "includes workspace allocation + count read-back")
+            res[name]["digest"] = checksum(native.mask_to_index(m, n_src))
+        del f, g
+        torch.cuda.empty_cache()
+
+    if args.only_pointwise:
+        for tdt, B, tag in ((torch.float32, 4, "f32"), (torch.float64, 8, "f64")):
+            pointwise_rows(tdt, B, tag)
+        if args.out:
+            json.dump(res, open(args.out, "w"), indent=1)
+        return
+
     if args.only_obs:
         obs_rows()
         if args.out:
@@ -271,28 +355,8 @@ def main():
         y = x.new_like()
         record(f"(ceiling) torch copy_ of the stack {tag}", timeit(lambda: y.data.copy_(x.data)), 2 * x.data.numel() * B,
                "device-to-device copy of the same bytes: the practical read+write streaming rate")
-        p1 = native.level_program([[(native.OP_AFFINE, 0, 1.0, -273.15)] * L], dev)
-        kw = dict(n_pts=n_src, n_lev=L, x_pitch=x.pitch, y_pitch=y.pitch, layout=COLUMNS)
         stack_bytes = n_src * L * B
-        record(f"pointwise affine {tag} out-of-place", timeit(lambda: native.pointwise_stack(x.data, y.data, prog=p1, n_stage=1, **kw)), 2 * stack_bytes)
-        record(f"pointwise affine {tag} in-place", timeit(lambda: native.pointwise_stack(y.data, y.data, prog=p1, n_stage=1, **kw)), 2 * stack_bytes)
-        p2 = native.level_program([[(native.OP_MUL, 0, 9.80665, 0.0)] * L, [(native.OP_AFFINE, 0, 1.0, -273.15)] * L], dev)
-        record(f"pointwise 2 stages, uniform over the levels {tag} out-of-place", timeit(lambda: native.pointwise_stack(x.data, y.data, prog=p2, n_stage=2, **kw)), 2 * stack_bytes,
-               "operators by value")
-        pl = native.level_program([[(native.OP_AFFINE, 0, 1.0 + 0.001 * l, -273.15) for l in range(L)]], dev)
-        record(f"pointwise affine, a different operator per level {tag} out-of-place", timeit(lambda: native.pointwise_stack(x.data, y.data, prog=pl, n_stage=1, **kw)), 2 * stack_bytes,
-               "per-level tables: LDS kernel (f32 out of place), typed no-loop kernel (f64)")
-        pe = native.level_program([[(native.OP_LOG, 0, 0.0, 0.0)] * L, [(native.OP_EXP, 0, 0.0, 0.0)] * L], dev)
-        record(f"pointwise log then exp (sp_to_lnsp | lnsp_to_sp) {tag} out-of-place", timeit(lambda: native.pointwise_stack(x.data, y.data, prog=pe, n_stage=2, **kw)), 2 * stack_bytes,
-               "log and exp (the library's own routines in float64, atx_common.hpp) on every element")
-        pm = (torch.rand(n_src + 8, device=dev) < 0.3).to(torch.uint8)
-        pmask = native.level_program([[(native.OP_COPY, 1, 0.0, 0.0)] * L], dev)
-        record(f"apply_mask {tag}", timeit(lambda: native.pointwise_stack(x.data, y.data, prog=pmask, n_stage=1, point_mask=pm, **kw)), 2 * stack_bytes + n_src)
-        one = native.level_program([[(native.OP_AFFINE, 0, 2.0, 1.0)] + [(native.OP_COPY, 0, 0.0, 0.0)] * (L - 1)], dev)
-        record(f"pointwise 1 of {L} levels selected {tag} in-place", timeit(lambda: native.pointwise_stack(y.data, y.data, prog=one, n_stage=1, **kw)),
-               2 * n_src * B, "untouched levels are skipped; 16-B vector granularity")
-        record(f"reduce min+max of the stack {tag} (one pass)", timeit(lambda: native.reduce_stack(x.data, native.RED_MINMAX, n_pts=n_src, n_lev=L, pitch=x.pitch, layout=COLUMNS)),
-               stack_bytes, "the range check of cos_sin_from_rad; includes the device->host read (round 1: two passes of 0.79 ms)")
+        pointwise_rows(tdt, B, tag, x)
         # ---- multi-input
         z = x.new_like()
         # snow depth (m of water equivalent) and density as they occur — in REGIONS, as on a real field (points are stored by
@@ -363,24 +427,9 @@ def main():
                dst_pitch=one_lev.pitch, layout=COLUMNS)), 2 * n_src * B, "one field out of a column stack: a 64-byte sector per point is the least that can move")
         del half, one_lev
         # ---- regrid on field-major
-        pf = native.level_program([[(native.OP_AFFINE, 0, 1.0 + 0.001 * l, -273.15) for l in range(L)]], dev)
-        g = f.new_like()
-        kwf = dict(n_pts=n_src, n_lev=L, x_pitch=f.pitch, y_pitch=g.pitch, layout=FIELDS)
-        record(f"pointwise affine, a scale per field {tag} fields (the reference's array order)",
-               timeit(lambda: native.pointwise_stack(f.data, g.data, prog=pf, n_stage=1, **kwf)), 2 * stack_bytes, "one vector per lane, grid.y = field")
-        del g
         record(f"regrid_ell k=4 {tag} fields", timeit(lambda: plan4.apply(f)), bench.algorithmic_bytes(L, B, U4, n_tgt, 4))
-        # ---- masks / reductions on one field
-        first = f.data[0].contiguous()
-        mask = torch.empty(n_src + 8, dtype=torch.uint8, device=dev)
-        record(f"mask_build {tag} (1 field)", timeit(lambda: native.mask_build(first, mask, n=n_src, cmp=native.CMP_GT, threshold=280.0)), n_src * (B + 1))
-        record(f"reduce min {tag} (1 field)", timeit(lambda: native.reduce(first, native.RED_MIN)), n_src * B, "includes the device->host read of the result")
         del x, y, z, f
         torch.cuda.empty_cache()
-
-    m = (torch.rand(n_src, device=dev) < 0.7).to(torch.uint8)
-    cnt = int(m.sum().item())
-    record("mask_to_index (6.6M points, 70% kept)", timeit(lambda: native.mask_to_index(m, n_src)), 2 * n_src + 4 * cnt, "includes workspace allocation + count read-back")
 
     # ---- k-NN precompute
     sxyz = torch.from_numpy(np.ascontiguousarray(interp.unit_sphere_xyz(src_grid["latitudes"], src_grid["longitudes"]))).to(dev)
