@@ -1,7 +1,8 @@
-"""irregular_to_grid / assign_to_grid: where a table of observations enters the field path (R: filters/tabular/).
+"""superob / assign_to_grid / irregular_to_grid: where a table of observations enters the field path (R: filters/tabular/).
 
-``assign_to_grid`` adds the nearest grid point of every observation to the table; ``irregular_to_grid`` turns the table into one
-gridded field per target time and column, NaN where nothing was observed.  The fields it returns are levels of ONE stack in
+``superob`` thins a raw table to one row per grid cell, time slot and report type (per-group means by pandas' rule:
+``obs.group_means`` -> ``atx_obs_group_mean``); ``assign_to_grid`` adds the nearest grid point of every observation to the table;
+``irregular_to_grid`` turns the table into one gridded field per target time and column, NaN where nothing was observed.  The fields it returns are levels of ONE stack in
 HBM (``obs.grid_observations``: ``atx_obs_best_per_cell`` + ``atx_obs_fill_stack``), so a following ``regrid`` or per-point
 filter finds them resident.
 
@@ -14,6 +15,7 @@ Deviations from the reference, each said once when it first matters (``core.say_
     are dropped, as ``groupby`` drops them.
   * value columns must be numeric: they are read as float64, as the reference's float64 grids read them.
   * ``"h<nside>"`` grids need healpy and raise ``NotImplementedError``.
+  * ``superob``: the caller's table is not modified, and rows of equal ``date`` keep the first-appearance order of their groups.
 The other tabular filters of the reference (pandas bookkeeping with no field output) are not built: DESIGN.md §7.
 """
 
@@ -209,5 +211,240 @@ class AssignToGrid(Filter):
         return {**table, **added}
 
 
+class SuperOb(Filter):
+    """One row per grid cell, time slot and report type (R: filters/tabular/superob.py:21-97, support/superob.py:43-69).
+
+    Rows without ``date``, ``latitude`` or ``longitude`` are dropped.  Every remaining row gets ``spatial_index`` and ``distance``
+    (its nearest point of ``grid`` in the plane of (latitude, longitude) degrees, as ``assign_to_grid``), a time slot
+    ``(date - min(date)) // timeslot_length`` and ``grid_index = spatial_index + n_grid * slot``.  The rows are grouped by
+    ``(grid_index, *columns_to_groupby)``, groups in order of first appearance, rows with a missing key entry dropped.  Per group,
+    every column that is neither a key nor in ``columns_to_take_nearest`` gets its MEAN BY PANDAS' RULE — one Kahan sum in the row
+    order of the table, missing values skipped (``obs.group_means`` -> ``atx_obs_group_mean``; bit-equal to
+    ``groupby(sort=False).mean()``, float64 out, ``date`` stays a datetime) — and every column in ``columns_to_take_nearest`` the value of the
+    row of smallest ``distance``, the first such row among equals (``atx_obs_group_argmin``).  ``grid_index`` and ``distance`` are
+    dropped; columns come as ``columns_to_groupby``, the averaged columns in table order, ``columns_to_take_nearest``; rows are
+    sorted by ``date``.
+
+    ``grid="native"`` and an empty table are returned as given.  The result is the kind of table that came in: a DataFrame for a
+    DataFrame; for a mapping a dict of device tensors (dates as int64 nanoseconds) if any input column was a device tensor,
+    else of numpy arrays — so ``superob | irregular_to_grid`` can keep a table resident from raw rows to the stack.
+
+    Deviations: rows are taken by position (index labels are not consulted); the caller's DataFrame is NOT modified (the
+    reference's ``dropna(inplace=True)`` modifies it); rows of equal ``date`` keep the first-appearance order of their groups (a
+    stable sort; pandas' default quicksort leaves them in an order that depends on numpy's build); ``"h<nside>"`` grids need healpy
+    and raise ``NotImplementedError``.
+    """
+
+    def __init__(self, *, grid: str, timeslot_length: int, columns_to_take_nearest: list[str] | None = None,
+                 columns_to_groupby: list[str] | None = None) -> None:
+        if not isinstance(grid, str) or not grid:
+            raise ValueError("No grid specified.")
+        seconds = timeslot_length
+        if isinstance(seconds, bool) or not isinstance(seconds, (int, float, np.integer, np.floating)) or seconds != seconds \
+                or seconds <= 0 or seconds != int(seconds):
+            raise ValueError(f"timeslot_length must be a positive whole number of seconds, got {timeslot_length!r}")
+        self.grid = grid
+        self.timeslot_length = int(seconds)
+        self.columns_to_take_nearest = list(columns_to_take_nearest) if columns_to_take_nearest else []
+        self.columns_to_groupby = list(columns_to_groupby) if columns_to_groupby else []
+        both = set(self.columns_to_take_nearest) & (set(self.columns_to_groupby) | {"grid_index"})
+        if both:
+            raise ValueError(f"columns both grouped by and taken from the nearest row: {sorted(both)}")
+        say_once(LOG, (type(self), "deviations"), "superob: rows are taken by position (index labels are not consulted), the caller's "
+                 "table is not modified, and rows of equal date keep the first-appearance order of their groups (a stable sort)",
+                 level=logging.INFO)
+
+    def __repr__(self) -> str:
+        return f"SuperOb(grid={self.grid!r}, timeslot_length={self.timeslot_length})"
+
+    @staticmethod
+    def _define_grid(grid: str) -> tuple[np.ndarray, np.ndarray]:
+        """R: support/superob.py:19-25 — static and patchable, as ``IrregularToGrid._define_grid``."""
+        return _named_grid(grid)
+
+    def forward(self, table: Any) -> Any:
+        names = _column_names(table)
+        n_rows = len(table) if _is_dataframe(table) else (len(table[names[0]]) if names else 0)
+        if self.grid == "native" or n_rows == 0:
+            return table
+        grid_lat, grid_lon = self._define_grid(self.grid)
+        _require(table, ["date", "latitude", "longitude"] + self.columns_to_groupby + self.columns_to_take_nearest)
+        if _is_dataframe(table) and not table.index.is_unique:
+            say_once(LOG, (type(self), "position"), "superob: the table's index has duplicate labels; rows are taken by position "
+                     "here, the reference would repeat the rows of a duplicated label")
+        return _superob(self, _Table(table), grid_lat, grid_lon)
+
+
+class _Table:
+    """The columns of a DataFrame or mapping by name, with what ``SuperOb`` needs of them: positional row selection that keeps
+    the column's kind, and a float64 device view for the columns that are averaged."""
+
+    def __init__(self, table: Any) -> None:
+        self.frame = _is_dataframe(table)
+        self.columns = {c: table[c] for c in _column_names(table)}
+        self.resident = any(isinstance(v, torch.Tensor) for v in self.columns.values())
+        self.device = next((v.device for v in self.columns.values() if isinstance(v, torch.Tensor) and v.is_cuda), None)
+
+    def __len__(self) -> int:
+        return len(next(iter(self.columns.values())))
+
+    def take(self, rows: np.ndarray | torch.Tensor) -> "_Table":
+        """The rows at the positions ``rows`` (host array or device tensor, whichever the column is)."""
+        host, dev = (rows.cpu().numpy(), rows) if isinstance(rows, torch.Tensor) else (rows, None)
+        out = {}
+        for name, col in self.columns.items():
+            if isinstance(col, torch.Tensor):
+                index = torch.from_numpy(host) if dev is None else dev
+                out[name] = col.reshape(-1)[index.to(col.device)]
+            elif hasattr(col, "iloc"):
+                out[name] = col.iloc[host]
+            else:
+                out[name] = np.asarray(col)[host]
+        taken = _Table.__new__(_Table)
+        taken.frame, taken.columns, taken.resident, taken.device = self.frame, out, self.resident, self.device
+        return taken
+
+    def is_datetime(self, name: str) -> bool:
+        col = self.columns[name]
+        if isinstance(col, torch.Tensor):
+            return name == "date"  # obs.to_ns: an int64 tensor in the date column IS nanoseconds
+        return getattr(obs._host_array(col).dtype, "kind", "") == "M"
+
+    def missing(self, name: str, dev: torch.device) -> torch.Tensor:
+        """Where the column has no value (NaN / NaT), on the device."""
+        col = self.columns[name]
+        if self.is_datetime(name):
+            return obs._device(obs.to_ns(col), dev) == obs.NAT
+        if isinstance(col, torch.Tensor):
+            return torch.isnan(col.reshape(-1)).to(dev) if col.dtype.is_floating_point else torch.zeros(col.numel(), dtype=torch.bool, device=dev)
+        a = obs._host_array(col)
+        if a.dtype.kind == "f":
+            return obs._device(np.isnan(a), dev)
+        if a.dtype.kind in "iub":
+            return torch.zeros(a.size, dtype=torch.bool, device=dev)
+        return obs._device(np.array([v is None or v != v for v in a.tolist()], dtype=bool), dev)
+
+    def as_float64(self, name: str, out: torch.Tensor) -> None:
+        """The column as float64 into the device row ``out``: integers and bools converted, datetimes as ``(double)`` of their int64
+        nanoseconds with NaT as NaN — what pandas hands to its group mean.  Anything else cannot be averaged: ``TypeError``."""
+        col = self.columns[name]
+        if self.is_datetime(name):
+            ns = obs._device(obs.to_ns(col), out.device)
+            out.copy_(ns)
+            out.masked_fill_(ns == obs.NAT, float("nan"))
+            return
+        if not isinstance(col, torch.Tensor):
+            a = obs._host_array(col)
+            if a.dtype.kind not in "iubf":
+                raise TypeError(f"superob: column {name!r} of dtype {a.dtype} cannot be averaged; name it in columns_to_groupby or "
+                                "columns_to_take_nearest, or drop it first")
+            col = torch.from_numpy(np.ascontiguousarray(a.reshape(-1)))
+        elif col.dtype.is_complex:
+            raise TypeError(f"superob: column {name!r} of dtype {col.dtype} cannot be averaged")
+        out.copy_(col.reshape(-1))
+
+
+def _superob(f: SuperOb, table: _Table, grid_lat: np.ndarray, grid_lon: np.ndarray) -> Any:
+    from .. import stack as _stack
+
+    dev = table.device or _stack.device()
+    # R: superob.py:72 — rows without date / latitude / longitude leave (here: a copy of the rest, the caller's table stays)
+    gone = table.missing("date", dev) | table.missing("latitude", dev) | table.missing("longitude", dev)
+    if bool(gone.any()):
+        table = table.take(torch.nonzero(~gone).reshape(-1))
+    n = len(table)
+    if n == 0:
+        return _superob_result(table, {c: v for c, v in table.columns.items()}, None)
+    # R: support/superob.py:43-69
+    lat, lon = (c.cpu().numpy() if isinstance(c, torch.Tensor) else obs._host_array(c) for c in (table.columns["latitude"], table.columns["longitude"]))
+    distance, spatial = obs.nearest_grid_index(grid_lat, grid_lon, lat, lon)
+    distance, spatial = obs._device(np.asarray(distance, dtype=np.float64), dev), obs._device(np.asarray(spatial, dtype=np.int64), dev)
+    date = obs._device(obs.to_ns(table.columns["date"]), dev)
+    slot = (date - date.min()) // (f.timeslot_length * 10**9)
+    added = {"grid_index": spatial + len(grid_lat) * slot, "spatial_index": spatial, "distance": distance}
+    columns = dict(table.columns)
+    columns.update(added)  # DataFrame.assign: an existing column keeps its place, a new one goes to the end
+    table.columns = columns
+    key_names = ["grid_index"] + f.columns_to_groupby
+    averaged = [c for c in columns if c not in set(key_names) | set(f.columns_to_take_nearest)]
+    # R: superob.py:86-88
+    keys, valid = [], None
+    for name in key_names:
+        codes, ok = obs.key_codes(columns[name])
+        keys.append(codes)
+        if ok is not None:
+            ok = obs._device(ok, dev)
+            valid = ok if valid is None else valid & ok
+    groups = obs.superob_groups(keys, valid, dev)
+    values = torch.empty((len(averaged), n), dtype=torch.float64, device=dev)
+    for j, name in enumerate(averaged):
+        table.as_float64(name, values[j])
+    mean, _ = obs.group_means(values, groups)
+    nearest = obs.group_nearest(distance, groups)
+    # R: superob.py:94-96 — groups in order of first appearance, then a stable sort by date (NaT last)
+    out_names = f.columns_to_groupby + [c for c in averaged if c != "distance"] + f.columns_to_take_nearest
+    mean_of = {name: mean[j] for j, name in enumerate(averaged)}
+
+    def as_ns(m: torch.Tensor) -> torch.Tensor:
+        # pandas: the float64 quotient truncated back to int64, NaT where nothing was summed
+        return torch.where(torch.isnan(m), torch.zeros_like(m), m).to(torch.int64).masked_fill_(torch.isnan(m), obs.NAT)
+
+    when = as_ns(mean_of["date"]) if "date" in mean_of else date[groups.first if "date" in key_names else nearest]
+    when = when[groups.appearance]
+    by_date = torch.argsort(torch.where(when == obs.NAT, torch.full_like(when, torch.iinfo(torch.int64).max), when), stable=True)
+    final = groups.appearance[by_date]
+    result = {}
+    for name in out_names:
+        if name in mean_of:
+            m = mean_of[name][final]
+            result[name] = as_ns(m) if table.is_datetime(name) else m
+        else:
+            result[name] = (groups.first if name in key_names else nearest)[final]  # a row index: the value is taken below
+    return _superob_result(table, result, by_date, set(mean_of))
+
+
+def _superob_result(table: _Table, result: dict[str, Any], labels: torch.Tensor | None, computed: set[str] = frozenset()) -> Any:
+    """The output table in the kind of the input.  ``result[name]`` is a device column of values for ``computed`` names and a
+    device column of ROW POSITIONS of ``table`` for the others; ``labels``: the index a DataFrame gets (pandas keeps the group
+    numbers through ``sort_values``).  ``labels is None``: ``result`` already holds the (empty) columns."""
+    if labels is None:
+        if table.frame:
+            import pandas as pd
+
+            return pd.DataFrame(result)
+        return dict(result)
+    host_rows: dict[int, np.ndarray] = {}
+
+    def rows_on_host(rows: torch.Tensor) -> np.ndarray:
+        return host_rows.setdefault(id(rows), rows.cpu().numpy())
+
+    out = {}
+    for name, col in result.items():
+        source = table.columns.get(name)
+        if name in computed:
+            if table.frame or not table.resident:
+                col = col.cpu().numpy()
+                col = col.view("datetime64[ns]") if table.is_datetime(name) else col
+        elif isinstance(source, torch.Tensor):
+            col = source.reshape(-1)[col.to(source.device)]
+            col = col if table.resident and not table.frame else col.cpu().numpy()
+        elif hasattr(source, "iloc"):
+            col = source.iloc[rows_on_host(col)]
+            col = col.reset_index(drop=True) if table.frame else col.to_numpy()
+        else:
+            col = np.asarray(source)[rows_on_host(col)]
+        if table.resident and not table.frame and isinstance(col, np.ndarray) and col.dtype.kind in "iubfM":
+            col = obs._device(obs.to_ns(col) if col.dtype.kind == "M" else col, table.device or result[name].device)
+        out[name] = col
+    if table.frame:
+        import pandas as pd
+
+        frame = pd.DataFrame(out)
+        frame.index = labels.cpu().numpy()
+        return frame
+    return out
+
+
 filter_registry.register("irregular_to_grid", IrregularToGrid)
 filter_registry.register("assign_to_grid", AssignToGrid)
+filter_registry.register("superob", SuperOb)

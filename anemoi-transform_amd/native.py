@@ -109,6 +109,10 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
          c_double, c_void_p, c_void_p, c_void_p],
     ),
     "atx_obs_fill_stack": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int64, c_int32, c_int64, c_void_p, c_int64, c_int, c_void_p]),
+    "atx_obs_group_mean": (
+        c_int, [c_void_p, c_int64, c_int32, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p],
+    ),
+    "atx_obs_group_argmin": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
     "atx_mask_build": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_double, c_int, c_void_p]),
     "atx_mask_count": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
     "atx_mask_to_index_workspace": (c_size_t, [c_int64]),
@@ -466,6 +470,35 @@ def obs_fill_stack(winner, values, out, *, n_time: int, n_cells: int, pitch: int
     assert out.numel() == 0 or out.stride(0) == pitch
     val_pitch = values.stride(0) if n_cols > 1 else max(n_obs, 1)
     _call("atx_obs_fill_stack", _ptr(winner), _ptr(values), n_obs, n_cols, val_pitch, n_time, n_cells, _ptr(out), pitch, layout, _stream())
+
+
+def _group_order_args(order, offsets) -> tuple[int, int]:
+    assert order.dtype == torch.int32 and order.is_contiguous() and offsets.dtype == torch.int64 and offsets.is_contiguous()
+    assert offsets.numel() >= 1
+    return order.numel(), offsets.numel() - 1
+
+
+def obs_group_mean(values, order, offsets, mean, count) -> None:
+    """``mean[c, g]`` / ``count[c, g]``: pandas' group mean (one Kahan sum in row order, NaN skipped) of column ``c`` of ``values``
+    (float64 ``[n_cols, n_obs]``, rows may be pitched) over the rows ``order[offsets[g]:offsets[g + 1]]`` — ``atx_obs_group_mean``.
+    ``order``: int32 row indices in group order (a stable sort by group); ``offsets``: int64 ``[n_groups + 1]``; ``mean`` float64 and
+    ``count`` int64: contiguous ``[n_cols, n_groups]``."""
+    n_cols, n_obs = values.shape
+    n_sel, n_groups = _group_order_args(order, offsets)
+    assert values.dtype == mean.dtype == torch.float64 and count.dtype == torch.int64 and (values.stride(1) == 1 or n_obs <= 1)
+    assert mean.is_contiguous() and count.is_contiguous() and tuple(mean.shape) == tuple(count.shape) == (n_cols, n_groups)
+    val_pitch = values.stride(0) if n_cols > 1 else max(n_obs, 1)
+    _call("atx_obs_group_mean", _ptr(values), n_obs, n_cols, val_pitch, _ptr(order), n_sel, _ptr(offsets), n_groups, _ptr(mean), _ptr(count),
+          max(n_groups, 1), _stream())
+
+
+def obs_group_argmin(distance, order, offsets, nearest) -> None:
+    """``nearest[g]`` (int32): the first row of smallest ``distance`` (float64 ``[n_obs]``) among ``order[offsets[g]:offsets[g + 1]]`` —
+    ``atx_obs_group_argmin``."""
+    n_sel, n_groups = _group_order_args(order, offsets)
+    assert distance.dtype == torch.float64 and distance.is_contiguous() and nearest.dtype == torch.int32 and nearest.is_contiguous()
+    assert nearest.numel() == n_groups
+    _call("atx_obs_group_argmin", _ptr(distance), distance.numel(), _ptr(order), n_sel, _ptr(offsets), n_groups, _ptr(nearest), _stream())
 
 
 def mask_build(m, mask, *, n, stride=1, cmp, threshold=0.0) -> None:

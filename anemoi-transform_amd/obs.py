@@ -10,6 +10,11 @@ What this module restates on the host is the bookkeeping around those two launch
 ``anemoi.utils.window.Window`` (``parse_window``), ``pd.Timedelta(time_freq)`` (``parse_frequency``), datetimes as int64
 nanoseconds (``to_ns``), ``spatial_index`` as int64 cells (``to_cells``) and the targets in order of first appearance
 (``unique_in_order``).  Arrays may be numpy arrays (uploaded) or device tensors (used in place).
+
+The second half serves ``superob`` (R: filters/tabular/superob.py), which thins a raw table before it is gridded: ``key_codes`` and
+``superob_groups`` turn key columns into rows in group order (torch on the device: one stable sort), ``group_means`` is pandas'
+``groupby().mean()`` bit for bit (``atx_obs_group_mean``: one Kahan sum per group and column in row order) and ``group_nearest`` its
+``groupby()["distance"].idxmin()`` (``atx_obs_group_argmin``).
 """
 
 from __future__ import annotations
@@ -245,3 +250,128 @@ def nearest_grid_index(grid_lat: np.ndarray, grid_lon: np.ndarray, lat: Any, lon
         raise ValueError("latitudes / longitudes beyond +-512 degrees")
     indices, d2, _ = device_knn(grid, points, 1)
     return np.sqrt(d2[:, 0]) * 512.0, indices[:, 0]
+
+
+# ---- superob: rows -> groups -> pandas' group means (R: filters/tabular/superob.py:78-96) --------------------------------------
+class Groups(NamedTuple):
+    """The rows of a table in group order.  Group ``g`` (numbered by ascending key, NOT by appearance) holds the rows
+    ``order[offsets[g]:offsets[g + 1]]``, ascending; ``first[g]`` is its first row and ``appearance`` lists the groups in the
+    order in which their first rows appear in the table — pandas' ``groupby(sort=False)`` order."""
+
+    order: torch.Tensor  # int32 [n_sel]
+    offsets: torch.Tensor  # int64 [n_groups + 1]
+    first: torch.Tensor  # int64 [n_groups]
+    appearance: torch.Tensor  # int64 [n_groups]
+
+    @property
+    def n_groups(self) -> int:
+        return self.first.numel()
+
+
+_KEY_LIMIT = 2**62
+
+
+def key_codes(column: Any) -> tuple[np.ndarray | torch.Tensor, np.ndarray | torch.Tensor | None]:
+    """A key column as ``(int64 codes, valid)``: equal entries get equal codes, ``valid`` (None: every row) is false where the
+    entry is missing (NaN, NaT, None) — ``groupby`` drops those rows.  Integer, bool and datetime columns and float columns of
+    whole numbers are their own codes; anything else (strings, categoricals, other floats) is numbered on the host first."""
+    if isinstance(column, torch.Tensor):
+        c = column.reshape(-1)
+        if not c.dtype.is_floating_point:
+            return c.to(torch.int64), None
+        ok = ~torch.isnan(c)
+        whole = torch.isfinite(c) & (c.abs() < 2.0**62) & (c == torch.floor(c))
+        if bool((whole | ~ok).all()):
+            return torch.where(ok, c, torch.zeros_like(c)).to(torch.int64), ok
+        codes = torch.zeros(c.numel(), dtype=torch.int64, device=c.device)
+        codes[ok] = torch.unique(c[ok], return_inverse=True)[1]
+        return codes, ok
+    a = _host_array(column).reshape(-1)
+    if a.dtype.kind in "iub":
+        return np.ascontiguousarray(a, dtype=np.int64), None
+    if a.dtype.kind == "M":
+        ns = to_ns(a)
+        return ns, ns != NAT
+    if a.dtype.kind == "f":
+        a = a.astype(np.float64)
+        ok = ~np.isnan(a)
+        if np.all((np.isfinite(a) & (np.abs(a) < 2.0**62) & (a == np.floor(a))) | ~ok):
+            return np.where(ok, a, 0.0).astype(np.int64), ok
+        codes = np.zeros(a.size, dtype=np.int64)
+        codes[ok] = np.unique(a[ok], return_inverse=True)[1]
+        return codes, ok
+    try:
+        import pandas as pd
+
+        codes = pd.factorize(column if hasattr(column, "dtype") and not isinstance(column, np.ndarray) else a)[0].astype(np.int64)
+    except ImportError:
+        seen: dict[Any, int] = {}
+        codes = np.array([-1 if (v is None or v != v) else seen.setdefault(v, len(seen)) for v in a.tolist()], dtype=np.int64)
+    return np.where(codes >= 0, codes, 0), codes >= 0
+
+
+def superob_groups(keys: Sequence[Any], valid: Any = None, dev: torch.device | None = None) -> Groups:
+    """The rows of a table grouped by the tuple of ``keys`` (int64 code columns, see ``key_codes``; numpy arrays are uploaded,
+    device tensors used in place), rows where ``valid`` is false left out.  The bookkeeping is torch on the device: the key columns
+    are folded into ONE int64 key, a STABLE sort of the kept rows by that key gives ``order``, the places where the sorted key
+    changes give ``offsets``, and — the sort being stable — the first row of every segment is the group's first appearance."""
+    dev = _stack.device() if dev is None else dev
+    keys = [_device(k, dev).reshape(-1).to(torch.int64) for k in keys]
+    if not keys:
+        raise ValueError("at least one key column")
+    n = keys[0].numel()
+    if any(k.numel() != n for k in keys):
+        raise ValueError(f"key columns differ in length: {[k.numel() for k in keys]}")
+    if n >= 2**31:
+        raise ValueError(f"{n} rows do not fit an int32 row index")
+    rows = None
+    if valid is not None:
+        valid = _device(valid, dev).reshape(-1).to(torch.bool)
+        if not bool(valid.all()):
+            rows = torch.nonzero(valid).reshape(-1)
+            keys = [k[rows] for k in keys]
+    n_sel = keys[0].numel()
+    if n_sel == 0:
+        empty = torch.zeros(0, dtype=torch.int64, device=dev)
+        return Groups(empty.to(torch.int32), torch.zeros(1, dtype=torch.int64, device=dev), empty, empty)
+    key, span = None, 1
+    for k in keys:
+        lo, hi = int(k.min()), int(k.max())
+        width = hi - lo + 1
+        if key is None:
+            key, span = k - lo, width
+            continue
+        if width >= _KEY_LIMIT or span * width >= _KEY_LIMIT:  # number both sides densely first (a sort each), then fold
+            uk, key = torch.unique(key, return_inverse=True)
+            uc, k = torch.unique(k, return_inverse=True)
+            span, width, lo = uk.numel(), uc.numel(), 0
+        key = key * width + (k - lo)
+        span *= width
+    sorted_key, perm = torch.sort(key, stable=True)
+    change = torch.ones(n_sel, dtype=torch.bool, device=dev)
+    change[1:] = sorted_key[1:] != sorted_key[:-1]
+    starts = torch.nonzero(change).reshape(-1)
+    offsets = torch.cat([starts, torch.tensor([n_sel], dtype=torch.int64, device=dev)])
+    order = perm if rows is None else rows[perm]
+    first = order[starts]
+    return Groups(order.to(torch.int32).contiguous(), offsets.contiguous(), first, torch.argsort(first))
+
+
+def group_means(values: torch.Tensor, groups: Groups) -> tuple[torch.Tensor, torch.Tensor]:
+    """``(mean, count)``, float64 / int64 ``[n_cols, n_groups]`` in ``groups``' own numbering: pandas' ``groupby().mean()`` of the
+    float64 device columns ``values`` (``[n_cols, n_obs]``) bit for bit — ``atx_obs_group_mean``."""
+    n_cols = values.shape[0]
+    mean = torch.empty((n_cols, groups.n_groups), dtype=torch.float64, device=values.device)
+    count = torch.empty((n_cols, groups.n_groups), dtype=torch.int64, device=values.device)
+    if n_cols and groups.n_groups:
+        native.obs_group_mean(values, groups.order, groups.offsets, mean, count)
+    return mean, count
+
+
+def group_nearest(distance: torch.Tensor, groups: Groups) -> torch.Tensor:
+    """Per group the first row of smallest ``distance`` (pandas ``groupby()["distance"].idxmin()`` on a table in row order), int64
+    ``[n_groups]`` in ``groups``' own numbering — ``atx_obs_group_argmin``."""
+    nearest = torch.empty(groups.n_groups, dtype=torch.int32, device=distance.device)
+    if groups.n_groups:
+        native.obs_group_argmin(distance.contiguous(), groups.order, groups.offsets, nearest)
+    return nearest.to(torch.int64)

@@ -68,7 +68,8 @@
 extern "C" {
 #endif
 
-#define ATX_VERSION 420 /* 0.4.2 — additions only, so the number stays: atx_obs_best_per_cell / atx_obs_fill_stack (observation tables
+#define ATX_VERSION 420 /* 0.4.2 — additions only, so the number stays: atx_obs_group_mean / atx_obs_group_argmin (superob: per-group
+                           * means by pandas' row-order Kahan rule and the nearest row of every group); atx_obs_best_per_cell / atx_obs_fill_stack (observation tables
                            * onto a grid: a keyed arg-min and the gather that fills the stack); atx_rotate_vectors_stack (vector components between projection
                            * frames, a per-point table shared by every level) with its atx_frame enum; atx_pressure_at_height_stack (the
                            * first vertical reduction, one value per model column) and two multi-input operators, ATX_COMB_Q_TO_D /
@@ -400,6 +401,33 @@ ATX_API int atx_obs_best_per_cell(const int64_t* date_ns, const int64_t* cell, c
  *   R: filters/tabular/irregular_to_grid.py:135 (grids of NaN), :190-207 (_fill_grids), :163-188 (fields time-major, then column) */
 ATX_API int atx_obs_fill_stack(const int32_t* winner, const double* values, int64_t n_obs, int32_t n_cols, int64_t val_pitch,
                                int32_t n_time, int64_t n_cells, double* out, int64_t pitch, int layout, void* stream);
+
+/* ---- observation thinning (superob) ------------------------------------------ */
+/* mean[c * out_pitch + g], count[c * out_pitch + g] = pandas' group mean of column c over the rows of group g, and the number of
+ * rows that took part.  The rows of group g are order[offsets[g] .. offsets[g + 1]), ascending within the group (a STABLE sort
+ * of the rows by group): the sum is taken in that order, one Kahan chain per group and column,
+ *   y = v - comp;  t = sum + y;  comp = (t - sum) - y;  if comp is NaN, comp = 0;  sum = t;        mean = sum / count
+ * with NaN values skipped (pandas/_libs/groupby.pyx group_mean; no contraction).  A group and column without a non-NaN row
+ * gives NaN and count 0.  The chain is never split or reordered, so the result equals `df.groupby(keys)[cols].mean()` bit for
+ * bit and does not depend on the launch shape; no atomics.  Integer and datetime columns go in converted to double (NaT as NaN).
+ *   values   device double, n_cols columns of n_obs, column c at values + c * val_pitch
+ *   order    device int32 [n_sel]: row indices (n_sel <= n_obs: dropped rows are simply absent); entries outside [0, n_obs) are
+ *            skipped like NaN, never used as an address
+ *   offsets  device int64 [n_groups + 1], 0 = offsets[0] <= ... <= offsets[n_groups] = n_sel (the caller's contract; a group whose
+ *            bounds leave [0, n_sel] or run backwards gives NaN / 0)
+ *   mean     device double, count device int64: n_cols rows of n_groups, out_pitch elements apart
+ * n_obs >= 2^31 or n_cols outside 1 .. 65535: ATX_EINVAL.  val_pitch < n_obs, out_pitch < n_groups, n_sel > n_obs or
+ * n_groups > n_sel: ATX_ESHAPE.
+ *   R: filters/tabular/superob.py:86 `df.groupby(groupby_cols, observed=True, sort=False)[columns_to_average].mean()` */
+ATX_API int atx_obs_group_mean(const double* values, int64_t n_obs, int32_t n_cols, int64_t val_pitch, const int32_t* order, int64_t n_sel,
+                               const int64_t* offsets, int64_t n_groups, double* mean, int64_t* count, int64_t out_pitch, void* stream);
+
+/* nearest[g] = the row of group g with the smallest distance, the FIRST such row in the group's order among equals (pandas
+ * idxmin on a table in row order); a NaN distance is chosen only when the group has nothing else (then: its first row); -1 for
+ * a group with bad bounds.  order / offsets as for atx_obs_group_mean.
+ *   R: filters/tabular/superob.py:88 `df.groupby(groupby_cols, observed=True, sort=False)["distance"].idxmin()` */
+ATX_API int atx_obs_group_argmin(const double* distance, int64_t n_obs, const int32_t* order, int64_t n_sel, const int64_t* offsets,
+                                 int64_t n_groups, int32_t* nearest, void* stream);
 
 /* ---- masks ------------------------------------------------------------------ */
 

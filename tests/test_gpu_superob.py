@@ -1,0 +1,242 @@
+"""superob on the device: ``atx_obs_group_mean`` + ``atx_obs_group_argmin`` (csrc/atx_superob.hip) through
+``create_filter_by_name("superob", ...)`` against the reference's own test cases, the golden frames recorded from the reference
+(tests/golden/superob.json) and the numpy restatement (tests/superob_restatement.py).  Equality everywhere: pandas' group mean is
+one Kahan sum in row order, and the kernel takes it in that order."""
+
+from __future__ import annotations
+
+import numpy as np
+import pytest
+import torch
+
+from anemoi_transform_amd import obs
+from anemoi_transform_amd.filters import create_filter_by_name
+from anemoi_transform_amd.grids import lookup
+
+import obs_gridding_restatement as G
+import superob_restatement as R
+
+pytestmark = pytest.mark.gpu
+
+GOLDEN = R.load_golden()
+CONFIG = dict(grid="o96", timeslot_length=3600, columns_to_take_nearest=["date"], columns_to_groupby=["reportype"])
+
+
+def _grid(name):
+    info = lookup(name)
+    return info["latitudes"], info["longitudes"]
+
+
+def _restated(table, config):
+    lat, lon = _grid(config["grid"])
+    return R.superob(table, lat, lon, config["timeslot_length"], config["columns_to_take_nearest"], config["columns_to_groupby"])
+
+
+def _bits(a):
+    a = np.asarray(a)
+    return a.astype("datetime64[ns]").view(np.int64) if a.dtype.kind == "M" else (a.view(np.int64) if a.dtype == np.float64 else a)
+
+
+def assert_same_columns(got: dict, want: dict, canonical: bool = False) -> None:
+    """Same names in the same order, same dtypes, same BITS (so NaN / NaT / inf / -0.0 count)."""
+    assert list(got) == list(want)
+    if canonical:
+        got, want = R.canonical(got), R.canonical(want)
+    for name in want:
+        g, w = np.asarray(got[name]), np.asarray(want[name])
+        assert g.dtype == w.dtype, f"{name}: {g.dtype} != {w.dtype}"
+        np.testing.assert_array_equal(_bits(g), _bits(w), err_msg=name)
+        if w.dtype.kind in "fM":
+            np.testing.assert_array_equal(g, w, err_msg=name)  # and as values: NaN = NaN, NaT = NaT
+
+
+# ---- the reference's own tests (R: tests/tabular_filters/test_superob.py) ---------------------------------------------------------
+def _reference_frame(pd, longitude, reportype):
+    return pd.DataFrame({
+        "date": [pd.Timestamp("2025-01-01 00:00:00"), pd.Timestamp("2025-01-01 00:00:01"), pd.Timestamp("2025-01-01 02:00:01"),
+                 pd.Timestamp("2025-01-01 02:00:02")],
+        "latitude": [89.1, 89.3, 89.2, 89.2],
+        "longitude": longitude,
+        "reportype": reportype,
+        "obsvalue_rawbt_1": [207, 209, 265, 266],
+    })
+
+
+def _assert_as_the_reference_asserts(pd, result, expect):
+    pd.testing.assert_frame_equal(result[expect.columns].reset_index(drop=True), expect.reset_index(drop=True), check_dtype=True,
+                                  check_column_type=True, check_names=True)
+
+
+def test_superob():
+    pd = pytest.importorskip("pandas")
+    df = _reference_frame(pd, [-126, -126, -90, -90], [1001, 1001, 1001, 1001])
+    before = df.copy()
+    result = create_filter_by_name("superob", **CONFIG)(df)
+    expect = pd.DataFrame({
+        "date": [pd.Timestamp("2025-01-01 00:00:01"), pd.Timestamp("2025-01-01 02:00:01")],
+        "latitude": [89.2, 89.2],
+        "longitude": [-126.0, -90.0],
+        "spatial_index": [13.0, 15.0],
+        "reportype": [1001, 1001],
+        "obsvalue_rawbt_1": [208.0, 265.5],
+    })
+    _assert_as_the_reference_asserts(pd, result, expect)
+    assert list(result.columns) == ["reportype", "latitude", "longitude", "obsvalue_rawbt_1", "spatial_index", "date"]
+    pd.testing.assert_frame_equal(df, before)  # the caller's table is not modified
+
+
+def test_superob_groupby():
+    pd = pytest.importorskip("pandas")
+    df = _reference_frame(pd, [-126.1, -126.3, -90, -90], [1001, 1001, 1001, 1002])
+    result = create_filter_by_name("superob", **CONFIG)(df)
+    expect = pd.DataFrame({
+        "date": [pd.Timestamp("2025-01-01 00:00:00"), pd.Timestamp("2025-01-01 02:00:01"), pd.Timestamp("2025-01-01 02:00:02")],
+        "latitude": [89.2, 89.2, 89.2],
+        "longitude": [-126.2, -90.0, -90.0],
+        "spatial_index": [13.0, 15.0, 15.0],
+        "reportype": [1001, 1001, 1002],
+        "obsvalue_rawbt_1": [208.0, 265.0, 266.0],
+    })
+    _assert_as_the_reference_asserts(pd, result, expect)
+
+
+# ---- the golden frames ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", GOLDEN["cases"], ids=lambda c: c["id"])
+def test_golden_frames_bit_equal(case):
+    want = R.golden_expected(case)
+    got = create_filter_by_name("superob", **case["config"])(R.golden_table(case))
+    assert all(isinstance(v, np.ndarray) for v in got.values())  # numpy in, numpy out
+    assert_same_columns(got, want, canonical=True)  # tied dates ordered canonically: pandas' quicksort leaves them as numpy's build does
+
+
+@pytest.mark.parametrize("case", GOLDEN["cases"], ids=lambda c: c["id"])
+def test_golden_frames_as_dataframes(case):
+    pd = pytest.importorskip("pandas")
+    got = create_filter_by_name("superob", **case["config"])(pd.DataFrame(R.golden_table(case)))
+    assert isinstance(got, pd.DataFrame)
+    assert {c: str(t) for c, t in got.dtypes.items()} == case["expected_dtypes"]
+    assert_same_columns({c: got[c].to_numpy() for c in got.columns}, R.golden_expected(case), canonical=True)
+
+
+# ---- against the restatement ---------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("seed", range(20))
+def test_seeded_tables_equal_the_restatement(seed):
+    table, config = R.random_table(5000 + seed, big_group=3000 if seed % 4 == 0 else 0, n=9000 if seed % 4 == 0 else None,
+                                   with_strings=seed % 5 == 2)
+    want = _restated(table, config)
+    got = create_filter_by_name("superob", **config)(table)
+    assert_same_columns(got, want)  # row ORDER included: both sort stably by date
+
+
+def test_groups_with_nothing_to_average_give_nan_and_nat():
+    table = {"date": np.array(["2025-01-01T00:00:00"] * 3 + ["2025-01-01T00:00:05"], dtype="datetime64[ns]"),
+             "latitude": np.array([10.0, 10.0, 10.0, -40.0]), "longitude": np.array([20.0, 20.0, 20.0, 60.0]),
+             "v": np.array([np.nan, np.nan, np.nan, np.inf]), "w": np.array([np.inf, -np.inf, 1.0, -0.0]),
+             "seen": np.array(["NaT", "NaT", "NaT", "2025-01-01T00:00:00.000000003"], dtype="datetime64[ns]")}
+    config = dict(grid="5/5", timeslot_length=3600, columns_to_take_nearest=["date"])
+    got = create_filter_by_name("superob", **config)(table)
+    assert_same_columns(got, _restated(table, {**config, "columns_to_groupby": []}))
+    assert np.isnan(got["v"][0]) and got["v"][1] == np.inf and np.isnan(got["w"][0]) and np.isnat(got["seen"][0])
+
+
+def _on_device(table):
+    out = {}
+    for name, v in table.items():
+        v = np.asarray(v)
+        out[name] = torch.from_numpy(v.astype("datetime64[ns]").view(np.int64) if v.dtype.kind == "M" else v).cuda()
+    return out
+
+
+def test_device_tensors_in_device_tensors_out_and_twice_the_same():
+    table, config = R.random_table(7001)
+    del table["seen"]  # on the device only `date` is known to hold datetimes: an int64 tensor elsewhere is an integer column
+    want = _restated(table, config)
+    f = create_filter_by_name("superob", **config)
+    got = f(_on_device(table))
+    assert list(got) == list(want)
+    assert all(isinstance(v, torch.Tensor) and v.is_cuda for v in got.values())
+    assert got["date"].dtype == torch.int64 and got["counts"].dtype == torch.float64 and got["reportype"].dtype == torch.float64
+    for name in want:
+        np.testing.assert_array_equal(_bits(got[name].cpu().numpy()), _bits(want[name]), err_msg=name)
+    again = f(_on_device(table))
+    mixed = f({**_on_device(table), "wide": table["wide"]})  # one host column among device tensors: still device tensors out
+    for other in (again, mixed):
+        for name in got:
+            assert other[name].is_cuda and np.array_equal(_bits(other[name].cpu().numpy()), _bits(got[name].cpu().numpy())), name
+
+
+def test_superob_then_irregular_to_grid_on_device_tensors():
+    rng = np.random.default_rng(42)
+    table, _ = R.random_table(7002, n=1500)
+    base = np.datetime64("2025-01-01T00:00:00", "ns")
+    table = {k: table[k] for k in ("date", "latitude", "longitude", "wide", "near")}
+    table["window_date"] = base + rng.integers(1, 4, 1500) * np.timedelta64(3600 * 10**9, "ns")
+    so = dict(grid="5/5", timeslot_length=1800, columns_to_take_nearest=["date"], columns_to_groupby=["window_date"])
+    ig = dict(window_date_column="window_date", columns=["wide", "near"], time_freq="1h", grid="5/5", window="(-3h, +3h]")
+    pipeline = create_filter_by_name("superob", **so) | create_filter_by_name("irregular_to_grid", **ig)
+    fields = pipeline(_on_device(table))
+    thinned = _restated(table, so)
+    thinned["spatial_index"] = thinned["spatial_index"].astype(np.int64)
+    n_cells = len(_grid("5/5")[0])
+    want = G.run_table(thinned, ig, n_cells, obs.parse_window, obs.parse_frequency)
+    assert len(fields) == len(want) == 3 * 2 and np.isfinite(want).sum() > 50
+    assert len({id(f.stack_ref()[0]) for f in fields}) == 1  # one stack in HBM
+    for i, field in enumerate(fields):
+        np.testing.assert_array_equal(field.to_numpy(flatten=True), want[i])
+
+
+def test_non_numeric_column_among_the_averaged_raises_type_error():
+    table, config = R.random_table(7003, with_strings=True)
+    with pytest.raises(TypeError, match="station"):
+        create_filter_by_name("superob", **{**config, "columns_to_groupby": ["reportype"]})(table)
+
+
+# ---- a large table ---------------------------------------------------------------------------------------------------------------------
+def test_two_million_rows():
+    """~500 000 groups and one group of 100 000 rows; the restatement on all of the big group and 2 000 random others."""
+    rng = np.random.default_rng(99)
+    n, n_big = 2_000_000, 100_000
+    lat, lon = _grid("o96")
+    lon = np.where(lon > 180, lon - 360, lon)
+    cell = rng.integers(0, len(lat), n)
+    big = rng.choice(n, n_big, replace=False)
+    cell[big] = 20_000
+    table = {"date": np.datetime64("2025-01-01T00:00:00", "ns") + rng.integers(0, 12 * 3600, n) * np.timedelta64(10**9, "ns"),
+             "latitude": lat[cell] + rng.uniform(-0.05, 0.05, n), "longitude": lon[cell] + rng.uniform(-0.05, 0.05, n)}
+    table["date"][big] = np.datetime64("2025-01-01T00:00:00", "ns") + rng.integers(0, 3600, n_big) * np.timedelta64(10**9, "ns")
+    table["wide"] = rng.standard_normal(n) * 10.0 ** rng.integers(-8, 9, n)
+    table["wide"][rng.random(n) < 0.1] = np.nan
+    table["near"] = 1e15 + rng.integers(0, 1000, n) * 0.125
+    got = create_filter_by_name("superob", grid="o96", timeslot_length=3600, columns_to_take_nearest=["date"])(table)
+    n_groups = len(got["date"])
+    assert 400_000 <= n_groups <= 600_000
+    assert np.all(np.diff(got["date"].view(np.int64)) >= 0)
+
+    # the groups, restated on the host (the search by cKDTree, the bookkeeping by numpy)
+    distance, spatial = R.nearest_grid(lat, lon, table["latitude"], table["longitude"])
+    ns = table["date"].view(np.int64)
+    key = spatial + len(lat) * ((ns - ns.min()) // (3600 * 10**9))
+    order = np.argsort(key, kind="stable")
+    starts = np.flatnonzero(np.r_[True, np.diff(key[order]) != 0])
+    ends = np.r_[starts[1:], n]
+    sizes = ends - starts
+    assert len(starts) == n_groups and sizes.max() >= n_big
+    sample = np.unique(np.r_[np.argmax(sizes), rng.choice(n_groups, 2000, replace=False)])
+    members = [order[starts[g]:ends[g]] for g in sample]
+    # the same groups in the output: found by their nearest row's date and cell (the means of spatial_index are whole numbers)
+    nearest = np.array([rows[np.argmin(distance[rows])] for rows in members])
+    small = [i for i, rows in enumerate(members) if len(rows) < n_big]
+    lookup_key = {(int(s), int(d)): i for i, (s, d) in enumerate(zip(got["spatial_index"].astype(np.int64).tolist(), got["date"].view(np.int64).tolist()))}
+    for name in ("wide", "near", "latitude"):
+        want = np.empty(len(members))
+        want[small] = R.kahan_means_of_many([table[name][members[i]] for i in small])
+        for i, rows in enumerate(members):
+            if len(rows) >= n_big:
+                want[i] = R.kahan_mean(table[name][rows])[0]
+        rows_out = []
+        for i, rows in enumerate(members):
+            k = (int(spatial[rows[0]]), int(ns[nearest[i]]))
+            rows_out.append(lookup_key.get(k, -1))
+        rows_out = np.array(rows_out)
+        assert (rows_out >= 0).all()
+        np.testing.assert_array_equal(_bits(got[name][rows_out]), _bits(want), err_msg=name)

@@ -46,6 +46,8 @@ def main():
     ap.add_argument("--only-vertical", action="store_true", help="only the column kernel (atx_pressure_at_height_stack) rows")
     ap.add_argument("--only-rotate", action="store_true", help="only the vector-frame kernel (atx_rotate_vectors_stack) rows")
     ap.add_argument("--only-obs", action="store_true", help="only the observation-gridding rows (atx_obs_best_per_cell, atx_obs_fill_stack)")
+    ap.add_argument("--only-superob", action="store_true", help="only the superob rows (atx_obs_group_mean, atx_obs_group_argmin, the filter end "
+                    "to end beside the reference's statement in pandas on this host); --only-obs runs them after its own rows")
     ap.add_argument("--only-pointwise", action="store_true", help="only the per-point, mask and reduction rows (atx_pointwise.hip, atx_mask.hip, "
                     "atx_reduce.hip), each with a checksum of what it computed on the seeded stack")
     args = ap.parse_args()
@@ -172,6 +174,111 @@ def main():
             del date, values, uniform, swath, best, winner
             torch.cuda.empty_cache()
 
+    def superob_pandas_ms(table, grid_lat, grid_lon, slot, repeats):
+        """The reference's statement for one table on this host, one process, as pandas runs it (R: support/superob.py:43-69,
+        superob.py:72-96): cKDTree, groupby().mean(), groupby().idxmin(), concat, sort_values."""
+        try:
+            import pandas as pd
+            from scipy.spatial import cKDTree
+        except ImportError:
+            return None
+        points = np.column_stack([grid_lat, np.where(grid_lon > 180, grid_lon - 360, grid_lon)])
+        times = []
+        for _ in range(repeats):
+            df = pd.DataFrame(table)
+            t0 = time.perf_counter()
+            df = df.dropna(subset=["date", "latitude", "longitude"])
+            time_grid = pd.date_range(df["date"].min(), df["date"].max(), freq=f"{slot}s")
+            temporal = np.clip(np.searchsorted(time_grid, df["date"], side="right") - 1, 0, None)
+            distances, spatial = cKDTree(points).query(df[["latitude", "longitude"]])
+            df = df.assign(grid_index=spatial + len(points) * temporal, spatial_index=spatial, distance=distances)
+            keys = ["grid_index", "reportype"]
+            averaged = df.groupby(keys, observed=True, sort=False)[[c for c in df.columns if c not in keys + ["date"]]].mean()
+            nearest = df.loc[df.groupby(keys, observed=True, sort=False)["distance"].idxmin(), ["date"] + keys].set_index(keys)
+            out = pd.concat([averaged, nearest], axis=1, join="inner").reset_index().drop(columns=["grid_index", "distance"])
+            out = out.sort_values("date")
+            times.append((time.perf_counter() - t0) * 1e3)
+            rows = len(out)
+            del df, averaged, nearest, out
+        return float(np.median(times)), rows
+
+    def superob_rows():
+        """superob: the group bookkeeping (torch: fold the keys, one stable sort, segment offsets), the two kernels on their own, and
+        the filter end to end — table resident in HBM and table in host memory, interleaved, medians — beside the reference's
+        statement in pandas on this host.  4 value columns; mean group sizes 4 and 40; once ONE group of 10^6 rows (its sum is
+        sequential by definition).  Algorithmic bytes of bookkeeping + mean: keys (8) + permutation (4) + n_cols * 8 per row in,
+        n_cols * 8 per group out; of the mean kernel alone: 4 + n_cols * 8 per row, 8 + n_cols * 16 per group."""
+        from anemoi_transform_amd import obs
+        from anemoi_transform_amd.filters import create_filter_by_name
+
+        n_cols, slot = 4, 3600
+        grid = lookup("o96")
+        grid_lat, grid_lon = grid["latitudes"], np.where(grid["longitudes"] > 180, grid["longitudes"] - 360, grid["longitudes"])
+        n_grid = len(grid_lat)
+        for n, size, single in ((1_000_000, 4, False), (1_000_000, 40, False), (10_000_000, 4, False), (10_000_000, 40, False),
+                                (1_000_000, 1_000_000, True)):
+            shape = f"{n:.0e} rows C{n_cols} " + ("one group" if single else f"groups of ~{size}")
+            rng = np.random.default_rng(n + size)
+            n_keys = max(1, n // size)
+            n_slots = max(1, round(n_keys / n_grid))
+            cell = rng.integers(0, min(n_grid, n_keys), n)
+            table = {"date": np.datetime64("2025-01-01T00:00:00", "ns") + rng.integers(0, n_slots * slot, n) * np.timedelta64(10**9, "ns"),
+                     "latitude": grid_lat[cell] + rng.uniform(-0.05, 0.05, n), "longitude": grid_lon[cell] + rng.uniform(-0.05, 0.05, n),
+                     "reportype": np.full(n, 1001, dtype=np.int64)}
+            for j in range(n_cols - 2):  # latitude and longitude are averaged too: n_cols value columns beside spatial_index / distance
+                v = rng.standard_normal(n) * 10.0 ** rng.integers(-8, 9, n)
+                v[rng.random(n) < 0.1] = np.nan
+                table[f"v{j}"] = v
+            resident = {k: torch.from_numpy(v.view(np.int64) if v.dtype.kind == "M" else v).to(dev) for k, v in table.items()}
+            # the kernels on their own, on the groups the filter forms (cell and slot known here without the search)
+            ns = resident["date"]
+            key = torch.from_numpy(cell).to(dev) + n_grid * ((ns - ns.min()) // (slot * 10**9))
+            values = torch.stack([resident["latitude"], resident["longitude"]] + [resident[f"v{j}"] for j in range(n_cols - 2)])
+            distance = torch.rand(n, dtype=torch.float64, device=dev)
+            groups = obs.superob_groups([key], None, dev)
+            G = groups.n_groups
+            mean = torch.empty((n_cols, G), dtype=torch.float64, device=dev)
+            count = torch.empty((n_cols, G), dtype=torch.int64, device=dev)
+            nearest = torch.empty(G, dtype=torch.int32, device=dev)
+            note = f"{G} groups, the largest {int((groups.offsets[1:] - groups.offsets[:-1]).max())} rows"
+            t_groups = timeit(lambda: obs.superob_groups([key], None, dev), n=7)
+            t_mean = timeit(lambda: native.obs_group_mean(values, groups.order, groups.offsets, mean, count), n=7)
+            t_argmin = timeit(lambda: native.obs_group_argmin(distance, groups.order, groups.offsets, nearest), n=7)
+            record(f"superob_groups {shape}", t_groups, n * 12, "torch on the device: fold the keys, ONE stable sort, offsets; " + note)
+            record(f"obs_group_mean {shape}", t_mean, n * (4 + 8 * n_cols) + G * (8 + 16 * n_cols), "Kahan in row order, lane per (group, column); " + note)
+            record(f"obs_group_argmin {shape}", t_argmin, n * 12 + G * 12, "first row of smallest distance; " + note)
+            record(f"superob groups + mean {shape}", t_groups + t_mean, n * (12 + 8 * n_cols) + G * 8 * n_cols, "sum of the two rows above")
+            res[f"obs_group_mean {shape}"]["rows_per_s"] = n / (t_mean * 1e-3)
+            res[f"superob groups + mean {shape}"]["rows_per_s"] = n / ((t_groups + t_mean) * 1e-3)
+            del key, values, distance, groups, mean, count, nearest
+            # the filter end to end: resident and host-fed interleaved (wall clock around a device synchronise), medians
+            f = create_filter_by_name("superob", grid="o96", timeslot_length=slot, columns_to_take_nearest=["date"], columns_to_groupby=["reportype"])
+            took = {"resident": [], "host-fed": []}
+            for i in range(1 + (3 if n > 2_000_000 else 5)):
+                for name, tab in (("resident", resident), ("host-fed", table)):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    out = f(tab)
+                    torch.cuda.synchronize()
+                    if i:  # the first round warms up (code objects, the grid's search tree)
+                        took[name].append((time.perf_counter() - t0) * 1e3)
+                    rows_out = len(out["date"])
+                    del out
+            for name, ts in took.items():
+                res[f"superob filter {name} {shape}"] = {"ms": float(np.median(ts)), "min_ms": float(min(ts)), "max_ms": float(max(ts)), "runs": len(ts),
+                                                          "rows_per_s": n / (float(np.median(ts)) * 1e-3), "rows_out": rows_out,
+                                                          "note": "create_filter_by_name('superob') end to end: drop missing, nearest grid point (device search, "
+                                                                  "latitude / longitude and the answer cross the host link), groups, means, nearest row, sort by date"}
+                print(f"{'superob filter ' + name + ' ' + shape:58s} {np.median(ts):9.1f} ms  [{min(ts):.1f} .. {max(ts):.1f}]  {rows_out} rows out", flush=True)
+            host = superob_pandas_ms(table, grid["latitudes"], grid["longitudes"], slot, repeats=1 if n > 2_000_000 else 3)
+            if host is not None:
+                res[f"superob pandas {shape}"] = {"ms": host[0], "rows_out": host[1], "runs": 1 if n > 2_000_000 else 3,
+                                                  "note": "the reference's statement on this host, one process: cKDTree, groupby().mean(), "
+                                                          "groupby().idxmin(), concat, sort_values"}
+                print(f"{'superob pandas ' + shape:58s} {host[0]:9.1f} ms  (host)  {host[1]} rows out", flush=True)
+            del resident, table
+            torch.cuda.empty_cache()
+
     def checksum(out):
         """Order-sensitive 128-bit checksum of a tensor's bytes, summed on the device in wrapping int64; anything else by its repr."""
         if not torch.is_tensor(out):
@@ -254,8 +361,15 @@ def main():
             json.dump(res, open(args.out, "w"), indent=1)
         return
 
+    if args.only_superob:
+        superob_rows()
+        if args.out:
+            json.dump(res, open(args.out, "w"), indent=1)
+        return
+
     if args.only_obs:
         obs_rows()
+        superob_rows()
         if args.out:
             json.dump(res, open(args.out, "w"), indent=1)
         return
