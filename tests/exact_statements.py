@@ -16,10 +16,14 @@ defines — those have to be matched exactly.
 
 from __future__ import annotations
 
+import json
 import math
+import os
 
 import mpmath
 import numpy as np
+
+import vertical_restatement as vr
 
 PREC = 128
 mp = mpmath.mp
@@ -197,6 +201,7 @@ class Consts:
         self.aw, self.bw, self.ai, self.bi = c(17.502), c(32.19), c(22.587), c(-0.7)
         self.eps, self.k = c(MET_EPSILON), c(MET_EPSILON * (1.0 / MET_EPSILON - 1.0))
         self.one_m_eps, self.guard, self.rzero = c(1.0 - MET_EPSILON), c(1.0e-4), c(1.0e-4)
+        self.qzero = c(1.0e-8)
         self.dp_num = c(17.502 * MET_T0)
         self.deg_polar, self.rad2deg = c(DEG_POLAR), c(rad2deg_factor(np.dtype(dtype).type))
 
@@ -265,6 +270,41 @@ def in_guard_band(k: Consts, r, t, p, dtype) -> np.ndarray:
     return out
 
 
+def q_to_d_exact(k: Consts, q: float, p: float):
+    """dewpoint_from_specific_humidity (tests/vertical_restatement.py): q == 0 -> 1e-8 (rounded), e = p q / (eps + c(eps (1/eps - 1)) q),
+    ln = log(e / c1), (32.19 ln - c(17.502 T0)) / (ln - 17.502)."""
+    if _special((q, p)):
+        return math.nan
+    q = k.qzero if q == 0 else mpmath.mpf(q)
+    e = mpmath.mpf(p) * q / (k.eps + k.k * q)
+    if e <= 0:
+        return math.nan
+    ln = mpmath.log(e / k.c1)
+    return (k.bw * ln - k.dp_num) / (ln - k.aw)
+
+
+def d_to_q_exact(k: Consts, td: float, p: float, guarded: bool = True):
+    """specific_humidity_from_dewpoint: e = es_water(td); NaN where p - e < 1e-4; eps e / (p - c(1 - eps) e).  Non-finite operands give
+    what numpy's statement gives."""
+    if _special((td, p)):
+        with np.errstate(all="ignore"):
+            return float(vr.specific_humidity_from_dewpoint(np.array([td]), np.array([p]))[0])
+    e = _es_water(k, mpmath.mpf(td))
+    if guarded and p - e < k.guard:
+        return math.nan
+    return k.eps * e / (p - k.one_m_eps * e)
+
+
+def in_guard_band_d(k: Consts, td, p, dtype) -> np.ndarray:
+    """``in_guard_band`` for specific_humidity_from_dewpoint: e = es_water(td)."""
+    eps = float(np.finfo(dtype).eps)
+    out = np.zeros(len(td), dtype=bool)
+    for i, (ti, pi) in enumerate(zip(np.asarray(td, float), np.asarray(p, float))):
+        if math.isfinite(ti + pi):
+            out[i] = abs(pi - _es_water(k, mpmath.mpf(ti)) - k.guard) <= GUARD_BAND_ULPS * eps * abs(pi)
+    return out
+
+
 def direction_deg_exact(k: Consts, s: float, c: float):
     """direction_from_cos_sin(degrees=True): rad2deg(atan2(s, c)) with the wrap to [0, 360), exact."""
     a = atan2_exact(s, c)
@@ -319,7 +359,8 @@ def _cases(dtype, parts):
 
 
 def humidity_cases(kind: str, dtype, n: int = 4096, seed: int = 0) -> dict:
-    """Inputs of one humidity statement: ``kind`` in r_to_d (r, t), d_to_r (td, t), q_to_r (q, t, p), r_to_q (r, t, p)."""
+    """Inputs of one humidity statement: ``kind`` in r_to_d (r, t), d_to_r (td, t), q_to_r (q, t, p), r_to_q (r, t, p), q_to_d (q, p),
+    d_to_q (td, p)."""
     rng = np.random.default_rng(seed)
     dt = np.dtype(dtype).type
     t = lambda m: rng.uniform(150.0, 350.0, m)  # noqa: E731
@@ -347,6 +388,25 @@ def humidity_cases(kind: str, dtype, n: int = 4096, seed: int = 0) -> dict:
             "mixed-phase ends": (10.0 ** rng.uniform(-6.0, -2.0, lad.size), lad, rng.uniform(5e4, 1.05e5, lad.size)),
         }
         return _cases(dtype, {**parts, "specials": _humidity_specials(kind, dtype)})
+    if kind == "q_to_d":
+        zeros = np.where(np.arange(n // 4) % 2 == 0, 0.0, rng.uniform(sub_lo, sub_hi, n // 4))
+        parts = {
+            "atmosphere": (10.0 ** rng.uniform(-8.0, math.log10(0.05), n), p(n)),
+            "q = 0 and subnormal": (zeros, p(n // 4)),
+        }
+        return _cases(dtype, {**parts, "specials": _humidity_specials(kind, dtype)})
+    if kind == "d_to_q":
+        # the guard band: p within 48 ulps of es_water(td) + 1e-4
+        k = consts(dtype)
+        tb = rng.uniform(280.0, 320.0, n // 8).astype(dtype)
+        e = np.array([float(_es_water(k, mpmath.mpf(float(tt)))) for tt in tb])
+        bits = np.int32 if dt is np.float32 else np.int64
+        pb = ((e + 1.0e-4).astype(dtype).view(bits) + rng.integers(-48, 49, e.size).astype(bits)).view(dtype)
+        parts = {
+            "atmosphere": (t(n), p(n)),  # es_water(350 K) = 41 kPa: the guard's NaN occurs
+            "guard band": (tb, pb),
+        }
+        return _cases(dtype, {**parts, "specials": _humidity_specials(kind, dtype)})
     assert kind == "r_to_q"
     # the guard band: p - e within a few parts in 1e6 of 1e-4 (e = r es_mixed(t) / 100 chosen to hit it)
     k = consts(dtype)
@@ -368,8 +428,11 @@ def humidity_cases(kind: str, dtype, n: int = 4096, seed: int = 0) -> dict:
 def _humidity_specials(kind: str, dtype) -> tuple:
     """NaN and +-inf in every operand but the pressure (an infinite pressure makes numpy's q_to_r infinite, not NaN): NaN results."""
     s = [np.nan, np.inf, -np.inf]
-    ok = {"r_to_d": 50.0, "d_to_r": 280.0, "q_to_r": 0.01, "r_to_q": 50.0}[kind]
+    ok = {"r_to_d": 50.0, "d_to_r": 280.0, "q_to_r": 0.01, "r_to_q": 50.0, "q_to_d": 0.01, "d_to_q": 280.0}[kind]
     x = np.array(s + [ok] * 3)
+    if kind in ("q_to_d", "d_to_q"):  # (x, p): the pressure is the second operand — NaN only: an infinite pressure is an infinite divisor,
+        # outside the domain of the kernels' `quotient` (csrc/atx_combine.hip), as for q_to_r above
+        return (x, np.array([85000.0] * 3 + [np.nan, 85000.0, 85000.0]))
     t = np.array([280.0] * 3 + s)
     return (x, t) if kind in ("r_to_d", "d_to_r") else (x, t, np.full(6, 85000.0))
 
@@ -663,17 +726,293 @@ def _build(name, dt) -> Statement:
             want, fn = oracle.relative_humidity_from_dewpoint(*ins), d_to_r_exact
         elif kind == "q_to_r":
             want, fn = oracle.relative_humidity_from_specific_humidity(ins[1], ins[0], p), q_to_r_exact
+        elif kind == "q_to_d":
+            want, fn = vr.dewpoint_from_specific_humidity(*ins), q_to_d_exact
+        elif kind == "d_to_q":
+            want, fn = vr.specific_humidity_from_dewpoint(*ins), d_to_q_exact
+            band = in_guard_band_d(k, *_flat(*ins), dt)
+            alt = {0: (band, np.nan)}
         else:
             want, fn = oracle.specific_humidity_from_relative_humidity(ins[1], ins[0], p), r_to_q_exact
             band = in_guard_band(k, *_flat(ins[0], ins[1], p), dt)
             alt = {0: (band, np.nan)}
         args = _flat(*ins[:2]) + ([p.reshape(-1)] if p is not None else [])
         exact = ex(lambda *a: fn(k, *a), *args)
-        if kind == "r_to_q":  # within the guard band the reference is the unguarded statement, and NaN is accepted too
-            exact[band] = ex(lambda *a: r_to_q_exact(k, *a, guarded=False), *[x[band] for x in args])
+        if kind in ("r_to_q", "d_to_q"):  # within the guard band the reference is the unguarded statement, and NaN is accepted too
+            unguarded = r_to_q_exact if kind == "r_to_q" else d_to_q_exact
+            exact[band] = ex(lambda *a: unguarded(k, *a, guarded=False), *[x[band] for x in args])
         return Statement(name, dt, ins, case, [exact], [want.astype(dt, copy=False)], [COMPOSED], levels=levels, alt=alt)
 
 
 SINGLE_FUNCTION = ("exp", "log", "cos_sin", "cos_sin_deg", "atan2", "snow_cover", "polar_to_xy")
-COMPOSED_STATEMENTS = ("atan2_deg", "xy_to_polar", "r_to_d", "d_to_r", "q_to_r", "r_to_q", "q_to_r_level", "r_to_q_level")
+COMPOSED_STATEMENTS = ("atan2_deg", "xy_to_polar", "r_to_d", "d_to_r", "q_to_r", "r_to_q", "q_to_r_level", "r_to_q_level",
+                       "q_to_d", "d_to_q")
 ALL = SINGLE_FUNCTION + COMPOSED_STATEMENTS
+
+
+# ---- the column statement: pressure_at_height_levels (tests/vertical_restatement.py, csrc/atx_vertical.hip) ---------------------
+# Evaluated per column on the exact values of the stored numbers (float32 inputs widened exactly; A, B float64), with the constants as
+# the float64 literals the statement uses: Rd, Rv, g, and alpha[0] = fl64(log 2) (numpy's np.log(2.0), the kernel's kLn2) — that double,
+# not the exact ln 2.  tdphi = fl64(height * g) is rounded BEFORE the comparison, as numpy and the kernel's host side both do.
+#
+# No "either side" band is needed where tdphi meets a dphi[k]: the statement is continuous across every one of its branch boundaries —
+# `below` meets `above` at p_full[n-1] (tdphi = dphi[n-1]), adjacent segments meet at p_full[k] (tdphi = dphi[k]), and the wrap of
+# i == n (a = n-1, b = 0) meets the top segment at p_full[0] — so a count that the exact dphi and numpy's rounded one decide differently
+# moves the value by no more than the slope times the rounding (tests/test_exact_statements.py checks the continuity).
+#
+# A level whose term cannot be evaluated (a NaN or an infinity in t or q, a half-level pressure ratio that is not positive, a zero
+# layer thickness in pressure) makes dphi non-finite from that level to the top in numpy; the exact dphi is "special" there.  The count
+# takes numpy's verdict at those levels (a NaN never counts, -inf always does); a result that needs a special dphi, a zero denominator
+# (da == db: n_lev == 1 above the level; dphi[n-1] == 0) or a non-finite surface pressure is the value numpy's restatement gives — NaN
+# or +-inf, matched as `ulp_errors` matches specials.
+LN2_F64 = float(np.log(2.0))
+_GOLDEN_AB = None
+
+
+def hybrid_column(n):
+    """n + 1 half levels of a hybrid column: pure pressure (A) near the top, terrain-following (B) near the ground, A[0] = B[0] = 0."""
+    global _GOLDEN_AB
+    if n == 2:  # the reference's own bottom levels, the top half level not at 0
+        if _GOLDEN_AB is None:
+            path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "height_level_humidity.json")
+            _GOLDEN_AB = json.load(open(path))["AB"]
+        return np.array(_GOLDEN_AB["A"]), np.array(_GOLDEN_AB["B"])
+    eta = np.concatenate([[0.0], np.geomspace(2e-4, 1.0, n)]) if n > 1 else np.array([0.0, 1.0])
+    B = np.clip((eta - 0.2) / 0.8, 0.0, 1.0) ** 1.5
+    return 101325.0 * (eta - B) * 0.9, B
+
+
+class ColumnProfile:
+    """One column, exact: p_half, p_full (mpf lists) and dphi (mpf, or None where it is special)."""
+
+    def __init__(self, t, q, sp: float, A, B):
+        n = len(t)
+        self.n, self.ok = n, math.isfinite(sp)
+        if not self.ok:
+            return
+        m = mpmath.mpf
+        rd, rv = m(vr.RD), m(vr.RV)
+        ph = [m(float(A[k])) + m(float(B[k])) * m(sp) for k in range(n + 1)]
+        self.p_half, self.p_full = ph, [(ph[k] + ph[k + 1]) / 2 for k in range(n)]
+        self.dphi = [None] * n
+        s = m(0)
+        for k in range(n - 1, -1, -1):  # bottom level first; dphi is computed once and serves every height
+            tk, qk = float(t[k]), float(q[k])
+            if not (math.isfinite(tk) and math.isfinite(qk)):
+                break
+            if k == 0:
+                alpha = m(LN2_F64)  # alpha_top = "ifs"
+            else:
+                lo, hi = ph[k], ph[k + 1]
+                if lo == 0 or hi == lo or hi / lo <= 0:
+                    break
+                alpha = 1 - lo / (hi - lo) * mpmath.log(hi / lo)
+            s = s + alpha * (rd * (1 - m(qk)) + rv * m(qk)) * m(tk)
+            self.dphi[k] = s
+
+    def count(self, tdphi: float, dphi_numpy) -> int:
+        """i = #{k : tdphi > dphi[k]}; numpy's (non-finite) dphi decides at the special levels."""
+        return sum(bool(tdphi > (dphi_numpy[k] if d is None else d)) for k, d in enumerate(self.dphi))
+
+    def levels(self, i: int):
+        """(a, b) of the count i > 0, as the statement indexes them."""
+        n = self.n
+        a = n - i - 1
+        a = a + n if a < 0 else a  # i == n: numpy's index -1 is the bottom level
+        b = 0 if i == n else a + 1
+        return a, min(b, n - 1)
+
+    def value(self, tdphi: float, dphi_numpy, special: float):
+        """The exact pressure at tdphi = fl64(height * g).  A special dphi enters as numpy's value of it: a NaN gives NaN; an infinite
+        dphi[n-1] or dphi[a] makes the interpolation weight 0 (the result is p_half[n] / p_full[b], exact); an infinite dphi[b] gives
+        inf / inf.  Where a denominator is zero or the surface pressure is not finite the value is ``special``, numpy's (not finite)."""
+        if not self.ok:
+            return special
+        n, i = self.n, self.count(tdphi, dphi_numpy)
+        at = lambda k: float(dphi_numpy[k]) if self.dphi[k] is None else self.dphi[k]  # noqa: E731
+        if i == 0:
+            d = at(n - 1)
+            if isinstance(d, float):
+                return math.nan if math.isnan(d) else self.p_half[n]
+            if d == 0:
+                return special
+            return self.p_half[n] + tdphi / d * (self.p_full[n - 1] - self.p_half[n])
+        a, b = self.levels(i)
+        da, db = at(a), at(b)
+        if isinstance(db, float) or (isinstance(da, float) and math.isnan(da)):
+            return math.nan if a != b else special
+        if isinstance(da, float):
+            return self.p_full[b]
+        if da == db:
+            return special
+        return self.p_full[b] + (tdphi - db) / (da - db) * (self.p_full[a] - self.p_full[b])
+
+
+def tdphi_of(height: float) -> float:
+    return float(height) * vr.G
+
+
+def numpy_dphi(t, q, sp, A, B) -> np.ndarray:
+    """The restatement's dphi ``[n_lev, m]`` (float64)."""
+    _, _, alpha = vr.pressure_at_model_levels(A, B, sp)
+    return vr.relative_geopotential_thickness(alpha, t, q)
+
+
+def column_exact(heights, t, q, sp, A, B):
+    """``(exact, numpy)``: object and float64 arrays ``[len(heights), m]`` of pressure_at_height_levels on the columns of t, q
+    ``[n_lev, m]`` and sp ``[m]``."""
+    t, q, sp = np.asarray(t), np.asarray(q), np.asarray(sp)
+    m = sp.size
+    with np.errstate(all="ignore"):
+        dphi = numpy_dphi(t, q, sp, A, B)
+        want = np.stack([vr.pressure_at_height_levels(h, t, q, sp, A, B) for h in heights])
+    exact = np.empty((len(heights), m), dtype=object)
+    for c in range(m):
+        prof = ColumnProfile(t[:, c], q[:, c], float(sp[c]), A, B)
+        for j, h in enumerate(heights):
+            x = prof.value(tdphi_of(h), dphi[:, c], float(want[j, c]))
+            if isinstance(x, float) and math.isfinite(x):
+                raise AssertionError(f"column {c}, height {h}: numpy gives the finite {x} where the exact statement has no value")
+            exact[j, c] = x
+    return exact, want
+
+
+def second_walk(dphi: np.ndarray, tdphi: float) -> np.ndarray:
+    """Per column of numpy's dphi: 0 < i < n and a = n - 1 - i is not the first level from the bottom that does not count — the
+    kernel's `a != a0`, the columns that walk a second time."""
+    n = dphi.shape[0]
+    counts = tdphi > dphi
+    i = counts.sum(axis=0)
+    first = n - 1 - np.argmax(~counts[::-1], axis=0)  # (argmax of an all-False column is 0; those columns have i == n)
+    return (i > 0) & (i < n) & (n - 1 - i != first)
+
+
+COLUMN_N_LEV = (1, 2, 3, 60, 137)
+# Height classes.  "near ground" is 0, 2 and 10 m — the heights the four filters are used at — and a negative height (i == 0 extended
+# below the ground); 100 m is a class of its own: the ill-conditioned alpha of the bottom level enters `below` in proportion to the
+# height, and numpy's own error there is ten times that at 10 m, which one class would carry to the heights that matter.
+NEAR_GROUND, H100, ALOFT, ABOVE_TOP = "near ground", "100 m", "aloft", "above top"
+HEIGHT_CLASSES = (NEAR_GROUND, H100, ALOFT, ABOVE_TOP)
+# Case groups: numpy's error on the physical columns and on the bent / special ones (cancellations of a negative layer) differ by
+# orders of magnitude, so its worst is pinned — and the kernel's ceiling set — for each
+PHYSICAL, ODD = "physical", "bent and special"
+CASE_GROUP = {"atmosphere": PHYSICAL, "standard profile": PHYSICAL, "bent": ODD, "specials": ODD}
+
+
+def _standard_profile(rng, n, m, A, B):
+    """A smooth lapse-rate profile in pressure (T = T0 (p / sp)^0.19 down to an isothermal 216.65 K) with 0.2 K of noise; q falls with
+    pressure.  dphi is strictly monotone and alpha realistic."""
+    sp = rng.uniform(60000.0, 105000.0, m)
+    p_full, _, _ = vr.pressure_at_model_levels(A, B, sp)
+    t0 = rng.uniform(260.0, 305.0, m)
+    t = np.maximum(t0 * (np.maximum(p_full, 1.0) / sp) ** 0.19, 216.65) + rng.normal(0.0, 0.2, (n, m))
+    q = np.maximum(rng.uniform(2e-3, 1.8e-2, m) * (p_full / sp) ** 3, 2e-6) * rng.uniform(0.8, 1.2, (n, m))
+    return t, q, sp
+
+
+def _column_heights(n, t, q, sp, A, B):
+    """(height, class) pairs: 0, 2, 10, 100 m and one negative height (i == 0, extrapolation below the ground), two interior heights and
+    one above the top level, the last three from the median dphi[0] of these columns."""
+    with np.errstate(all="ignore"):
+        top = float(np.median(numpy_dphi(t, q, sp, A, B)[0])) / vr.G
+    return [(0.0, NEAR_GROUND), (2.0, NEAR_GROUND), (10.0, NEAR_GROUND), (100.0, H100), (-2.0, NEAR_GROUND),
+            (0.3 * top, ALOFT), (0.7 * top, ALOFT), (1.5 * top + 1000.0, ABOVE_TOP)]
+
+
+def column_cases(dtype, n_lev: int, seed: int = 0):
+    """``(cases, heights)``: {case name: (t[n_lev, m], q[n_lev, m], sp[m])} in ``dtype`` on ``hybrid_column(n_lev)``, and the
+    (height, class) pairs every case is evaluated at."""
+    rng = np.random.default_rng(1000 * seed + n_lev)
+    n = n_lev
+    A, B = hybrid_column(n)
+    big = n >= 60
+    # atmosphere: the ranges of test_height_level_humidity.random_columns, a few dry columns
+    m = 160 if big else 256
+    t = rng.uniform(200.0, 310.0, (n, m))
+    q = 10.0 ** rng.uniform(-6.0, -1.7, (n, m))
+    q[:, :7] = 0.0
+    atmosphere = (t, q, rng.uniform(50000.0, 106000.0, m))
+    standard = _standard_profile(rng, n, 64 if big else 128, A, B)
+    heights = _column_heights(n, *standard, A, B)
+    # bent: negative temperatures that make dphi non-monotone.  Two thirds of the columns are aimed: a level one to three above the one
+    # where dphi first reaches tdphi of a chosen height gets a temperature negative enough to pull dphi under tdphi again, so that
+    # level counts, a moves up past it, and the pair (a, a + 1) is no longer the one the first walk kept; the rest carry one to
+    # three negative temperatures anywhere (the top included: dphi[0] far below every height).
+    m = 96 if big else 128
+    bt, bq, bsp = _standard_profile(rng, n, m, A, B)
+    with np.errstate(all="ignore"):
+        _, _, alpha = vr.pressure_at_model_levels(A, B, bsp)
+        term = alpha * (vr.RD * (1.0 - bq) + vr.RV * bq)  # per kelvin
+        dphi = numpy_dphi(bt, bq, bsp, A, B)
+    aimed = [h for h, _ in heights[1:4]] + [h for h, cls in heights if cls == ALOFT]
+    for c in range(m):
+        if c % 8 == 7:
+            continue  # (a few columns stay straight: the case takes every branch at every n_lev)
+        if c % 3 < 2 and n > 1:
+            tdphi = tdphi_of(aimed[(c // 3) % len(aimed)])
+            below = np.flatnonzero(tdphi > dphi[:, c])
+            first = int(below.min()) - 1 if below.size else n - 1  # the first level from the bottom that does not count
+            j = max(first - int(rng.integers(1, 4)), 0)
+            if j < first or first == 0:
+                need = dphi[min(j + 1, n - 1), c] - tdphi  # what the term of level j has to undo
+                bt[j, c] = -(max(need, 0.0) / term[j, c]) * rng.uniform(1.2, 3.0) - rng.uniform(1.0, 50.0)
+        elif n > 1 or c % 2 == 0:  # (n_lev == 1: every other column, so that both of its branches are taken)
+            for j in rng.integers(n, size=int(rng.integers(1, 4))):
+                bt[j, c] = -rng.uniform(100.0, 900.0)
+    # specials: NaN / +-inf in t or q at the top, the bottom and the middle; NaN, 0, negative and infinite sp; t = 0 at the bottom level
+    st, sq, ssp = _standard_profile(rng, n, 24, A, B)
+    c = 0
+    for arr in (st, sq):
+        for level in (0, n - 1, n // 2):
+            for v in (np.nan, np.inf, -np.inf):
+                if c < 18:
+                    arr[level, c] = v
+                c += 1
+    ssp[18:22] = [np.nan, 0.0, -50000.0, np.inf]
+    st[n - 1, 22:24] = 0.0  # dphi[n-1] = 0: 0 / 0 at height 0
+    cases = {"atmosphere": atmosphere, "standard profile": standard, "bent": (bt, bq, bsp), "specials": (st, sq, ssp)}
+    return _cases(dtype, cases), heights
+
+
+class ColumnStatement:
+    """The column statement on ``column_cases(dtype, n_lev)``: per case the inputs, the exact values and numpy's (float64)
+    ``[n_heights, m]``; the errors of a result in ulps of ``dtype`` per case and height."""
+
+    def __init__(self, dtype, n_lev):
+        self.dtype, self.n_lev = np.dtype(dtype).type, n_lev
+        self.A, self.B = hybrid_column(n_lev)
+        self.cases, self.heights = column_cases(dtype, n_lev)
+        self.exact, self.numpy_out = {}, {}
+        for name, (t, q, sp) in self.cases.items():
+            self.exact[name], self.numpy_out[name] = column_exact([h for h, _ in self.heights], t, q, sp, self.A, self.B)
+        self._np_err = {}
+
+    def errors(self, case: str, j: int, got: np.ndarray) -> np.ndarray:
+        """ulps (of the statement's dtype) of ``got`` from the exact values of height j; the columns may repeat cyclically."""
+        x = self.exact[case][j]
+        return ulp_errors(got, np.resize(x, np.asarray(got).size), self.dtype)
+
+    def numpy_errors(self, case: str, j: int) -> np.ndarray:
+        """numpy's own: the restatement's float64 value, rounded to the statement's dtype."""
+        if (case, j) not in self._np_err:
+            with np.errstate(all="ignore"):
+                self._np_err[case, j] = self.errors(case, j, self.numpy_out[case][j].astype(self.dtype))
+        return self._np_err[case, j]
+
+    def numpy_worst(self, cls: str, case: str | None = None, group: str | None = None) -> float:
+        """numpy's worst finite error over the heights of a class, on one case, one group of cases, or all."""
+        worst = 0.0
+        for name in ([case] if case else [c for c in self.cases if group in (None, CASE_GROUP[c])]):
+            for j, (_, c) in enumerate(self.heights):
+                if c == cls:
+                    e = self.numpy_errors(name, j)
+                    e = e[np.isfinite(e)]
+                    worst = max(worst, float(e.max()) if e.size else 0.0)
+        return worst
+
+
+def column_statement(dtype, n_lev: int) -> ColumnStatement:
+    key = ("column", np.dtype(dtype).name, n_lev)
+    if key not in _CACHE:
+        _CACHE[key] = ColumnStatement(dtype, n_lev)
+    return _CACHE[key]

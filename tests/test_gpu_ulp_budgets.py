@@ -74,7 +74,11 @@ def budgets(dtype) -> dict:
 # composed statements: an absolute ceiling per operator (ulps; the direction of xy_to_polar in ulps of 360 degrees), above numpy's own
 # worst (tests/test_exact_statements.py pins it) by a margin, far below what a lost refinement step costs (2^-46 relative: ~100 ulps f64)
 CEILING = {"atan2_deg": 4.0, "xy_to_polar": 4.0, "r_to_d": 6.0, "d_to_r": 90.0, "q_to_r": 48.0, "r_to_q": 48.0, "q_to_r_level": 48.0,
-           "r_to_q_level": 48.0}
+           "r_to_q_level": 48.0,
+           # the two dewpoint forms of q_height.py: ceil(1.1 x + 0.1 + SLACK) of numpy's pinned worst x over both dtypes (the top of
+           # the window it is pinned in, plus the slack) — q_to_d: numpy 1.89 (float64) / 1.99 (float32) -> 5; d_to_q: numpy 23.69 /
+           # 39.15 -> 46
+           "q_to_d": 5.0, "d_to_q": 46.0}
 
 COMB = {  # statement -> (operator, flags, outputs)
     "cos_sin": (native.COMB_COS_SIN, 0, 2),
@@ -90,6 +94,8 @@ COMB = {  # statement -> (operator, flags, outputs)
     "r_to_q": (native.COMB_R_TO_Q, 0, 1),
     "q_to_r_level": (native.COMB_Q_TO_R, 0, 1),
     "r_to_q_level": (native.COMB_R_TO_Q, 0, 1),
+    "q_to_d": (native.COMB_Q_TO_D, 0, 1),
+    "d_to_q": (native.COMB_D_TO_Q, 0, 1),
 }
 LAYOUTS = [(COLUMNS, 0), (FIELDS, 0), (COLUMNS, 1), (FIELDS, 3)]  # (layout, padding of the pitch): the last two are not vector-aligned
 LAYOUT_IDS = ["columns", "fields", "columns-pitch+1", "fields-pitch+3"]
