@@ -8,6 +8,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 
 #include "../../include/atx.h"
 
@@ -50,6 +51,14 @@ constexpr int kXcds = 8;     // MI355X: 8 XCDs, private 4 MiB L2 each
 constexpr int64_t kStreamGrid = ATX_MAX_GRID;
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// f(std::true_type{}) or f(std::false_type{}): a run-time flag becomes a template argument of the launch inside f, and only the
+// combinations a caller spells out are instantiated.  Returns what f returns (the same type on both sides).
+template <typename F>
+static auto with_flag(bool flag, F&& f) {
+    if (flag) return f(std::true_type{});
+    return f(std::false_type{});
+}
 
 // ---- 16-byte vectors ----------------------------------------------------------
 template <typename T>

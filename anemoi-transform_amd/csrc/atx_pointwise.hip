@@ -509,13 +509,7 @@ pointwise_fields_rows_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t
 
 // ---- dispatch -----------------------------------------------------------------------------------------------------------------
 
-// f(std::true_type{}) or f(std::false_type{}): a run-time flag becomes a template argument of the launch inside f, and only the
-// combinations a caller spells out are instantiated.
-template <typename F>
-static void with_flag(bool flag, F&& f) {
-    if (flag) f(std::true_type{});
-    else f(std::false_type{});
-}
+// (with_flag: atx_common.hpp)
 template <typename F>
 static void with_trans_nt(bool trans, bool nt, F&& f) {
     with_flag(trans, [&](auto tr) { with_flag(nt, [&](auto n) { f(tr, n); }); });

@@ -1,4 +1,4 @@
-// Regrid kernels: precomputed index(+weight) gather over a stack of levels.
+// The C ABI of the gather: atx_regrid_ell / _batch / _ordered, atx_regrid_csr / _ordered, atx_check_indices, atx_set_tuning.
 //
 // Replaces, for all levels of a stack in ONE launch, the per-field statements
 //   R: filters/fields/regrid.py:380  data[..., self.nearest_grid_points]
@@ -6,17 +6,10 @@
 //   R: filters/fields/regrid.py:420  data[..., self.mask]
 // that the reference runs once per 2-D field in a Python loop (regrid.py:204-208).
 //
-// HBM-bound gather, no MFMA.  Design:
-//  * ATX_COLUMNS stacks, fixed k <= 4 without epilogue — the headline case — run the DIRECT kernel: one
-//    (target, 16-byte vector) item per lane, no shared memory, no barrier, no loop; consecutive lanes read consecutive
-//    16 B of one source column and write consecutive 16 B of the output.
-//  * epilogues and runtime k run the TILED kernel: a workgroup owns a tile of consecutive targets, stages their neighbour
-//    indices / weights (and the per-vector operator table) in LDS once, then sweeps the flattened (target, vector) items
-//    with up to 4 items per lane in flight; general CSR rows likewise from a staged slice of the CSR arrays.
-//  * workgroups are dealt to XCDs in contiguous ranges (xcd_tile) so neighbouring targets that share source columns share
-//    an L2; several stacks of one shape share a launch (grid.y = stack).
-//  * ATX_FIELDS stacks: lane = target, neighbour indices / weights live in registers and are reused for every level of
-//    the level chunk.
+// This file checks the arguments, range-checks the tables under ATX_VALIDATE, cuts a batch into launches of kMaxBatch stacks and
+// falls back to gather-then-program when a fused program does not fit in LDS.  The kernels (HBM-bound gathers, no MFMA; DESIGN.md
+// §3) are in atx_regrid_columns.inc and atx_regrid_fields.inc, instantiated per element type in atx_regrid_f32.hip /
+// atx_regrid_f64.hip and reached through regrid_ell_typed<T> / regrid_csr_typed<T> (atx_regrid_decl.hpp).
 #include <type_traits>
 
 #include "atx_common.hpp"
@@ -29,21 +22,8 @@ namespace atx {
 
 thread_local int g_tile_override = 0;  // tuning hook (atx_set_tuning): per calling thread, meant for benchmarks and tests (results never depend on it)
 
-__global__ void __launch_bounds__(kBlock)
-check_indices_kernel(const int32_t* __restrict__ idx, int64_t n, int64_t n_src, unsigned long long* n_bad) {
-    unsigned long long bad = 0;
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
-        const int64_t v = idx[i];
-        bad += (v < 0 || v >= n_src) ? 1u : 0u;
-    }
-    // wavefront (64-lane) shuffle reduction, then one atomic per wave
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) bad += __shfl_down(bad, off, kWave);
-    if ((threadIdx.x & (kWave - 1)) == 0 && bad) atomicAdd(n_bad, bad);
-}
-
-// The same count with a lower bound of -1 allowed (ATX_ELL_PADDED marks absent entries with -1) and, for ordered traversals,
-// over a row table that must stay inside [0, n_tgt).
+// Entries of a table outside [lo, hi), counted on the device: atx_check_indices (lo = 0), and ATX_VALIDATE with a lower bound of -1
+// where ATX_ELL_PADDED marks absent entries with -1 and, for ordered traversals, over a row table that must stay inside [0, n_tgt).
 __global__ void __launch_bounds__(kBlock)
 check_range_kernel(const int32_t* __restrict__ idx, int64_t n, int64_t lo, int64_t hi, unsigned long long* n_bad) {
     unsigned long long bad = 0;
@@ -51,6 +31,7 @@ check_range_kernel(const int32_t* __restrict__ idx, int64_t n, int64_t lo, int64
         const int64_t v = idx[i];
         bad += (v < lo || v >= hi) ? 1u : 0u;
     }
+    // wavefront (64-lane) shuffle reduction, then one atomic per wave
 #pragma unroll
     for (int off = kWave / 2; off > 0; off >>= 1) bad += __shfl_down(bad, off, kWave);
     if ((threadIdx.x & (kWave - 1)) == 0 && bad) atomicAdd(n_bad, bad);
@@ -161,15 +142,15 @@ static int regrid_ell_common(const char* fn, const void* const* srcs, void* cons
             batch.src[i] = i < batch.n ? srcs[first + i] : nullptr;
             batch.out[i] = i < batch.n ? outs[first + i] : nullptr;
         }
-        int rc = dtype == ATX_F32
-            ? regrid_ell_typed<float>(batch, idx, w, n_tgt, k, (int)n_lev, src_pitch, out_pitch, layout, pad, epi, s)
-            : regrid_ell_typed<double>(batch, idx, w, n_tgt, k, (int)n_lev, src_pitch, out_pitch, layout, pad, epi, s);
+        auto run = [&](const Epilogue& e) {
+            if (dtype == ATX_F32) return regrid_ell_typed<float>(batch, idx, w, n_tgt, k, (int)n_lev, src_pitch, out_pitch, layout, pad, e, s);
+            return regrid_ell_typed<double>(batch, idx, w, n_tgt, k, (int)n_lev, src_pitch, out_pitch, layout, pad, e, s);
+        };
+        int rc = run(epi);
         if (rc == ATX_SPLIT_PROGRAM) {  // the fused tables do not fit in LDS: the plain gather, then the program on its output in place
             Epilogue plain;
             plain.tgt_rows = tgt_rows;
-            rc = dtype == ATX_F32
-                ? regrid_ell_typed<float>(batch, idx, w, n_tgt, k, (int)n_lev, src_pitch, out_pitch, layout, pad, plain, s)
-                : regrid_ell_typed<double>(batch, idx, w, n_tgt, k, (int)n_lev, src_pitch, out_pitch, layout, pad, plain, s);
+            rc = run(plain);
             for (int i = 0; i < batch.n && rc == ATX_OK; ++i)
                 rc = atx_pointwise_stack(batch.out[i], batch.out[i], n_tgt, n_lev, out_pitch, out_pitch, dtype, layout, prog, vec_prog, host_prog,
                                          n_stage, tgt_mask, stream);
@@ -265,7 +246,7 @@ extern "C" int atx_check_indices(const int32_t* idx, int64_t n, int64_t n_src, i
     if (n == 0) return ATX_OK;
     int64_t blocks = (n + kBlock - 1) / kBlock;
     if (blocks > kStreamGrid) blocks = kStreamGrid;
-    hipLaunchKernelGGL(check_indices_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, s, idx, n, n_src,
+    hipLaunchKernelGGL(check_range_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, s, idx, n, (int64_t)0, n_src,
                        reinterpret_cast<unsigned long long*>(n_bad));
     ATX_LAUNCH_CHECK("check_indices");
     return ATX_OK;

@@ -1,5 +1,5 @@
-// The regrid kernels and launchers (atx_regrid_kernels.inc) instantiated for float stacks; see atx_regrid_decl.hpp.
-#include "atx_regrid_kernels.inc"
+// The regrid kernels and launchers (atx_regrid_typed.inc and the two pieces it includes) instantiated for float stacks; see atx_regrid_decl.hpp.
+#include "atx_regrid_typed.inc"
 
 namespace atx {
 template int regrid_ell_typed<float>(const EllBatch& batch, const int32_t* idx, const void* w_, int64_t n_tgt, int k,

@@ -152,6 +152,16 @@ def lib_path() -> str:
     return os.environ.get("ATX_LIBRARY") or os.path.join(LIB_DIR, LIB_NAME)
 
 
+def open_library(path: str) -> ctypes.CDLL:
+    """A build of libatx.so with every prototype declared; raises if a symbol of the header is missing."""
+    handle = ctypes.CDLL(path)
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(handle, name)  # AttributeError if the symbol is not exported
+        fn.restype = restype
+        fn.argtypes = argtypes
+    return handle
+
+
 def load() -> ctypes.CDLL:
     """Load libatx.so (once) and declare every prototype.  Raises if it is absent."""
     global _lib
@@ -163,13 +173,16 @@ def load() -> ctypes.CDLL:
             f"{path} not found: the HIP extension is not built. Run `python -c \"import __graft_entry__ as g; "
             "g.build()\"` (hipcc --offload-arch=gfx950) — this package has no CPU fallback."
         )
-    handle = ctypes.CDLL(path)
-    for name, (restype, argtypes) in SIGNATURES.items():
-        fn = getattr(handle, name)  # AttributeError if the symbol is not exported
-        fn.restype = restype
-        fn.argtypes = argtypes
-    _lib = handle
-    return handle
+    _lib = open_library(path)
+    return _lib
+
+
+def use_library(handle: ctypes.CDLL | None) -> ctypes.CDLL | None:
+    """Route every wrapper of this module through ``handle`` (from ``open_library``) and return what was in use before; ``None``
+    goes back to ``load()``'s own.  For side-by-side timing of two builds in one process (tools/kernel_bench.py --lib)."""
+    global _lib
+    before, _lib = _lib, handle
+    return before
 
 
 def _raise(code: int, fn: str) -> None:

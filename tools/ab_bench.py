@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
 """Interleaved A/B timing of libatx builds on the bench workload (one process, one GPU).
 
-    python tools/ab_bench.py --libs base=anemoi-transform_amd/lib/libatx.so nt=anemoi-transform_amd/lib/variants/libatx_nt_store.so \
+    bash tools/build_variant.sh parent --rev HEAD~1
+    python tools/ab_bench.py --libs parent=anemoi-transform_amd/lib/variants/libatx_parent.so new=anemoi-transform_amd/lib/libatx.so \
         --tiles 0 16 24 --rounds 7 --cases k4f32 k1f32 k4f64
+
+(The gather's compile-time knobs are frozen, HISTORY.md: variants are builds of other commits.)
 
 Every (library, tile) pair is timed in every round, rounds interleaved
 (cdna_hip_programming.md §5.4 rule 24); reports median / min ms per launch and the
@@ -12,7 +15,6 @@ roofline fraction on algorithmic bytes.
 from __future__ import annotations
 
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -50,11 +52,7 @@ def main():
     libs = {}
     for spec in args.libs:
         name, path = spec.split("=", 1)
-        h = ctypes.CDLL(os.path.join(ROOT, path) if not os.path.isabs(path) else path)
-        for fn, (restype, argtypes) in native.SIGNATURES.items():
-            getattr(h, fn).restype = restype
-            getattr(h, fn).argtypes = argtypes
-        libs[name] = h
+        libs[name] = native.open_library(os.path.join(ROOT, path) if not os.path.isabs(path) else path)
 
     src_grid, tgt_grid = lookup(args.src_grid), lookup(args.tgt_grid)
     n_src, n_tgt = len(src_grid["latitudes"]), len(tgt_grid["latitudes"])

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Per-point programs made of RUNS of levels (several variables sharing a column): the by-value runs kernel (round 4) against the routes such
-programs took before (profiles/r04_runs_probe.log).  The per-point route is fixed now (float32 programs of two or more stages); the fused
-regrid epilogue still has its knob: build a variant with `bash tools/build_variant.sh noruns -DATX_EPI_RUNS=0` and run with
-ATX_LIBRARY=anemoi-transform_amd/lib/variants/libatx_noruns.so for the other side."""
+programs took before (profiles/r04_runs_probe.log).  Both routes are fixed now (per-point: float32 programs of two or more stages; the
+fused regrid epilogue: `ATX_EPI_RUNS` is frozen at 1 — HISTORY.md, "The gather kernels' A/B knobs, frozen"); the other side of the epilogue
+needs a `bash tools/build_variant.sh noruns --rev 402a730 -DATX_EPI_RUNS=0` build, run with
+ATX_LIBRARY=anemoi-transform_amd/lib/variants/libatx_noruns.so."""
 from __future__ import annotations
 
 import os

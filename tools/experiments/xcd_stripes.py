@@ -1,5 +1,8 @@
 #!/usr/bin/env python3
-"""Round-4 experiment: how the workgroups of the direct gather kernel are dealt to the XCDs (ATX_DIRECT_STRIPE builds), targets in NATURAL
+"""(The `ATX_DIRECT_STRIPE` / `ATX_LONG_ROW_STRIPE` knobs are frozen — HISTORY.md, "The gather kernels' A/B knobs, frozen"; the
+other sides need `tools/build_variant.sh NAME --rev 402a730 -D...` builds.)
+
+Round-4 experiment: how the workgroups of the direct gather kernel are dealt to the XCDs (ATX_DIRECT_STRIPE builds), targets in NATURAL
 order against the column-block order of round 3.  tools/experiments/tile_orders.py showed that only FULL-HEIGHT column blocks help long
 rows — bands of limited height and 2-D tiles do not — i.e. the gain is not vertical reuse in L2 but balance: with one contiguous range of
 targets per XCD (xcd_tile) the XCDs that hold polar rows (every source column shared by many targets) finish early and the equatorial

@@ -50,6 +50,11 @@ def main():
                     "to end beside the reference's statement in pandas on this host); --only-obs runs them after its own rows")
     ap.add_argument("--only-pointwise", action="store_true", help="only the per-point, mask and reduction rows (atx_pointwise.hip, atx_mask.hip, "
                     "atx_reduce.hip), each with a checksum of what it computed on the seeded stack")
+    ap.add_argument("--only-regrid", action="store_true", help="only the gather rows (atx_regrid_columns.inc, atx_regrid_fields.inc), each with a "
+                    "checksum of what one call writes into a zeroed output stack")
+    ap.add_argument("--lib", nargs="+", default=[], metavar="NAME=PATH", help="with --only-regrid: time these builds of libatx.so side by side in "
+                    "one process, alternating, --rounds rounds (the first one is the reference)")
+    ap.add_argument("--rounds", type=int, default=8)
     args = ap.parse_args()
     graft.load_package()
     from anemoi_transform_amd import interp, native
@@ -354,6 +359,144 @@ def main():
         del f, g
         torch.cuda.empty_cache()
 
+    def regrid_rows(tdt, B, tag, x, idx, w, libs=None, rounds=1):
+        """The rows that run kernels of atx_regrid_columns.inc and atx_regrid_fields.inc, on the seeded stack `x`.  `digest` is the
+        checksum of what ONE call of the row writes into an output stack zeroed first (padding slots are never written).  With
+        `libs` ({name: handle}, the first one the reference): every library times every row in each of `rounds` rounds, one
+        process, after one round that is thrown away (code objects, clocks), the libraries alternating and taking turns to go
+        first; the per-round medians go to `<name>_ms` and the digests must agree.  (This mode keeps every plan alive until the end.)"""
+        from anemoi_transform_amd.gather import target_order_for
+
+        rows = []
+
+        def row(name, plan, alg_bytes, note="", src=x, tile=0, **kw):
+            def call(out=None):
+                native.set_tuning(tile)
+                try:
+                    return plan.apply(src, out=out, **kw)
+                finally:
+                    native.set_tuning(0)
+
+            def one_call():
+                out = Stack.empty(plan.n_tgt, L, tdt, dev, src.layout, zero=True)
+                return call(out).data
+
+            if libs:
+                rows.append((name, call, one_call, alg_bytes, note))
+            else:  # measured here, so that a plan the caller does not keep is freed before the next one is built
+                record(name, timeit(call), alg_bytes, note)
+                res[name]["digest"] = checksum(one_call())
+
+        U4, U1 = int(np.unique(idx).size), int(np.unique(idx[:, 0]).size)
+        plan4 = GatherPlan(n_src, n_tgt, index=idx, weights=w)
+        plan1 = GatherPlan(n_src, n_tgt, index=idx[:, 0])
+        row(f"regrid_ell k=4 {tag} columns", plan4, bench.algorithmic_bytes(L, B, U4, n_tgt, 4), "incl. output allocation")
+        row(f"regrid_ell k=1 {tag} columns", plan1, bench.algorithmic_bytes(L, B, U1, n_tgt, 1))
+        keep = (np.arange(idx.size) % 9 != 0).reshape(idx.shape)
+        indptr = np.concatenate([[0], np.cumsum(keep.sum(axis=1))])
+        csr = GatherPlan(n_src, n_tgt, csr=(w[keep], idx[keep], indptr))
+        nnz = int(keep.sum())
+        csr_bytes = L * B * (int(np.unique(idx[keep]).size) + n_tgt) + nnz * (4 + B) + 4 * n_tgt
+        row(f"regrid_csr ragged(3-4) {tag} columns", csr, csr_bytes, "general CSR kernel")
+        padded = GatherPlan.from_matrix(dict(matrix_data=w[keep], matrix_indices=idx[keep], matrix_indptr=indptr, matrix_shape=(n_tgt, n_src)))
+        assert padded.padded
+        row(f"regrid ragged(3-4) as padded fixed-k {tag}", padded, csr_bytes, "what regrid(matrix=...) uses for short ragged rows")
+        tile = 16 if B == 4 else 8  # what the tiled kernels' heuristic picks at 137 levels
+        row(f"regrid_csr ragged(3-4) {tag} columns, TILED kernel", csr, csr_bytes, "round 1's kernel (LDS-staged CSR slice)", tile=tile)
+        # long rows: 16 nearest neighbours, and the same with entries dropped (rows of 9-16)
+        idx16, w16 = interp.knn_inverse_distance(src_grid, tgt_grid, k=16, device=True, ties="index")
+        U16 = int(np.unique(idx16).size)
+        blocks16, blocks12 = (target_order_for(tgt_grid["latitudes"], tgt_grid["longitudes"], k) for k in (16, 12))
+        bytes16 = bench.algorithmic_bytes(L, B, U16, n_tgt, 16)
+        row(f"regrid_ell k=16 {tag} columns", GatherPlan(n_src, n_tgt, index=idx16, weights=w16), bytes16,
+            "compile-time k = 16 on the direct kernel; targets in natural order, workgroups dealt to the XCDs in stripes (round 4)")
+        row(f"regrid_ell k=16 {tag} columns, targets in column blocks", GatherPlan(n_src, n_tgt, index=idx16, weights=w16).order_targets(blocks16), bytes16,
+            "what regrid(matrix=...) does for k >= 5 on large output grids (atx_regrid_ell_ordered; same bits)")
+        rng16 = np.random.default_rng(16)
+        keep16 = rng16.random(idx16.shape) < 0.75
+        keep16[:, :9] = True
+        indptr16 = np.concatenate([[0], np.cumsum(keep16.sum(axis=1))])
+        csr16_tables = (w16[keep16], idx16[keep16], indptr16)
+        csr16 = GatherPlan(n_src, n_tgt, csr=csr16_tables)
+        nnz16 = int(keep16.sum())
+        csr16_bytes = L * B * (int(np.unique(idx16[keep16]).size) + n_tgt) + nnz16 * (4 + B) + 4 * n_tgt
+        row(f"regrid_csr rows of 9-16 {tag} columns", csr16, csr16_bytes, "general CSR, direct kernel")
+        row(f"regrid_csr rows of 9-16 {tag} columns, TILED kernel", csr16, csr16_bytes, "round 1's kernel", tile=tile)
+        matrix16 = dict(matrix_data=csr16_tables[0], matrix_indices=csr16_tables[1], matrix_indptr=indptr16, matrix_shape=(n_tgt, n_src))
+        padded16 = GatherPlan.from_matrix(matrix16)
+        assert padded16.padded and padded16.k == 16
+        row(f"regrid rows of 9-16 as padded fixed-k {tag}", padded16, csr16_bytes, "what regrid(matrix=...) uses for ragged rows up to 16 entries")
+        row(f"regrid rows of 9-16 as padded fixed-k {tag}, targets in column blocks", GatherPlan.from_matrix(matrix16).order_targets(blocks16), csr16_bytes,
+            "the same in the order the regrid filter's policy picks on large output grids")
+        row(f"regrid_csr rows of 9-16 {tag} columns, targets in column blocks", GatherPlan(n_src, n_tgt, csr=csr16_tables).order_targets(blocks12), csr16_bytes,
+            "what regrid(matrix=...) does for long ragged rows on large output grids (atx_regrid_csr_ordered; same bits)")
+        del csr16, padded16
+        # coarsening by box averages (a conservative-style matrix): every 1-degree cell averages the ~200 O1280 points inside it
+        one = lookup([1.0, 1.0])
+        n_one = len(one["latitudes"])
+        cell = (np.rint(90.0 - src_grid["latitudes"]).astype(np.int64) * 360 + np.mod(np.rint(src_grid["longitudes"]).astype(np.int64), 360))
+        order_b = np.argsort(cell, kind="stable")
+        counts_b = np.bincount(cell, minlength=n_one)
+        indptr_b = np.concatenate([[0], np.cumsum(counts_b)])
+        data_b = (1.0 / np.maximum(counts_b, 1))[cell[order_b]]
+        box_bytes = L * B * (n_src + n_one) + n_src * (4 + B) + 4 * n_one
+        row(f"regrid_csr box average O1280->1deg {tag} (rows of ~{int(counts_b.mean())})", GatherPlan(n_src, n_one, csr=(data_b, order_b.astype(np.int32), indptr_b)),
+            box_bytes, "general CSR, every source column read once")
+        prog = native.level_program([[(native.OP_MUL, 0, 9.80665, 0.0)] * L, [(native.OP_AFFINE, 0, 1.0, -273.15)] * L], dev)
+        row(f"regrid_ell k=4 {tag} + 2-stage epilogue", plan4, bench.algorithmic_bytes(L, B, U4, n_tgt, 4), "fused regrid -> orog_to_z -> rescale, every level",
+            prog=prog, n_stage=2)
+        cp = (native.OP_COPY, 0, 0.0, 0.0)
+        prog5 = native.level_program([[cp] * (L - 1) + [(native.OP_MUL, 0, 9.80665, 0.0)], [(native.OP_AFFINE, 0, 1.0, -273.15)] * (L - 1) + [cp]], dev)
+        row(f"regrid_ell k=4 {tag} + config-5 epilogue", plan4, bench.algorithmic_bytes(L, B, U4, n_tgt, 4),
+            "136 levels convert, 1 level orog_to_z: operators by value, two pieces", prog=prog5, n_stage=2)
+        # ---- regrid on field-major
+        f = Stack.empty(n_src, L, tdt, dev, FIELDS)
+        native.relayout(x.data, f.data, n_pts=n_src, n_lev=L, src_pitch=x.pitch, dst_pitch=f.pitch, src_layout=COLUMNS, dst_layout=FIELDS)
+        row(f"regrid_ell k=4 {tag} fields", plan4, bench.algorithmic_bytes(L, B, U4, n_tgt, 4), src=f)
+
+        if not libs:
+            return
+        times = {(name, lib): [] for name, *_ in rows for lib in libs}
+        before = native.use_library(None)
+        for r in range(rounds + 1):
+            for lib in (list(libs) if r % 2 else list(libs)[::-1]):
+                native.use_library(libs[lib])
+                for name, call, *_ in rows:
+                    ms = timeit(call)
+                    if r:  # round 0 warms up
+                        times[name, lib].append(ms)
+        for name, call, one_call, alg_bytes, note in rows:
+            digests = {}
+            for lib, handle in libs.items():
+                native.use_library(handle)
+                digests[lib] = checksum(one_call())
+            ref, *others = libs
+            lo, hi = min(times[name, ref]), max(times[name, ref])
+            res[name] = {"algorithmic_bytes": alg_bytes, "note": note, "digest": digests[ref], "digests_equal": len(set(digests.values())) == 1}
+            line = f"{name:74s}"
+            for lib in libs:
+                med = float(np.median(times[name, lib]))
+                res[name][f"{lib}_ms"] = times[name, lib]
+                res[name][f"{lib}_median_ms"] = med
+                line += f" {lib} {med:8.4f}"
+            for lib in others:
+                med = res[name][f"{lib}_median_ms"]
+                res[name][f"{lib}_minus_{ref}_pct"] = 100.0 * (med / res[name][f"{ref}_median_ms"] - 1.0)
+                res[name][f"{lib}_within_{ref}_spread"] = bool(lo <= med <= hi)
+                line += f"  {res[name][f'{lib}_minus_{ref}_pct']:+5.2f} %  in [{lo:.4f}, {hi:.4f}]: {lo <= med <= hi}"
+            print(line + ("" if res[name]["digests_equal"] else "  DIGESTS DIFFER"), flush=True)
+        native.use_library(before)
+
+    if args.only_regrid:
+        libs = {name: native.open_library(os.path.abspath(path)) for name, path in (spec.split("=", 1) for spec in args.lib)}
+        idx, w = interp.knn_inverse_distance(src_grid, tgt_grid, k=4)
+        for tdt, B, tag in ((torch.float32, 4, "f32"), (torch.float64, 8, "f64")):
+            regrid_rows(tdt, B, tag, bench.synth_stack(src_grid, L, tdt, dev, 0, COLUMNS), idx, w, libs, args.rounds)
+            torch.cuda.empty_cache()
+        if args.out:
+            json.dump(res, open(args.out, "w"), indent=1)
+        return
+
     if args.only_pointwise:
         for tdt, B, tag in ((torch.float32, 4, "f32"), (torch.float64, 8, "f64")):
             pointwise_rows(tdt, B, tag)
@@ -393,78 +536,7 @@ def main():
         vertical_rows(tdt, B, tag)
         rotate_rows(tdt, B, tag)
         x = bench.synth_stack(src_grid, L, tdt, dev, 0, COLUMNS)
-        U4, U1 = int(np.unique(idx).size), int(np.unique(idx[:, 0]).size)
-        # ---- regrid variants
-        plan4 = GatherPlan(n_src, n_tgt, index=idx, weights=w)
-        plan1 = GatherPlan(n_src, n_tgt, index=idx[:, 0])
-        record(f"regrid_ell k=4 {tag} columns", timeit(lambda: plan4.apply(x)), bench.algorithmic_bytes(L, B, U4, n_tgt, 4), "incl. output allocation")
-        record(f"regrid_ell k=1 {tag} columns", timeit(lambda: plan1.apply(x)), bench.algorithmic_bytes(L, B, U1, n_tgt, 1))
-        keep = (np.arange(idx.size) % 9 != 0).reshape(idx.shape)
-        indptr = np.concatenate([[0], np.cumsum(keep.sum(axis=1))])
-        csr = GatherPlan(n_src, n_tgt, csr=(w[keep], idx[keep], indptr))
-        nnz = int(keep.sum())
-        csr_bytes = L * B * (int(np.unique(idx[keep]).size) + n_tgt) + nnz * (4 + B) + 4 * n_tgt
-        record(f"regrid_csr ragged(3-4) {tag} columns", timeit(lambda: csr.apply(x)), csr_bytes, "general CSR kernel")
-        padded = GatherPlan.from_matrix(dict(matrix_data=w[keep], matrix_indices=idx[keep], matrix_indptr=indptr, matrix_shape=(n_tgt, n_src)))
-        assert padded.padded
-        record(f"regrid ragged(3-4) as padded fixed-k {tag}", timeit(lambda: padded.apply(x)), csr_bytes, "what regrid(matrix=...) uses for short ragged rows")
-        tile = 16 if B == 4 else 8  # what the tiled kernels' heuristic picks at 137 levels
-        native.set_tuning(tile)
-        record(f"regrid_csr ragged(3-4) {tag} columns, TILED kernel", timeit(lambda: csr.apply(x)), csr_bytes, "round 1's kernel (LDS-staged CSR slice)")
-        native.set_tuning(0)
-        # long rows: 16 nearest neighbours, and the same with entries dropped (rows of 9-16)
-        idx16, w16 = interp.knn_inverse_distance(src_grid, tgt_grid, k=16, device=True, ties="index")
-        U16 = int(np.unique(idx16).size)
-        plan16 = GatherPlan(n_src, n_tgt, index=idx16, weights=w16)
-        bytes16 = bench.algorithmic_bytes(L, B, U16, n_tgt, 16)
-        record(f"regrid_ell k=16 {tag} columns", timeit(lambda: plan16.apply(x)), bytes16, "compile-time k = 16 on the direct kernel; targets in natural order, workgroups dealt to the XCDs in stripes (round 4)")
-        from anemoi_transform_amd.gather import target_order_for
-
-        plan16.order_targets(target_order_for(tgt_grid["latitudes"], tgt_grid["longitudes"], 16))
-        record(f"regrid_ell k=16 {tag} columns, targets in column blocks", timeit(lambda: plan16.apply(x)), bytes16,
-               "what regrid(matrix=...) does for k >= 5 on large output grids (atx_regrid_ell_ordered; same bits)")
-        rng16 = np.random.default_rng(16)
-        keep16 = rng16.random(idx16.shape) < 0.75
-        keep16[:, :9] = True
-        indptr16 = np.concatenate([[0], np.cumsum(keep16.sum(axis=1))])
-        csr16 = GatherPlan(n_src, n_tgt, csr=(w16[keep16], idx16[keep16], indptr16))
-        nnz16 = int(keep16.sum())
-        csr16_bytes = L * B * (int(np.unique(idx16[keep16]).size) + n_tgt) + nnz16 * (4 + B) + 4 * n_tgt
-        record(f"regrid_csr rows of 9-16 {tag} columns", timeit(lambda: csr16.apply(x)), csr16_bytes, "general CSR, direct kernel")
-        native.set_tuning(tile)
-        record(f"regrid_csr rows of 9-16 {tag} columns, TILED kernel", timeit(lambda: csr16.apply(x)), csr16_bytes, "round 1's kernel")
-        native.set_tuning(0)
-        padded16 = GatherPlan.from_matrix(dict(matrix_data=w16[keep16], matrix_indices=idx16[keep16], matrix_indptr=indptr16, matrix_shape=(n_tgt, n_src)))
-        assert padded16.padded and padded16.k == 16
-        record(f"regrid rows of 9-16 as padded fixed-k {tag}", timeit(lambda: padded16.apply(x)), csr16_bytes, "what regrid(matrix=...) uses for ragged rows up to 16 entries")
-        padded16.order_targets(target_order_for(tgt_grid["latitudes"], tgt_grid["longitudes"], 16))
-        record(f"regrid rows of 9-16 as padded fixed-k {tag}, targets in column blocks", timeit(lambda: padded16.apply(x)), csr16_bytes,
-               "the same in the order the regrid filter's policy picks on large output grids")
-        del padded16
-        csr16.order_targets(target_order_for(tgt_grid["latitudes"], tgt_grid["longitudes"], 12))
-        record(f"regrid_csr rows of 9-16 {tag} columns, targets in column blocks", timeit(lambda: csr16.apply(x)), csr16_bytes,
-               "what regrid(matrix=...) does for long ragged rows on large output grids (atx_regrid_csr_ordered; same bits)")
-        del plan16, csr16, idx16, w16
-        # coarsening by box averages (a conservative-style matrix): every 1-degree cell averages the ~200 O1280 points inside it
-        one = lookup([1.0, 1.0])
-        n_one = len(one["latitudes"])
-        cell = (np.rint(90.0 - src_grid["latitudes"]).astype(np.int64) * 360 + np.mod(np.rint(src_grid["longitudes"]).astype(np.int64), 360))
-        order_b = np.argsort(cell, kind="stable")
-        counts_b = np.bincount(cell, minlength=n_one)
-        indptr_b = np.concatenate([[0], np.cumsum(counts_b)])
-        data_b = (1.0 / np.maximum(counts_b, 1))[cell[order_b]]
-        box = GatherPlan(n_src, n_one, csr=(data_b, order_b.astype(np.int32), indptr_b))
-        box_bytes = L * B * (n_src + n_one) + n_src * (4 + B) + 4 * n_one
-        record(f"regrid_csr box average O1280->1deg {tag} (rows of ~{int(counts_b.mean())})", timeit(lambda: box.apply(x)), box_bytes,
-               "general CSR, every source column read once")
-        del box
-        prog = native.level_program([[(native.OP_MUL, 0, 9.80665, 0.0)] * L, [(native.OP_AFFINE, 0, 1.0, -273.15)] * L], dev)
-        record(f"regrid_ell k=4 {tag} + 2-stage epilogue", timeit(lambda: plan4.apply(x, prog=prog, n_stage=2)),
-               bench.algorithmic_bytes(L, B, U4, n_tgt, 4), "fused regrid -> orog_to_z -> rescale, every level")
-        cp = (native.OP_COPY, 0, 0.0, 0.0)
-        prog5 = native.level_program([[cp] * (L - 1) + [(native.OP_MUL, 0, 9.80665, 0.0)], [(native.OP_AFFINE, 0, 1.0, -273.15)] * (L - 1) + [cp]], dev)
-        record(f"regrid_ell k=4 {tag} + config-5 epilogue", timeit(lambda: plan4.apply(x, prog=prog5, n_stage=2)),
-               bench.algorithmic_bytes(L, B, U4, n_tgt, 4), "136 levels convert, 1 level orog_to_z: operators by value, two pieces")
+        regrid_rows(tdt, B, tag, x, idx, w)
         # ---- per-point
         y = x.new_like()
         record(f"(ceiling) torch copy_ of the stack {tag}", timeit(lambda: y.data.copy_(x.data)), 2 * x.data.numel() * B,
@@ -540,8 +612,6 @@ def main():
         record(f"select 1 of {L} levels {tag}", timeit(lambda: native.select_levels(x.data, one_lev.data, [77], n_pts=n_src, n_src_lev=L, src_pitch=x.pitch,
                dst_pitch=one_lev.pitch, layout=COLUMNS)), 2 * n_src * B, "one field out of a column stack: a 64-byte sector per point is the least that can move")
         del half, one_lev
-        # ---- regrid on field-major
-        record(f"regrid_ell k=4 {tag} fields", timeit(lambda: plan4.apply(f)), bench.algorithmic_bytes(L, B, U4, n_tgt, 4))
         del x, y, z, f
         torch.cuda.empty_cache()
 
