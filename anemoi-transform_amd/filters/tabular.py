@@ -1,10 +1,16 @@
-"""superob / assign_to_grid / irregular_to_grid: where a table of observations enters the field path (R: filters/tabular/).
+"""Tables of observations: where they enter the field path, and the per-row columns recipes derive on the way (R: filters/tabular/).
 
 ``superob`` thins a raw table to one row per grid cell, time slot and report type (per-group means by pandas' rule:
 ``obs.group_means`` -> ``atx_obs_group_mean``); ``assign_to_grid`` adds the nearest grid point of every observation to the table;
 ``irregular_to_grid`` turns the table into one gridded field per target time and column, NaN where nothing was observed.  The fields it returns are levels of ONE stack in
 HBM (``obs.grid_observations``: ``atx_obs_best_per_cell`` + ``atx_obs_fill_stack``), so a following ``regrid`` or per-point
 filter finds them resident.
+
+Between those steps recipes add per-row derived columns: ``add_forcings`` (solar and calendar forcings, ``obs.forcings`` ->
+``atx_obs_forcings``), ``add_azimuth`` and ``add_msg_angles`` (satellite viewing geometry, ``obs.view_angles`` ->
+``atx_obs_view_angles``) and ``radiance_to_brightness_temperature`` (the inverse Planck law for CrIS, ``obs.brightness_temperature`` ->
+``atx_obs_planck_bt``).  Each is transcendental arithmetic over every row — one launch over columns that stay in HBM, so a chain such
+as ``superob | add_forcings | irregular_to_grid`` keeps a table of device tensors resident from raw rows to the stack.
 
 A table is a pandas DataFrame (when pandas can be imported) or a plain mapping ``name -> 1-D array / device tensor``.
 
@@ -13,10 +19,14 @@ Deviations from the reference, each said once when it first matters (``core.say_
     labels would duplicate rows there.
   * ``spatial_index`` must be an integer column, or a float column whose non-missing entries are whole numbers; missing entries
     are dropped, as ``groupby`` drops them.
-  * value columns must be numeric: they are read as float64, as the reference's float64 grids read them.
+  * value columns must be numeric: they are read as float64, as the reference's float64 grids read them.  The per-row filters read
+    latitude, longitude, spacecraft position and radiance columns as float64 as well (the reference would compute a float32 column
+    in float32).
   * ``"h<nside>"`` grids need healpy and raise ``NotImplementedError``.
   * ``superob``: the caller's table is not modified, and rows of equal ``date`` keep the first-appearance order of their groups.
-The other tabular filters of the reference (pandas bookkeeping with no field output) are not built: DESIGN.md §7.
+  * ``add_azimuth``: the caller's table is not modified (the reference writes the new column into its argument).
+The other tabular filters of the reference (row-dropping, renaming and masking bookkeeping in pandas, with no arithmetic for the
+device to do) are not built: DESIGN.md §7.
 """
 
 from __future__ import annotations
@@ -445,6 +455,168 @@ def _superob_result(table: _Table, result: dict[str, Any], labels: torch.Tensor 
     return out
 
 
+# ---- per-row derived columns ---------------------------------------------------------------------------------------------------------
+def _table_device(table: Any) -> tuple[bool, torch.device]:
+    """``(resident, device)``: whether any column of the table is a device tensor, and the device the launch runs on."""
+    from .. import stack as _stack
+
+    tensors = [v for v in (table[c] for c in _column_names(table)) if isinstance(v, torch.Tensor)]
+    return bool(tensors), next((v.device for v in tensors if v.is_cuda), None) or _stack.device()
+
+
+def _with_columns(table: Any, added: dict[str, torch.Tensor], resident: bool) -> Any:
+    """The table with the device rows ``added``, in the kind of the input and never the caller's object: ``DataFrame.assign`` for a
+    DataFrame; for a mapping a new dict, of device tensors if any input column was one, else with the new columns as numpy arrays."""
+    if _is_dataframe(table):
+        return table.assign(**{name: col.cpu().numpy() for name, col in added.items()})
+    return {**table, **{name: (col if resident else col.cpu().numpy()) for name, col in added.items()}}
+
+
+class AddForcings(Filter):
+    """Adds solar and calendar forcing columns to the table (R: filters/tabular/add_forcings.py:19-127,
+    support/compute_forcings.py:14-87).
+
+    ``columns``: names from ``cos_julian_day``, ``sin_julian_day``, ``cos_sza``, ``sin_local_time``, ``cos_local_time``,
+    ``cos_latitude``, ``sin_latitude``, ``cos_longitude``, ``sin_longitude``; anything else raises ``ValueError``.  The table needs
+    ``date`` (datetime64 or int64 nanoseconds), ``latitude`` and ``longitude``.  The julian day counts WHOLE days and seconds from
+    1 January of the date's year (``Timedelta.days`` / ``.seconds``); NaT gives NaN in every date-dependent column; ``cos_sza`` is
+    clipped at 0.  One launch (``obs.forcings`` -> ``atx_obs_forcings``) whatever the number of columns.
+
+    Deviation: latitude and longitude are read as float64."""
+
+    SUPPORTED_FORCINGS = set(obs.FORCINGS)
+
+    def __init__(self, *, columns: list[str]) -> None:
+        if not set(columns).issubset(self.SUPPORTED_FORCINGS):
+            raise ValueError(f"Unknown columns requested: {set(columns) - self.SUPPORTED_FORCINGS}")
+        self.columns = columns
+
+    def __repr__(self) -> str:
+        return f"AddForcings({list(self.columns)})"
+
+    def forward(self, table: Any) -> Any:
+        _require(table, ["date", "latitude", "longitude"])
+        resident, dev = _table_device(table)
+        return _with_columns(table, obs.forcings(table["date"], table["latitude"], table["longitude"], list(self.columns), dev=dev), resident)
+
+
+class AddAzimuth(Filter):
+    """Adds the viewing azimuth of a spacecraft whose position every row carries (R: filters/tabular/add_azimuth.py:19-62,
+    support/sat_view_angles.py:52-97).  ``azimuth``, ``spacecraft_latitude`` and ``spacecraft_longitude`` name the columns; a missing
+    spacecraft column raises ``ValueError``.  Exactly 0.0 where the spacecraft is within 0.00001 degrees in latitude OR longitude
+    (a NaN included).  ``obs.view_angles`` -> ``atx_obs_view_angles``.
+
+    Deviations: the caller's table is not modified (the reference writes the column into its argument); the four columns are read
+    as float64."""
+
+    def __init__(self, *, azimuth: str = "azimuth", spacecraft_latitude: str = "spacecraft_latitude",
+                 spacecraft_longitude: str = "spacecraft_longitude") -> None:
+        self.azimuth = azimuth
+        self.spacecraft_latitude = spacecraft_latitude
+        self.spacecraft_longitude = spacecraft_longitude
+        say_once(LOG, (type(self), "deviations"), "add_azimuth: the caller's table is not modified (the reference writes the azimuth "
+                 "column into its argument), and the position columns are read as float64", level=logging.INFO)
+
+    def __repr__(self) -> str:
+        return f"AddAzimuth({self.azimuth!r})"
+
+    def forward(self, table: Any) -> Any:
+        _require(table, [self.spacecraft_latitude, self.spacecraft_longitude])
+        _require(table, ["latitude", "longitude"])
+        resident, dev = _table_device(table)
+        angles = obs.view_angles(table["latitude"], table["longitude"], table[self.spacecraft_latitude], table[self.spacecraft_longitude],
+                                 azimuth=True, zenith=False, dev=dev)
+        return _with_columns(table, {self.azimuth: angles["azimuth"]}, resident)
+
+
+class AddMSGAngles(Filter):
+    """Adds the Meteosat viewing azimuth and / or zenith (R: filters/tabular/add_msg_angles.py:22-81,
+    support/sat_view_angles.py:17-132).  ``angle``: ``"azimuth"``, ``"zenith"`` or ``"both"`` (anything else: ``ValueError``);
+    ``azimuth``, ``zenith`` and ``satellite_id`` name the columns; a table without the id column raises ``ValueError``.
+
+    The sub-satellite point comes from the id and the date (``obs.meteosat_position``): latitude 0; longitude 41.5 for id 55 after
+    2016-10-20, 45.5 for 56 after 2022-05-08, -3.4 for 57 before 2013-01-24 and for 70 before 2015-12-01 (strict comparisons), 0
+    otherwise — stored IN THE DTYPE OF THE ID COLUMN, as the reference's ``np.zeros_like(satids)`` stores it: with integer ids, which
+    the reference's own tests use, the longitudes are 41 / 45 / -3, and its expected literals depend on it.  The table is built with
+    torch on the device; the angles are ``obs.view_angles`` -> ``atx_obs_view_angles``.
+
+    Deviation: latitude, longitude and the sub-satellite table are read as float64 by the kernel (a float32 id column gives float32
+    sub-satellite longitudes first, as the reference's does)."""
+
+    def __init__(self, *, angle: str = "both", azimuth: str = "azimuth", zenith: str = "zenith", satellite_id: str = "satellite_id") -> None:
+        if angle not in ("azimuth", "zenith", "both"):
+            raise ValueError(f"Invalid angle: {angle}. Must be 'azimuth', 'zenith' or 'both'.")
+        self.angle = ("azimuth", "zenith") if angle == "both" else (angle,)
+        self.azimuth = azimuth
+        self.zenith = zenith
+        self.satellite_id = satellite_id
+
+    def __repr__(self) -> str:
+        return f"AddMSGAngles({'+'.join(self.angle)})"
+
+    def forward(self, table: Any) -> Any:
+        if self.satellite_id not in _column_names(table):
+            raise ValueError(f"DataFrame must contain a column '{self.satellite_id}' for MSG angles calculation.")
+        _require(table, ["latitude", "longitude", "date"])
+        resident, dev = _table_device(table)
+        sat_lat, sat_lon = obs.meteosat_position(table[self.satellite_id], table["date"], dev=dev)
+        angles = obs.view_angles(table["latitude"], table["longitude"], sat_lat, sat_lon, azimuth="azimuth" in self.angle,
+                                 zenith="zenith" in self.angle, dev=dev)
+        return _with_columns(table, {getattr(self, name): angles[name] for name in self.angle}, resident)
+
+
+class RadianceToBrightnessTemperature(Filter):
+    """CrIS NSR / FSR radiances in mW/(m^2 sr cm^-1) to brightness temperatures in K
+    (R: filters/tabular/radiance_to_brightness_temperature.py:20-120).  Every column whose name starts with ``input_prefix`` and ends
+    in ``_<channel number>`` is replaced, in place in the column order, by ``<output_prefix><channel number>``; no such column raises
+    ``ValueError``, and so does a ``mode`` other than ``"cris_fsr"`` / ``"cris_nsr"``.  The columns are sorted by channel number and
+    stacked into one ``[n_ch, n]`` block, converted in ONE launch (``obs.brightness_temperature`` -> ``atx_obs_planck_bt``) and handed
+    back row by row.  A channel outside the bands of the mode has no wavenumber: its column comes back NaN.  Radiances of zero,
+    negative or below 1e-298 are floored (``maximum(R * 1e-2, 1e-300)``).
+
+    Deviation: radiance columns are read as float64."""
+
+    def __init__(self, *, mode: str, input_prefix: str = "obsvalue_rad_", output_prefix: str = "obsvalue_rawbt_") -> None:
+        if mode not in ("cris_fsr", "cris_nsr"):
+            raise ValueError(f"Invalid mode: {mode}. Must be 'cris_fsr' or 'cris_nsr'.")
+        self.mode = mode
+        self.input_prefix = input_prefix
+        self.output_prefix = output_prefix
+
+    def __repr__(self) -> str:
+        return f"RadianceToBrightnessTemperature({self.mode!r})"
+
+    def forward(self, table: Any) -> Any:
+        import re
+
+        names = _column_names(table)
+        cols = [c for c in names if isinstance(c, str) and c.startswith(self.input_prefix)]
+        if not cols:
+            raise ValueError(f"No columns starting with '{self.input_prefix}' found in DataFrame.")
+        found = [re.search(r"_(\d+)$", c) for c in cols]
+        if not all(found):
+            raise ValueError(f"columns without a trailing channel number: {[c for c, m in zip(cols, found) if not m]}")
+        # R: :89-94 — sorted by channel, so that wavenumbers and columns line up
+        chans = np.array([int(m.group(1)) for m in found], dtype=np.int64)
+        order = np.argsort(chans, kind="stable")
+        cols, chans = [cols[i] for i in order], chans[order]
+        resident, dev = _table_device(table)
+        radiance = torch.stack([obs.float_column(table[c], dev) for c in cols])
+        tb = obs.brightness_temperature(radiance, obs.cris_wavenumbers(chans, self.mode), out=radiance)
+        renamed = {c: f"{self.output_prefix}{ch}" for c, ch in zip(cols, chans)}
+        if _is_dataframe(table):
+            out = table.copy()
+            for j, c in enumerate(cols):
+                out[c] = tb[j].cpu().numpy()
+            return out.rename(columns=renamed)
+        row = {c: j for j, c in enumerate(cols)}
+        return {renamed.get(c, c): ((tb[row[c]] if resident else tb[row[c]].cpu().numpy()) if c in row else table[c]) for c in names}
+
+
 filter_registry.register("irregular_to_grid", IrregularToGrid)
 filter_registry.register("assign_to_grid", AssignToGrid)
 filter_registry.register("superob", SuperOb)
+filter_registry.register("add_forcings", AddForcings)
+filter_registry.register("add_azimuth", AddAzimuth)
+filter_registry.register("add_msg_angles", AddMSGAngles)
+filter_registry.register("radiance_to_brightness_temperature", RadianceToBrightnessTemperature)

@@ -13,7 +13,7 @@ from __future__ import annotations
 import ctypes
 import os
 import threading
-from ctypes import POINTER, c_char_p, c_double, c_int, c_int32, c_int64, c_size_t, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_int, c_int32, c_int64, c_size_t, c_uint32, c_void_p
 from typing import Any
 
 import numpy as np
@@ -113,6 +113,9 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
         c_int, [c_void_p, c_int64, c_int32, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p],
     ),
     "atx_obs_group_argmin": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+    "atx_obs_forcings": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_uint32, c_void_p, c_int64, c_void_p]),
+    "atx_obs_view_angles": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_uint32, c_void_p, c_int64, c_void_p]),
+    "atx_obs_planck_bt": (c_int, [c_void_p, c_int64, c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "atx_mask_build": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_double, c_int, c_void_p]),
     "atx_mask_count": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
     "atx_mask_to_index_workspace": (c_size_t, [c_int64]),
@@ -512,6 +515,52 @@ def obs_group_argmin(distance, order, offsets, nearest) -> None:
     assert distance.dtype == torch.float64 and distance.is_contiguous() and nearest.dtype == torch.int32 and nearest.is_contiguous()
     assert nearest.numel() == n_groups
     _call("atx_obs_group_argmin", _ptr(distance), distance.numel(), _ptr(order), n_sel, _ptr(offsets), n_groups, _ptr(nearest), _stream())
+
+
+# the nine columns of atx_obs_forcings in the order of their mask bits (R: filters/tabular/add_forcings.py:51-61)
+FORCINGS = ("cos_julian_day", "sin_julian_day", "cos_sza", "sin_local_time", "cos_local_time", "cos_latitude", "sin_latitude",
+            "cos_longitude", "sin_longitude")
+VIEW_AZIMUTH, VIEW_ZENITH = 1, 2
+
+
+def _rows(*columns, n: int) -> None:
+    for c in columns:
+        assert c is None or (c.dtype == torch.float64 and c.is_contiguous() and c.numel() == n)
+
+
+def obs_forcings(date_ns, latitude, longitude, mask: int, out) -> None:
+    """``out`` (float64 ``[popcount(mask), n]``, rows may be pitched): the forcings whose bits ``mask`` holds (``FORCINGS`` order) of
+    the rows ``date_ns`` (int64 nanoseconds, NaT = INT64_MIN), ``latitude``, ``longitude`` (float64 degrees) — ``atx_obs_forcings``.
+    A column the mask does not need may be ``None``."""
+    n = out.shape[1]
+    _rows(latitude, longitude, n=n)
+    assert date_ns is None or (date_ns.dtype == torch.int64 and date_ns.is_contiguous() and date_ns.numel() == n)
+    assert out.dtype == torch.float64 and out.shape[0] == bin(int(mask)).count("1") and (out.stride(1) == 1 or n <= 1)
+    pitch = out.stride(0) if out.shape[0] > 1 else max(n, 1)
+    _call("atx_obs_forcings", _ptr(date_ns), _ptr(latitude), _ptr(longitude), n, int(mask), _ptr(out), pitch, _stream())
+
+
+def obs_view_angles(latitude, longitude, sat_latitude, sat_longitude, flags: int, out) -> None:
+    """``out`` (float64 ``[popcount(flags), n]``): the viewing azimuth (``VIEW_AZIMUTH``) and / or zenith (``VIEW_ZENITH``) in degrees,
+    azimuth first — ``atx_obs_view_angles``.  All four inputs float64 ``[n]`` in degrees."""
+    n = out.shape[1]
+    _rows(latitude, longitude, sat_latitude, sat_longitude, n=n)
+    assert out.dtype == torch.float64 and out.shape[0] == bin(int(flags)).count("1") and (out.stride(1) == 1 or n <= 1)
+    pitch = out.stride(0) if out.shape[0] > 1 else max(n, 1)
+    _call("atx_obs_view_angles", _ptr(latitude), _ptr(longitude), _ptr(sat_latitude), _ptr(sat_longitude), n, int(flags), _ptr(out), pitch,
+          _stream())
+
+
+def obs_planck_bt(radiance, a, b, out) -> None:
+    """``out[c, i] = b[c] / log1p(a[c] / max(radiance[c, i] * 1e-2, 1e-300))`` for float64 ``[n_ch, n]`` radiances (rows may be
+    pitched) and the per-channel tables ``a``, ``b`` (float64 ``[n_ch]``) — ``atx_obs_planck_bt``.  ``out is radiance`` is allowed."""
+    n_ch, n = radiance.shape
+    assert radiance.dtype == out.dtype == a.dtype == b.dtype == torch.float64 and tuple(out.shape) == (n_ch, n)
+    assert a.is_contiguous() and b.is_contiguous() and a.numel() == b.numel() == n_ch
+    assert (radiance.stride(1) == 1 and out.stride(1) == 1) or n <= 1
+    in_pitch = radiance.stride(0) if n_ch > 1 else max(n, 1)
+    out_pitch = out.stride(0) if n_ch > 1 else max(n, 1)
+    _call("atx_obs_planck_bt", _ptr(radiance), n, n_ch, in_pitch, _ptr(a), _ptr(b), _ptr(out), out_pitch, _stream())
 
 
 def mask_build(m, mask, *, n, stride=1, cmp, threshold=0.0) -> None:

@@ -15,6 +15,11 @@ The second half serves ``superob`` (R: filters/tabular/superob.py), which thins 
 ``superob_groups`` turn key columns into rows in group order (torch on the device: one stable sort), ``group_means`` is pandas'
 ``groupby().mean()`` bit for bit (``atx_obs_group_mean``: one Kahan sum per group and column in row order) and ``group_nearest`` its
 ``groupby()["distance"].idxmin()`` (``atx_obs_group_argmin``).
+
+The third part is the per-row derived columns that recipes put between those steps (R: filters/tabular/add_forcings.py, add_azimuth.py,
+add_msg_angles.py, radiance_to_brightness_temperature.py): ``forcings``, ``view_angles`` and ``brightness_temperature``, one launch each
+(``atx_obs_forcings``, ``atx_obs_view_angles``, ``atx_obs_planck_bt``) over columns that stay in HBM, and ``meteosat_position``, the
+sub-satellite table of ``add_msg_angles`` (torch on the device).
 """
 
 from __future__ import annotations
@@ -375,3 +380,115 @@ def group_nearest(distance: torch.Tensor, groups: Groups) -> torch.Tensor:
     if groups.n_groups:
         native.obs_group_argmin(distance.contiguous(), groups.order, groups.offsets, nearest)
     return nearest.to(torch.int64)
+
+
+# ---- per-row derived columns (R: filters/tabular/add_forcings.py, add_azimuth.py, add_msg_angles.py, radiance_to_brightness_temperature.py) ----
+FORCINGS = native.FORCINGS  # the nine names in the order of R: add_forcings.py:51-61, which is the order of the kernel's mask bits
+
+
+def float_column(column: Any, dev: torch.device) -> torch.Tensor:
+    """A numeric column as a contiguous float64 device row (a device tensor is used in place when it already is one)."""
+    if isinstance(column, torch.Tensor):
+        if column.dtype.is_complex or column.dtype == torch.bool:
+            raise ValueError(f"a numeric column is needed, got {column.dtype}")
+        return column.reshape(-1).to(device=dev, dtype=torch.float64).contiguous()
+    a = _host_array(column)
+    if a.dtype.kind not in "iuf":
+        raise ValueError(f"a numeric column is needed, got dtype {a.dtype}")
+    return _device(np.ascontiguousarray(a.reshape(-1), dtype=np.float64), dev)
+
+
+def forcings(date: Any, latitude: Any, longitude: Any, columns: Sequence[str], dev: torch.device | None = None) -> dict[str, torch.Tensor]:
+    """``{name: float64 device row}`` for the forcing names in ``columns`` (a subset of ``FORCINGS``), in the order given
+    (R: add_forcings.py:68-127, support/compute_forcings.py:14-87) — ONE launch of ``atx_obs_forcings``; julian day, hours since
+    midnight and the angles are computed once per row and shared by the outputs.  ``date``: datetimes or int64 nanoseconds (NaT gives
+    NaN in every date-dependent column); ``latitude`` / ``longitude`` in degrees, read as float64."""
+    unknown = set(columns) - set(FORCINGS)
+    if unknown:
+        raise ValueError(f"Unknown columns requested: {unknown}")
+    dev = _stack.device() if dev is None else dev
+    mask = 0
+    for name in columns:
+        mask |= 1 << FORCINGS.index(name)
+    if mask == 0:
+        return {}
+    lat, lon = float_column(latitude, dev), float_column(longitude, dev)
+    ns = _device(to_ns(date), dev)
+    if not ns.numel() == lat.numel() == lon.numel():
+        raise ValueError(f"columns differ in length: date {ns.numel()}, latitude {lat.numel()}, longitude {lon.numel()}")
+    wanted = [name for name in FORCINGS if mask >> FORCINGS.index(name) & 1]
+    out = torch.empty((len(wanted), ns.numel()), dtype=torch.float64, device=dev)
+    native.obs_forcings(ns, lat, lon, mask, out)
+    return {name: out[wanted.index(name)] for name in columns}
+
+
+def view_angles(latitude: Any, longitude: Any, sat_latitude: Any, sat_longitude: Any, *, azimuth: bool = True, zenith: bool = True,
+                dev: torch.device | None = None) -> dict[str, torch.Tensor]:
+    """``{"azimuth": ..., "zenith": ...}`` (those asked for; float64 device rows, degrees) of a satellite at per-row
+    ``(sat_latitude, sat_longitude)`` seen from ``(latitude, longitude)`` — ``atx_obs_view_angles``
+    (R: support/sat_view_angles.py:52-97 calc_azimuth, :17-49 calc_zenith).  All four columns are read as float64."""
+    dev = _stack.device() if dev is None else dev
+    flags = (native.VIEW_AZIMUTH if azimuth else 0) | (native.VIEW_ZENITH if zenith else 0)
+    if flags == 0:
+        return {}
+    cols = [float_column(c, dev) for c in (latitude, longitude, sat_latitude, sat_longitude)]
+    if len({c.numel() for c in cols}) > 1:
+        raise ValueError(f"columns differ in length: {[c.numel() for c in cols]}")
+    names = [n for n, on in (("azimuth", azimuth), ("zenith", zenith)) if on]
+    out = torch.empty((len(names), cols[0].numel()), dtype=torch.float64, device=dev)
+    native.obs_view_angles(*cols, flags, out)
+    return {name: out[k] for k, name in enumerate(names)}
+
+
+# R: support/sat_view_angles.py:120-130 — (satellite id, day, the side of the day that counts, sub-satellite longitude)
+_METEOSAT = ((55, "2016-10-20", ">", 41.5), (56, "2022-05-08", ">", 45.5), (57, "2013-01-24", "<", -3.4), (70, "2015-12-01", "<", -3.4))
+
+
+def meteosat_position(satellite_id: Any, date: Any, dev: torch.device | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """``(latitudes, longitudes)`` of the sub-satellite point per row (R: support/sat_view_angles.py:100-132), device tensors IN THE
+    DTYPE OF THE ID COLUMN: the reference builds them with ``np.zeros_like(satids)``, so integer ids — which its own tests use —
+    store 41.5 / 45.5 / -3.4 as 41 / 45 / -3, and the reference's literals depend on it.  The date comparisons are strict; NaT and
+    unknown ids give 0."""
+    dev = _stack.device() if dev is None else dev
+    ids = satellite_id if isinstance(satellite_id, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(_host_array(satellite_id)))
+    ids = ids.reshape(-1).to(dev)
+    ns = _device(to_ns(date), dev)
+    if ids.numel() != ns.numel():
+        raise ValueError(f"columns differ in length: satellite id {ids.numel()}, date {ns.numel()}")
+    lons = torch.zeros_like(ids)
+    for sat, day, side, lon in _METEOSAT:
+        limit = int(np.datetime64(day, "ns").astype(np.int64))
+        when = (ns > limit) if side == ">" else ((ns < limit) & (ns != NAT))
+        value = torch.tensor(lon, dtype=torch.float64).to(ids.dtype)  # numpy's assignment into the id dtype: towards zero for integers
+        lons = torch.where((ids == sat) & when, value.to(dev), lons)
+    return torch.zeros_like(ids), lons
+
+
+_C1_W, _C2 = 1.191042e-10, 1.4387768775  # W m^-2 sr^-1 cm^3; K cm (R: radiance_to_brightness_temperature.py:96-97)
+_CRIS_BANDS = {"cris_fsr": ((1, 713, 650.0, 0.625), (714, 1578, 1210.0, 0.625), (1579, 2211, 2155.0, 0.625)),
+               "cris_nsr": ((1, 713, 650.0, 0.625), (714, 1146, 1210.0, 1.250), (1147, 1305, 2155.0, 2.500))}
+
+
+def cris_wavenumbers(channels: Any, mode: str) -> np.ndarray:
+    """CrIS channel numbers to wavenumbers in cm^-1, NaN outside the bands of ``mode`` (R: radiance_to_brightness_temperature.py:52-80)."""
+    if mode not in _CRIS_BANDS:
+        raise ValueError(f"Invalid mode: {mode}. Must be 'cris_fsr' or 'cris_nsr'.")
+    ch = np.asarray(channels, dtype=np.int64)
+    nu = np.full(ch.shape, np.nan, dtype=float)
+    for first, last, start, step in _CRIS_BANDS[mode]:
+        m = (first <= ch) & (ch <= last)
+        nu[m] = start + step * (ch[m] - first)
+    return nu
+
+
+def brightness_temperature(radiance: torch.Tensor, wavenumber: Any, out: torch.Tensor | None = None) -> torch.Tensor:
+    """``b / log1p(a / max(R * 1e-2, 1e-300))`` with ``a = C1 nu^3``, ``b = C2 nu`` for a float64 device block ``radiance``
+    ``[n_ch, n]`` in mW/(m^2 sr cm^-1), one row per channel of ``wavenumber`` (cm^-1; NaN gives NaN) — ``atx_obs_planck_bt``
+    (R: radiance_to_brightness_temperature.py:96-113).  ``out`` may be ``radiance``."""
+    nu = np.asarray(wavenumber, dtype=np.float64).reshape(-1)
+    if radiance.dim() != 2 or radiance.shape[0] != nu.size:
+        raise ValueError(f"radiance must be [n_ch, n] with one row per wavenumber, got {tuple(radiance.shape)} for {nu.size} channels")
+    a, b = _device(_C1_W * (nu**3), radiance.device), _device(_C2 * nu, radiance.device)
+    out = torch.empty_like(radiance) if out is None else out
+    native.obs_planck_bt(radiance, a, b, out)
+    return out

@@ -68,7 +68,8 @@
 extern "C" {
 #endif
 
-#define ATX_VERSION 420 /* 0.4.2 — additions only, so the number stays: atx_obs_group_mean / atx_obs_group_argmin (superob: per-group
+#define ATX_VERSION 420 /* 0.4.2 — additions only, so the number stays: atx_obs_forcings / atx_obs_view_angles / atx_obs_planck_bt (per-row
+                           * observation operators); atx_obs_group_mean / atx_obs_group_argmin (superob: per-group
                            * means by pandas' row-order Kahan rule and the nearest row of every group); atx_obs_best_per_cell / atx_obs_fill_stack (observation tables
                            * onto a grid: a keyed arg-min and the gather that fills the stack); atx_rotate_vectors_stack (vector components between projection
                            * frames, a per-point table shared by every level) with its atx_frame enum; atx_pressure_at_height_stack (the
@@ -428,6 +429,42 @@ ATX_API int atx_obs_group_mean(const double* values, int64_t n_obs, int32_t n_co
  *   R: filters/tabular/superob.py:88 `df.groupby(groupby_cols, observed=True, sort=False)["distance"].idxmin()` */
 ATX_API int atx_obs_group_argmin(const double* distance, int64_t n_obs, const int32_t* order, int64_t n_sel, const int64_t* offsets,
                                  int64_t n_groups, int32_t* nearest, void* stream);
+
+/* ---- per-row observation operators (forcings, view angles, brightness temperature) ---- */
+/* float64, one lane per row, n == 0 is a no-op.  Every statement is evaluated in the operation order of the reference's source, with
+ * IEEE division and no contraction: the calendar, the arguments of the trigonometric functions and numpy's `%` have numpy's bits;
+ * cos / sin are the library's own routine for |x| < 1e5 (< 1 ulp), the device library's otherwise, asin / acos / atan / log1p the
+ * device library's.  Outputs are rows of ONE block: requested output k (in the order of its bit) at out + k * pitch.
+ *
+ * atx_obs_forcings: the nine columns of add_forcings, chosen by `mask`:
+ *   bit 0 cos_julian_day   1 sin_julian_day   2 cos_sza   3 sin_local_time   4 cos_local_time
+ *   bit 5 cos_latitude     6 sin_latitude     7 cos_longitude   8 sin_longitude
+ * julian_day = whole days since 1 January of the date's year + whole seconds of the day / 86400.0 (integer calendar; sub-second parts
+ * dropped, as Timedelta.seconds drops them; dates before 1970 are negative nanoseconds); hours = that day fraction * 24.  NaT
+ * (INT64_MIN) gives NaN in every date-dependent column.  cos_sza is clipped at 0.  Columns a mask does not need may be NULL.
+ *   date_ns    device int64 [n], nanoseconds since the epoch     latitude, longitude   device double [n], degrees
+ *   out        device double, popcount(mask) rows of n, pitch elements apart
+ * mask == 0 or bits beyond the nine, n < 0: ATX_EINVAL.  pitch < n: ATX_ESHAPE.
+ *   R: filters/tabular/add_forcings.py:51-61 (names), :86-127 (angles), support/compute_forcings.py:14-87 (cos_sza) */
+ATX_API int atx_obs_forcings(const int64_t* date_ns, const double* latitude, const double* longitude, int64_t n, uint32_t mask, double* out,
+                             int64_t pitch, void* stream);
+
+/* Viewing azimuth (flags bit 0) and zenith (bit 1) of a satellite at (sat_latitude, sat_longitude), per row, degrees; azimuth first
+ * when both are asked for.  Azimuth: exactly 0.0 unless BOTH |latitude - sat_latitude| and |longitude - sat_longitude| exceed 0.00001
+ * (a NaN fails the comparison); then the law of sines / cosines with minimum(1, sqrt(za)), the two clips to [-1, 1], the sign switch
+ * on azmsin > 0, the two wraps by 2 pi, degrees and numpy's mod 360.  Zenith: a geostationary orbit, satalt from the source's literals.
+ * flags outside 1 .. 3, n < 0: ATX_EINVAL.  pitch < n: ATX_ESHAPE.
+ *   R: filters/tabular/support/sat_view_angles.py:52-97 (calc_azimuth), :17-49 (calc_zenith); add_azimuth.py:57-60, add_msg_angles.py:74-80 */
+ATX_API int atx_obs_view_angles(const double* latitude, const double* longitude, const double* sat_latitude, const double* sat_longitude,
+                                int64_t n, uint32_t flags, double* out, int64_t pitch, void* stream);
+
+/* out[c * out_pitch + i] = b[c] / log1p(a[c] / max(radiance[c * in_pitch + i] * 1e-2, 1e-300)): CrIS radiances in mW/(m^2 sr cm^-1) to
+ * brightness temperatures in K, one row per channel; a = C1 nu^3 and b = C2 nu come from the host (a NaN wavenumber gives NaN, and
+ * so does a NaN radiance; a zero, negative or tiny radiance is floored at 1e-300).  out may be radiance (in place).
+ * n_ch outside 1 .. 65535, n < 0: ATX_EINVAL.  a pitch below n: ATX_ESHAPE.
+ *   R: filters/tabular/radiance_to_brightness_temperature.py:96-113 */
+ATX_API int atx_obs_planck_bt(const double* radiance, int64_t n, int32_t n_ch, int64_t in_pitch, const double* a, const double* b, double* out,
+                              int64_t out_pitch, void* stream);
 
 /* ---- masks ------------------------------------------------------------------ */
 

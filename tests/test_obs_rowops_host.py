@@ -1,0 +1,262 @@
+"""The per-row observation filters without a GPU: registration and argument errors, the C ABI of the three entry points, the numpy
+restatement (tests/obs_rowops_restatement.py) bit for bit against the frames the reference's own modules returned
+(tests/golden/obs_rowops.json), the reference's literals at the reference's tolerance, and numpy's OWN worst error against the exact
+statements on the generators the GPU tests share."""
+
+from __future__ import annotations
+
+import subprocess
+
+import numpy as np
+import pytest
+
+import __graft_entry__ as graft
+from anemoi_transform_amd import native, obs
+from anemoi_transform_amd.filters import create_filter_by_name, filter_registry
+from anemoi_transform_amd.filters.tabular import AddAzimuth, AddForcings, AddMSGAngles, RadianceToBrightnessTemperature
+
+import obs_rowops_restatement as R
+
+GOLDEN = R.load_golden()
+FILTERS = {"add_forcings": AddForcings, "add_azimuth": AddAzimuth, "add_msg_angles": AddMSGAngles,
+           "radiance_to_brightness_temperature": RadianceToBrightnessTemperature}
+
+
+# ---- registration and arguments ------------------------------------------------------------------------------------------------------
+def test_the_four_filters_are_registered_with_the_reference_signatures():
+    for name, cls in FILTERS.items():
+        assert filter_registry.is_registered(name), name
+    f = create_filter_by_name("add_forcings", columns=["cos_sza", "sin_latitude"])
+    assert isinstance(f, AddForcings) and f.columns == ["cos_sza", "sin_latitude"]
+    assert AddForcings.SUPPORTED_FORCINGS == set(R.FORCINGS) and obs.FORCINGS == R.FORCINGS == native.FORCINGS
+    a = create_filter_by_name("add_azimuth")
+    assert (a.azimuth, a.spacecraft_latitude, a.spacecraft_longitude) == ("azimuth", "spacecraft_latitude", "spacecraft_longitude")
+    m = create_filter_by_name("add_msg_angles")
+    assert (m.angle, m.azimuth, m.zenith, m.satellite_id) == (("azimuth", "zenith"), "azimuth", "zenith", "satellite_id")
+    assert create_filter_by_name("add_msg_angles", angle="zenith").angle == ("zenith",)
+    r = create_filter_by_name("radiance_to_brightness_temperature", mode="cris_nsr")
+    assert (r.mode, r.input_prefix, r.output_prefix) == ("cris_nsr", "obsvalue_rad_", "obsvalue_rawbt_")
+    for cls, args in ((AddForcings, (["cos_sza"],)), (AddAzimuth, ("az",)), (AddMSGAngles, ("both",)), (RadianceToBrightnessTemperature, ("cris_fsr",))):
+        with pytest.raises(TypeError):
+            cls(*args)  # keyword-only, as in the reference
+
+
+def test_argument_errors_are_the_references():
+    with pytest.raises(ValueError, match="Unknown columns requested"):
+        create_filter_by_name("add_forcings", columns=["cos_julian_day", "bad_column_name"])
+    with pytest.raises(ValueError, match="Invalid angle"):
+        create_filter_by_name("add_msg_angles", angle="invalid_angle")
+    with pytest.raises(ValueError, match="Invalid mode"):
+        create_filter_by_name("radiance_to_brightness_temperature", mode="bad_mode")
+    with pytest.raises(ValueError, match="Invalid mode"):
+        obs.cris_wavenumbers([1], "bad_mode")
+    with pytest.raises(ValueError, match="Unknown columns requested"):
+        obs.forcings(np.zeros(1, dtype=np.int64), np.zeros(1), np.zeros(1), ["tan_latitude"])
+
+
+def test_missing_columns_raise_before_anything_touches_the_device():
+    points = {"latitude": np.array([-10.0, 0.0, 10.0]), "longitude": np.array([0.0, 90.0, 270.0])}
+    with pytest.raises(ValueError, match="spacecraft_longitude"):
+        create_filter_by_name("add_azimuth")({**points, "spacecraft_latitude": np.array([-11.0, 1.0, 11.0])})
+    with pytest.raises(ValueError, match="satellite_id"):
+        create_filter_by_name("add_msg_angles")({**points, "date": np.zeros(3, dtype="datetime64[ns]")})
+    with pytest.raises(ValueError, match="satid"):
+        create_filter_by_name("add_msg_angles", satellite_id="satid")({**points, "satellite_id": np.array([55, 56, 57])})
+    with pytest.raises(ValueError, match="No columns starting with 'obsvalue_rad_'"):
+        create_filter_by_name("radiance_to_brightness_temperature", mode="cris_fsr")({"foo": np.array([0.01, 0.1, 1.0])})
+    with pytest.raises(ValueError, match="channel number"):
+        create_filter_by_name("radiance_to_brightness_temperature", mode="cris_fsr")({"obsvalue_rad_x": np.array([0.01])})
+    with pytest.raises(ValueError, match="longitude"):
+        create_filter_by_name("add_forcings", columns=["cos_sza"])({"date": np.zeros(1, dtype="datetime64[ns]"), "latitude": np.zeros(1)})
+
+
+def test_wavenumbers_are_the_restatements():
+    for mode in ("cris_fsr", "cris_nsr"):
+        channels = np.arange(-2, 2300)
+        got, want = obs.cris_wavenumbers(channels, mode), R.wavenumbers(channels, mode)
+        assert np.array_equal(got.view(np.int64), want.view(np.int64))
+    assert np.isnan(obs.cris_wavenumbers([0, 2212], "cris_fsr")).all() and np.isnan(obs.cris_wavenumbers([1306], "cris_nsr")).all()
+
+
+# ---- the C ABI ---------------------------------------------------------------------------------------------------------------------
+NAMES = ("atx_obs_forcings", "atx_obs_view_angles", "atx_obs_planck_bt")
+
+
+def test_entry_points_are_declared_bound_and_exported():
+    declared = graft.exported_names()
+    nm = subprocess.run(["nm", "-D", "--defined-only", graft.LIB], capture_output=True, text=True, check=True).stdout
+    exported = {line.split()[-1] for line in nm.splitlines() if line.strip()}
+    for name in NAMES:
+        assert name in declared, f"{name} is not declared in include/atx.h"
+        assert name in native.SIGNATURES, f"{name} is not bound in native.py"
+        assert name in exported, f"{name} is not exported by libatx.so"
+    assert native.load().atx_version() == 420  # additions only
+
+
+def test_abi_argument_validation_without_a_gpu():
+    lib = native.load()
+
+    def forcings(n=0, mask=1, pitch=0):
+        return lib.atx_obs_forcings(None, None, None, n, mask, None, pitch, None)
+
+    def angles(n=0, flags=3, pitch=0):
+        return lib.atx_obs_view_angles(None, None, None, None, n, flags, None, pitch, None)
+
+    def planck(n=0, n_ch=1, in_pitch=0, out_pitch=0):
+        return lib.atx_obs_planck_bt(None, n, n_ch, in_pitch, None, None, None, out_pitch, None)
+
+    assert forcings() == angles() == planck() == native.OK  # no rows: nothing to do, nothing dereferenced
+    assert forcings(n=-1) == native.EINVAL and forcings(mask=0) == native.EINVAL and forcings(mask=1 << 9) == native.EINVAL
+    assert b"nine" in lib.atx_last_error()
+    assert angles(flags=0) == native.EINVAL and angles(flags=4) == native.EINVAL and angles(n=-1) == native.EINVAL
+    assert planck(n_ch=0) == native.EINVAL and planck(n_ch=70000) == native.EINVAL and planck(n=-1) == native.EINVAL
+    assert forcings(n=10, pitch=9) == native.ESHAPE and angles(n=10, pitch=9) == native.ESHAPE
+    assert planck(n=10, in_pitch=9, out_pitch=10) == native.ESHAPE and planck(n=10, in_pitch=10, out_pitch=9) == native.ESHAPE
+    assert forcings(n=10, pitch=10) == native.EINVAL  # null pointers, found before any launch
+    assert b"null" in lib.atx_last_error()
+    assert angles(n=10, pitch=10) == native.EINVAL and planck(n=10, in_pitch=10, out_pitch=10) == native.EINVAL
+
+
+# ---- the restatement against the reference ---------------------------------------------------------------------------------------
+def test_the_fixture_holds_what_it_is_for():
+    """The seeded tables reach the edges the kernels can get wrong (tools/record_rowops_golden.py records them, nothing else)."""
+    by_id = {c["id"]: c for c in GOLDEN["cases"]}
+    assert sum(c["id"].startswith("reference_test_") for c in GOLDEN["cases"]) == 9 and len(GOLDEN["cases"]) == 15
+    t = R.golden_table(by_id["seeded_forcings_all"])
+    ns = R.to_ns(t["date"])
+    date = t["date"].astype("datetime64[ns]")
+    assert (ns == R.NAT).sum() >= 2 and np.isnan(t["latitude"]).any() and np.isnan(t["longitude"]).any()
+    assert (ns[ns != R.NAT] < 0).sum() >= 6  # before 1970
+    assert np.isin(np.array(["2024-02-29T00:00", "2024-02-29T23:59:59.999999999", "2024-12-31T23:59:59.999999999", "2025-01-01T00:00",
+                             "1969-12-31T23:59:59.999999999"], dtype="datetime64[ns]"), date).all()
+    lon = t["longitude"]
+    assert ((lon > -180) & (lon < 0)).any() and ((lon > 180) & (lon < 360)).any()
+    for case, kind in ((by_id["seeded_msg_integer_ids"], "i"), (by_id["seeded_msg_float_ids"], "f")):
+        t = R.golden_table(case)
+        ids, ns = t["satellite_id"], R.to_ns(t["date"])
+        assert ids.dtype.kind == kind
+        for sat, (day, _, _) in R.THRESHOLDS.items():
+            limit = int(np.datetime64(day, "ns").astype(np.int64))
+            sel = ns[(ids == sat) & (ns != R.NAT)]
+            assert (sel < limit).any() and (sel > limit).any(), sat
+        assert np.isin(ids[~np.isnan(ids.astype(float))], [55, 56, 57, 70]).sum() < len(ids) - 20  # unknown ids
+        lats, lons = R.meteosat_loc(ids, ns)
+        assert lons.dtype == ids.dtype and set(np.unique(lons).tolist()) == ({-3, 0, 41, 45} if kind == "i" else {-3.4, 0.0, 41.5, 45.5})
+        lat_ok = np.abs(t["latitude"] - lats) > 0.00001
+        lon_ok = np.abs(t["longitude"] - lons) > 0.00001
+        assert (~lat_ok & lon_ok).any() and (lat_ok & ~lon_ok).any() and (~lat_ok & ~lon_ok).any()
+    t = R.golden_table(by_id["seeded_azimuth"])
+    lat_ok, lon_ok = np.abs(t["latitude"] - t["sc_lat"]) > 0.00001, np.abs(t["longitude"] - t["sc_lon"]) > 0.00001
+    assert (~lat_ok & lon_ok).any() and (lat_ok & ~lon_ok).any() and (~lat_ok & ~lon_ok).any()
+    for mode in ("cris_fsr", "cris_nsr"):
+        t = R.golden_table(by_id[f"seeded_radiance_{mode[-3:]}"])
+        cols, chans = R.radiance_columns(list(t), "obsvalue_rad_")
+        edges = {e for first, last, _, _ in R.BANDS[mode] for e in (first, last)}
+        assert edges <= set(chans.tolist()) and np.isnan(R.wavenumbers(chans, mode)).sum() == 3 and list(chans) == sorted(chans)
+        assert [c for c in t if c.startswith("obsvalue_rad_")] != cols  # the table's order is not the channels'
+        block = np.stack([t[c] for c in cols])
+        assert (block == 0).any() and (block < 0).any() and (block == 1e-310).any() and np.isnan(block).any()
+
+
+@pytest.mark.parametrize("case", GOLDEN["cases"], ids=lambda c: c["id"])
+def test_restatement_equals_the_recorded_frames_bit_for_bit(case):
+    want = R.golden_expected(case)
+    got = R.apply_filter(case["filter"], case["config"], R.golden_table(case))
+    assert list(got) == list(want)
+    for name, recorded in want.items():
+        values = np.asarray(got[name])
+        if recorded.dtype.kind == "M":
+            assert np.array_equal(R.to_ns(values), R.to_ns(recorded)), name
+        elif recorded.dtype == np.float64:
+            assert np.array_equal(np.asarray(values, dtype=np.float64).view(np.int64), recorded.view(np.int64)), name
+        else:
+            assert np.array_equal(values, recorded), name
+
+
+@pytest.mark.parametrize("case", [c for c in GOLDEN["cases"] if "literals" in c], ids=lambda c: c["id"])
+def test_reference_literals_at_the_references_tolerance(case):
+    got = R.apply_filter(case["filter"], case["config"], R.golden_table(case))
+    for column, literal in case["literals"].items():
+        assert np.allclose(got[column], literal, rtol=case["rtol"]), column
+    assert case["rtol"] == (1e-3 if case["filter"] == "add_forcings" else 1e-5)
+
+
+def test_integer_ids_truncate_the_sub_satellite_longitudes():
+    """R: support/sat_view_angles.py:117-118 — ``np.zeros_like(satids)``: the reference's own expected azimuth of satellite 55 (78.703325)
+    is the azimuth seen from longitude 41, not 41.5."""
+    date = np.array(["2025-01-01T00"] * 3, dtype="datetime64[ns]")
+    lats, lons = R.meteosat_loc(np.array([55, 56, 57]), date)
+    assert lons.dtype.kind == "i" and lons.tolist() == [41, 45, 0]
+    assert R.meteosat_loc(np.array([55.0, 56.0, 57.0]), date)[1].tolist() == [41.5, 45.5, 0.0]
+    assert R.meteosat_loc(np.array([57, 70]), np.array(["2013-01-23T23:59", "2015-11-30"], dtype="datetime64[ns]"))[1].tolist() == [-3, -3]
+    at = np.array(["2016-10-20", "2022-05-08", "2013-01-24", "2015-12-01"], dtype="datetime64[ns]")  # strict: the day itself does not count
+    assert R.meteosat_loc(np.array([55, 56, 57, 70]), at)[1].tolist() == [0, 0, 0, 0]
+    assert np.isclose(R.calc_azimuth(np.array([-10.0]), np.array([0.0]), np.array([0]), np.array([41]))[0], 78.703325)
+    assert not np.isclose(R.calc_azimuth(np.array([-10.0]), np.array([0.0]), np.array([0.0]), np.array([41.5]))[0], 78.703325)
+
+
+def test_calendar_against_pandas():
+    """``julian_day_and_hours`` equals the reference's Timedelta arithmetic (R: add_forcings.py:99-114) bit for bit, NaT included."""
+    pd = pytest.importorskip("pandas")
+    rng = np.random.default_rng(5)
+    ns = np.concatenate([R.random_dates(rng, 2000), R.to_ns(R.forcings_table()["date"])])
+    date = pd.DatetimeIndex(ns.view("datetime64[ns]"))
+    delta = date - date.to_period("Y").to_timestamp()
+    julian_day = np.asarray(delta.days + delta.seconds / 86400.0, dtype=np.float64)
+    delta = date - date.to_period("D").to_timestamp()
+    hours = np.asarray((delta.days + delta.seconds / 86400.0) * 24, dtype=np.float64)
+    got = R.julian_day_and_hours(ns)
+    assert np.array_equal(got[0], julian_day, equal_nan=True) and np.array_equal(got[1], hours, equal_nan=True)
+    assert np.isnan(got[0]).sum() == 2 and got[0][~np.isnan(got[0])].min() >= 0 and got[0][~np.isnan(got[0])].max() < 366
+
+
+def test_forcing_arguments_are_numpys_intermediates():
+    """The arguments the exact references of the single-function forcings start from are what the reference's own ``_angle_radians``
+    computes, bit for bit — executed here with pandas as the reference executes it."""
+    pd = pytest.importorskip("pandas")
+    ins = R.forcing_cases()
+    date = pd.DatetimeIndex(ins["date"].view("datetime64[ns]"))
+    delta = date - date.to_period("Y").to_timestamp()
+    julian = (delta.days + delta.seconds / 86400.0) / 365.25 * np.pi * 2
+    delta = date - date.to_period("D").to_timestamp()
+    hours = (delta.days + delta.seconds / 86400.0) * 24
+    local = ((ins["longitude"] / 360.0 * 24.0 + hours) % 24) / 24 * np.pi * 2
+    want = {"julian_day": julian, "local_time": local, "latitude": np.deg2rad(ins["latitude"]), "longitude": np.deg2rad(ins["longitude"])}
+    got = R.forcing_arguments(ins["date"], ins["latitude"], ins["longitude"])
+    for name in want:
+        assert np.array_equal(np.asarray(want[name], dtype=np.float64).view(np.int64), got[name].view(np.int64)), name
+    assert np.float64(R.RAD) == np.deg2rad(1.0) and np.float64(R.DEG) == np.degrees(1.0)
+
+
+# ---- numpy's own error on the shared generators -----------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", sorted(R.NUMPY_WORST))
+def test_numpy_worst_error_is_pinned(name):
+    """Pinned within [0.8 x, 1.1 x + 0.1], as tests/test_exact_statements.py pins the humidity operators: the kernels' ceilings are
+    2 x + SLACK, so a generator that stopped reaching the hard inputs — or started to reach ill-conditioned ones — shows here first."""
+    rec = R.composed(name)
+    err = R.errors(name, rec["numpy"])
+    worst, pinned = float(err.max()), R.NUMPY_WORST[name]
+    print(f"{name}: numpy {worst:.3f}, pinned {pinned}, left out {int(rec['skip'].sum())} of {len(err)}")
+    assert np.isfinite(err).all() and 0.8 * pinned <= worst <= 1.1 * pinned + 0.1, (name, worst, pinned)
+    assert rec["skip"].sum() <= len(err) / 1000 and (name != "azimuth" or rec["skip"].sum() == 0)
+    if name != "brightness_temperature":
+        assert R.CEILING[name] == 2 * pinned + R.SLACK
+    else:
+        assert worst <= R.CEILING[name] == 3.0
+
+
+def test_generators_are_well_conditioned_and_reach_their_edges():
+    v = R.view_cases()
+    assert set(np.unique(v["sat_longitude"]).tolist()) == {0.0, 41.5, 45.5, -3.4} and not v["sat_latitude"].any()
+    d = np.abs(v["longitude"] - v["sat_longitude"])
+    assert 2.0 <= np.abs(v["latitude"]).min() and np.abs(v["latitude"]).max() <= 70.0 and 2.0 <= d.min() and d.max() <= 65.0
+    assert ((v["longitude"] - v["sat_longitude"]) > 0).any() and ((v["longitude"] - v["sat_longitude"]) < 0).any()
+    f = R.forcing_cases()
+    jd, hours = R.julian_day_and_hours(f["date"])
+    assert 0 <= jd.min() and jd.max() < 366 and jd.max() > 365 and 0 <= hours.min() and hours.max() < 24
+    assert f["latitude"].min() >= -90 and f["latitude"].max() <= 90 and f["longitude"].min() >= -180 and f["longitude"].max() <= 360
+    assert (f["date"] < 0).any() and (f["date"] % R.NS_SECOND != 0).any()
+    night = R.composed("cos_sza")["numpy"] == 0.0
+    assert 0.3 < night.mean() < 0.7
+    b = R.bt_cases()
+    assert b["radiance"].min() >= 1e-3 and b["radiance"].max() <= 10**2.5 and np.isfinite(b["a"]).all() and len(np.unique(b["b"])) > 1000

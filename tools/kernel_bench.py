@@ -48,6 +48,10 @@ def main():
     ap.add_argument("--only-obs", action="store_true", help="only the observation-gridding rows (atx_obs_best_per_cell, atx_obs_fill_stack)")
     ap.add_argument("--only-superob", action="store_true", help="only the superob rows (atx_obs_group_mean, atx_obs_group_argmin, the filter end "
                     "to end beside the reference's statement in pandas on this host); --only-obs runs them after its own rows")
+    ap.add_argument("--only-rowops", action="store_true", help="only the per-row observation kernels (atx_obs_forcings, atx_obs_view_angles, "
+                    "atx_obs_planck_bt) at --rows rows, rows/s beside the reference's numpy statements on this host")
+    ap.add_argument("--rows", type=int, default=10_000_000)
+    ap.add_argument("--commit", default=None, help="recorded in the --only-rowops result: the commit the library was built from")
     ap.add_argument("--only-pointwise", action="store_true", help="only the per-point, mask and reduction rows (atx_pointwise.hip, atx_mask.hip, "
                     "atx_reduce.hip), each with a checksum of what it computed on the seeded stack")
     ap.add_argument("--only-regrid", action="store_true", help="only the gather rows (atx_regrid_columns.inc, atx_regrid_fields.inc), each with a "
@@ -500,6 +504,55 @@ def main():
     if args.only_pointwise:
         for tdt, B, tag in ((torch.float32, 4, "f32"), (torch.float64, 8, "f64")):
             pointwise_rows(tdt, B, tag)
+        if args.out:
+            json.dump(res, open(args.out, "w"), indent=1)
+        return
+
+    def rowops_rows():
+        """The three per-row observation kernels at args.rows rows, once each: rows/s and the fraction of the HBM peak on algorithmic
+        bytes (they are VALU-bound: the fraction says how far from the memory roof the arithmetic keeps them), beside the reference's
+        numpy statements (tests/obs_rowops_restatement.py) on this host, one process, at a tenth of the rows."""
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import obs_rowops_restatement as R
+        from anemoi_transform_amd import obs
+
+        n = args.rows
+        rng = np.random.default_rng(n)
+        date = R.random_dates(rng, n)
+        lat, lon = rng.uniform(-90.0, 90.0, n), rng.uniform(-180.0, 360.0, n)
+        sat_lon = rng.choice([0.0, 41.5, 45.5, -3.4], n)
+        n_ch = 4
+        channels = np.array([7, 714, 1000, 2211])
+        radiance = 10.0 ** rng.uniform(-3.0, 2.5, (n_ch, n))
+        d_date, d_lat, d_lon, d_sat_lon, d_rad = (torch.from_numpy(a).to(dev) for a in (date, lat, lon, sat_lon, radiance))
+        d_sat_lat = torch.zeros(n, dtype=torch.float64, device=dev)
+        a, b = (torch.from_numpy(t).to(dev) for t in R.planck_tables(channels, "cris_fsr"))
+        out9 = torch.empty((9, n), dtype=torch.float64, device=dev)
+        out2 = torch.empty((2, n), dtype=torch.float64, device=dev)
+        out_bt = torch.empty_like(d_rad)
+        m = n // 10
+        host = {}
+        for name, fn in (("forcings", lambda: R.forcings(date[:m], lat[:m], lon[:m], list(R.FORCINGS))),
+                         ("view_angles", lambda: (R.calc_azimuth(lat[:m], lon[:m], np.zeros(m), sat_lon[:m]), R.calc_zenith(lat[:m], lon[:m], np.zeros(m), sat_lon[:m]))),
+                         ("planck_bt", lambda: R.brightness_temperature(radiance[:, :m].T, *R.planck_tables(channels, "cris_fsr")))):
+            t0 = time.perf_counter()
+            fn()
+            host[name] = m / (time.perf_counter() - t0)
+        rows = (("obs_forcings 9 columns", "forcings", lambda: native.obs_forcings(d_date, d_lat, d_lon, 0x1ff, out9), n * (24 + 72), n,
+                 "all nine forcings in one pass: julian day, hours and the angles once per row"),
+                ("obs_view_angles azimuth + zenith", "view_angles", lambda: native.obs_view_angles(d_lat, d_lon, d_sat_lat, d_sat_lon, 3, out2), n * (32 + 16), n,
+                 "both angles in one pass: the sines and cosines of the four positions shared"),
+                (f"obs_planck_bt {n_ch} channels", "planck_bt", lambda: native.obs_planck_bt(d_rad, a, b, out_bt), n * n_ch * 16, n,
+                 "b / log1p(a / max(R * 1e-2, 1e-300)), blockIdx.y = channel"))
+        for name, key, fn, alg, n_rows, note in rows:
+            ms = timeit(fn, n=9)
+            label = f"{name} {n:.0e} rows"
+            record(label, ms, alg, note)
+            res[label].update(rows_per_s=n_rows / (ms * 1e-3), numpy_rows_per_s=host[key], numpy_rows=m, commit=args.commit)
+            print(f"{'':42s} {n_rows / (ms * 1e-3):.3e} rows/s; numpy on this host, one process, {m} rows: {host[key]:.3e} rows/s", flush=True)
+
+    if args.only_rowops:
+        rowops_rows()
         if args.out:
             json.dump(res, open(args.out, "w"), indent=1)
         return

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Registers, LDS and scratch of every kernel in libatx.so, read from the code objects embedded in the library (no GPU, no recompilation):
-   python tools/kernel_resources.py [--lib PATH] [--scratch]      (--scratch: only kernels that use private scratch memory)
+   python tools/kernel_resources.py [--lib PATH] [--scratch] [--match TEXT]
+(--scratch: only kernels that use private scratch memory; --match: only kernels whose name holds TEXT, e.g. --match obs_ for the
+observation kernels: obs_forcings_kernel, obs_view_angles_kernel, obs_planck_bt_kernel, the gridding and superob kernels)
 A kernel that indexes a private array with a run-time subscript ends up in scratch memory and loses most of its bandwidth — round 3
 found the field-major per-point kernel that way (0.41 of the HBM peak instead of 0.83); tests/test_host_api.py keeps the list empty."""
 from __future__ import annotations
@@ -54,8 +56,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lib", default=os.path.join(ROOT, "anemoi-transform_amd", "lib", "libatx.so"))
     ap.add_argument("--scratch", action="store_true")
+    ap.add_argument("--match", default=None)
     args = ap.parse_args()
     rows = kernel_resources(args.lib)
+    if args.match:
+        rows = [r for r in rows if args.match in r["name"]]
     if args.scratch:
         rows = [r for r in rows if r["scratch"] > 0]
     for r, nice in zip(rows, demangle([r["name"] for r in rows])):
