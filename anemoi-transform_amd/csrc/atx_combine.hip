@@ -19,6 +19,9 @@ struct CombArgs {
 #ifndef ATX_FAST_SINCOS
 #define ATX_FAST_SINCOS 1
 #endif
+#ifndef ATX_SNOW_TANH
+#define ATX_SNOW_TANH 0  // the tanh of ATX_COMB_SNOW_COVER in float64: 0 atx_tanh_moderate, 1 the device library's tanh, 2 round 3's form (combine_one)
+#endif
 
 // Saturation vapour pressure over water / ice and in the mixed phase, as earthkit-meteo (>= 0.4.1, absent here) publishes them
 // (thermo.array.saturation_vapour_pressure: the IFS formulas, c1 = 611.21 Pa, T0 = 273.16 K, water 17.502 / 32.19, ice 22.587 / -0.7, the liquid
@@ -27,32 +30,18 @@ struct CombArgs {
 // each, four per element in q_to_r, which made the operator VALU-bound at 0.38 of the HBM peak): v_rcp + two Newton steps + one
 // residual correction, within 1 ulp of the correctly rounded quotient for the finite, normal operands these formulas see
 // (temperatures, pressures, vapour pressures; a zero or infinite divisor gives NaN where the division gives inf / 0 — no physical input).
-// ATX_HUMIDITY_IEEE_DIV=1 restores the plain division.  Measured on 137-level O1280 stacks: q_to_r 0.37 -> 0.52 (f32), 0.38 -> 0.50 (f64) of
-// 8 TB/s, r_to_d 0.56 -> 0.70 / 0.52 -> 0.57; an own float64 exp without the library's special cases and 1 or 4 vectors per lane instead of 2
-// changed nothing (profiles/r04_humidity_variants.log).
-#ifndef ATX_HUMIDITY_IEEE_DIV
-#define ATX_HUMIDITY_IEEE_DIV 0
-#endif
 __device__ __forceinline__ double quotient(double a, double b) {
-#if ATX_HUMIDITY_IEEE_DIV
-    return a / b;
-#else
     double r = __builtin_amdgcn_rcp(b);
     r = __builtin_fma(__builtin_fma(-b, r, 1.0), r, r);
     r = __builtin_fma(__builtin_fma(-b, r, 1.0), r, r);
     const double q = a * r;
     return __builtin_fma(__builtin_fma(-b, q, a), r, q);
-#endif
 }
 __device__ __forceinline__ float quotient(float a, float b) {
-#if ATX_HUMIDITY_IEEE_DIV
-    return a / b;
-#else
     float r = __builtin_amdgcn_rcpf(b);
     r = __builtin_fmaf(__builtin_fmaf(-b, r, 1.0f), r, r);
     const float q = a * r;
     return __builtin_fmaf(__builtin_fmaf(-b, q, a), r, q);
-#endif
 }
 template <typename T>
 __device__ __forceinline__ T es_water(T t) { return T(611.21) * atx_exp(quotient(T(17.502) * (t - T(273.16)), t - T(32.19))); }
@@ -74,6 +63,51 @@ __device__ __forceinline__ T es_mixed(T t) {
     if (a < T(1)) ei = es_ice(t);
     return a * ew + (T(1) - a) * ei;
 }
+
+// What the host validation, the launcher and the kernel need to know about an operator, in ONE place: a new operator is entered here
+// and as a case of combine_one.
+constexpr int kAnyNumber = -1, kTwoOrThree = -2;  // operand counts that are not one number
+enum class LevelParam {
+    kNone,          // not read
+    kPerLevel,      // the kernel reads level_param[level]: required
+    kPerLevelIf2,   // ... in place of the optional third operand: required when there are two
+    kTable,         // ATX_COMB_LOOKUP's table (its length, then its values): required
+};
+struct CombOp {
+    int n_in, n_out;
+    LevelParam param;
+    constexpr bool reads_level() const { return param == LevelParam::kPerLevel || param == LevelParam::kPerLevelIf2; }
+    constexpr bool needs_param(int given) const { return param == LevelParam::kPerLevel || param == LevelParam::kTable || (param == LevelParam::kPerLevelIf2 && given == 2); }
+    // compile-time bound of the operand count for the kernel (0: the launcher picks 1, 2, 3 or ATX_COMB_MAX_INPUTS from the call)
+    constexpr int bound() const { return n_in == kAnyNumber ? 0 : (n_in == kTwoOrThree ? 3 : n_in); }
+};
+constexpr CombOp comb_op(int op) {
+    switch (op) {
+        case ATX_COMB_SNOW_DEPTH_M: return {2, 1, LevelParam::kNone};
+        case ATX_COMB_SNOW_COVER: return {2, 1, LevelParam::kNone};
+        case ATX_COMB_COS_SIN: return {1, 2, LevelParam::kNone};
+        case ATX_COMB_ATAN2: return {2, 1, LevelParam::kNone};
+        case ATX_COMB_W_TO_WZ: return {3, 1, LevelParam::kPerLevel};
+        case ATX_COMB_WZ_TO_W: return {3, 1, LevelParam::kPerLevel};
+        case ATX_COMB_SUM: return {kAnyNumber, 1, LevelParam::kNone};
+        case ATX_COMB_SUB: return {2, 1, LevelParam::kNone};
+        case ATX_COMB_XY_TO_POLAR: return {2, 2, LevelParam::kNone};
+        case ATX_COMB_POLAR_TO_XY: return {2, 2, LevelParam::kNone};
+        case ATX_COMB_OPERA_CLIP: return {2, 2, LevelParam::kPerLevel};
+        case ATX_COMB_OPERA_PREPROCESS: return {3, 2, LevelParam::kPerLevel};
+        case ATX_COMB_ORAS6: return {2, 1, LevelParam::kPerLevel};
+        case ATX_COMB_LOOKUP: return {1, 1, LevelParam::kTable};
+        case ATX_COMB_R_TO_D: return {2, 1, LevelParam::kNone};
+        case ATX_COMB_D_TO_R: return {2, 1, LevelParam::kNone};
+        case ATX_COMB_Q_TO_R: return {kTwoOrThree, 1, LevelParam::kPerLevelIf2};
+        case ATX_COMB_R_TO_Q: return {kTwoOrThree, 1, LevelParam::kPerLevelIf2};
+        case ATX_COMB_Q_TO_D: return {2, 1, LevelParam::kNone};
+        case ATX_COMB_D_TO_Q: return {2, 1, LevelParam::kNone};
+        default: return {0, 0, LevelParam::kNone};  // no such operator
+    }
+}
+constexpr bool comb_ops_complete(int op = 0) { return op == ATX_COMB_COUNT_ || (comb_op(op).n_out >= 1 && comb_op(op).n_out <= 2 && comb_ops_complete(op + 1)); }
+static_assert(comb_ops_complete(), "every atx_comb_op needs its line in comb_op()");
 
 // g = 9.80665 (R: constants.py:13, value pinned by filters/tabular/geopotential_to_height.py:51)
 // OP is a template parameter: every operator gets its own kernel.  With a runtime switch the float64 kernels carried the
@@ -111,9 +145,6 @@ __device__ __forceinline__ void combine_one(int flags, const T* x, int n_in, T l
                 // only the statement's last line; a NaN, which the arithmetic carries through (every comparison below is false for it);
                 // or a negative argument (a negative snow depth), whose tanh the clip to [0, 1] replaces by 0 whatever its value.
                 // ATX_SNOW_TANH=1 restores the device library's tanh, =2 round 3's form.
-#ifndef ATX_SNOW_TANH
-#define ATX_SNOW_TANH 0
-#endif
                 if constexpr (ATX_SNOW_TANH == 0 && sizeof(T) == 8) {
                     const T t = (T)atx_tanh_moderate((double)arg);
                     const T sc = (t > T(0.99)) ? T(1.0) : t;
@@ -286,68 +317,26 @@ __device__ __forceinline__ void combine_one(int flags, const T* x, int n_in, T l
 }
 
 // The stacks are contiguous runs of vectors (pitch is a multiple of the vector): a workgroup sweeps line-aligned chunks
-// of kBlock * U vectors, U independent loads per operand and lane in flight (comb_unroll below; the n-ary sum keeps one:
-// 8 operands x 4 vectors would not fit the register file).
-// Vectors per lane in flight and grid shape, measured on 137-level O1280 stacks (profiles/r01_kernel_bench.log):
-//   f32: 2 vectors per lane, one workgroup per chunk, no grid cap — difference 2->1 1.81 ms (4 per lane under a 65536-workgroup
-//        cap: 2.11 ms; 1 per lane uncapped: 1.78 ms but cos+sin 1->2 slower), snow_cover 2.66 -> 2.17 ms;
-//   f64: 4 vectors per lane under the 65536-workgroup cap — difference 3.63 ms (uncapped 1 / 2 per lane: 4.30 / 3.60 ms, the
-//        transcendental operators lose 10 % uncapped).
-#ifndef ATX_COMB_NT
-#define ATX_COMB_NT 1  // round 3: non-temporal stores AND loads (ATX_COMB_NT_LOAD) — nothing is touched twice; profiles/r03_combine_ab.log
-#endif
-
-template <typename T, int N>
-__device__ __forceinline__ void comb_store(T* p, const Pack<T, N>& v) {
-#if ATX_COMB_NT
-    typedef T NV __attribute__((ext_vector_type(N)));
-    __builtin_nontemporal_store(*reinterpret_cast<const NV*>(&v), reinterpret_cast<NV*>(p));
-#else
-    *reinterpret_cast<Pack<T, N>*>(p) = v;
-#endif
+// of kBlock * U vectors, U independent loads per operand and lane in flight, one workgroup per chunk (the grid is clamped to what
+// a launch can hold and the kernel strides over the rest).  Every element is read once and written once: 16-byte accesses are
+// non-temporal, loads and stores; the element-by-element fallback (VEC == 1) uses plain ones.  What decided these shapes:
+// HISTORY.md, "The combine and relayout kernels' A/B knobs, frozen".
+constexpr int kCombUnroll = 2;       // vectors per lane, float32 and float64 alike
+constexpr int kCombUnrollOpera = 1;  // ... of the 4- and 5-stream OPERA operators
+constexpr int comb_unroll(int nin, int op) {
+    if (op == ATX_COMB_OPERA_CLIP || op == ATX_COMB_OPERA_PREPROCESS) return kCombUnrollOpera;
+    return nin > 3 ? 1 : kCombUnroll;  // the n-ary sum keeps one: 8 operands x 4 vectors would not fit the register file
 }
-template <typename T>
-__device__ __forceinline__ void comb_store(T* p, const Pack<T, 1>& v) {
-    *p = v.v[0];
-}
-
-// Launch shape knobs (A/B builds; tools/experiments/combine_ab.py): vectors per lane for 4- and 8-byte elements, the workgroup cap
-// for 8-byte elements (0 = none: one workgroup per chunk), non-temporal loads.
-#ifndef ATX_COMB_U_F32
-#define ATX_COMB_U_F32 2
-#endif
-// round 3: 2 per lane and NO cap for float64 too (was 4 under a 65536-workgroup cap): the no-loop shape runs the same on every
-// box, the capped sweep moved 3.46 <-> 3.82 ms (difference 2 -> 1) between two boxes of one afternoon
-#ifndef ATX_COMB_U_F64
-#define ATX_COMB_U_F64 2
-#endif
-#ifndef ATX_COMB_CAP_F64
-#define ATX_COMB_CAP_F64 0
-#endif
-#ifndef ATX_COMB_NT_LOAD
-#define ATX_COMB_NT_LOAD 1
-#endif
-#ifndef ATX_COMB_U_OPERA
-#define ATX_COMB_U_OPERA 1  // vectors per lane of the 4- and 5-stream OPERA operators (0: as the other operators).  Measured on 137-level O1280
-                            // stacks, 1 / 2 / 4 per lane: clipping 2->2 f32 0.748 / 0.702 / 0.754 of 8 TB/s, f64 0.814 / 0.752 / 0.810; preprocessing
-                            // 3->2 f32 0.764 / 0.699 / 0.694, f64 0.795 / 0.744 / 0.791 (profiles/r04_opera_unroll.log)
-#endif
-constexpr int comb_unroll(int nin, int elem_bytes, int op) {
-    if (ATX_COMB_U_OPERA > 0 && (op == ATX_COMB_OPERA_CLIP || op == ATX_COMB_OPERA_PREPROCESS)) return ATX_COMB_U_OPERA;
-    return nin > 3 ? 1 : (elem_bytes == 4 ? ATX_COMB_U_F32 : ATX_COMB_U_F64);
-}
-constexpr int64_t comb_grid_cap(int elem_bytes, int op) { return (elem_bytes == 4 || ATX_COMB_CAP_F64 == 0) ? 0x7fffffffll : (int64_t)ATX_COMB_CAP_F64; }
 
 template <typename T, int N>
 __device__ __forceinline__ Pack<T, N> comb_load(const T* p) {
-#if ATX_COMB_NT_LOAD
-    if constexpr (N > 1) {
-        typedef T NV __attribute__((ext_vector_type(N)));
-        NV v = __builtin_nontemporal_load(reinterpret_cast<const NV*>(p));
-        return *reinterpret_cast<Pack<T, N>*>(&v);
-    }
-#endif
-    return *reinterpret_cast<const Pack<T, N>*>(p);
+    if constexpr (N > 1) return pw_load_nt<T, N>(p);
+    else return *reinterpret_cast<const Pack<T, N>*>(p);
+}
+template <typename T, int N>
+__device__ __forceinline__ void comb_store(T* p, const Pack<T, N>& v) {
+    if constexpr (N > 1) pw_store_nt<T, N>(p, v);
+    else *p = v.v[0];
 }
 
 // NIN: compile-time bound of the operand count (1, 2, 3 or ATX_COMB_MAX_INPUTS) so the operand registers are exactly as many as needed
@@ -358,32 +347,16 @@ combine_kernel(CombArgs a, int flags, int n_in, int n_out, int64_t n_rows, int64
     using V = Pack<T, VEC>;
     const int vec_per_row = (int)(pitch / VEC);  // pitch % VEC == 0 on this path (else VEC == 1)
     const int64_t total = n_rows * vec_per_row;
-    constexpr int U = comb_unroll(NIN, (int)sizeof(T), OP);
+    constexpr int U = comb_unroll(NIN, OP);
     constexpr int64_t kChunk = (int64_t)kBlock * U;
-    constexpr bool kLevels = OP == ATX_COMB_W_TO_WZ || OP == ATX_COMB_WZ_TO_W || OP == ATX_COMB_OPERA_CLIP ||
-                             OP == ATX_COMB_OPERA_PREPROCESS || OP == ATX_COMB_ORAS6 || OP == ATX_COMB_Q_TO_R ||
-                             OP == ATX_COMB_R_TO_Q;  // the operators that read level_param[level] (when given one)
-    // every operator but the n-ary sum and the two humidity conversions that take the pressure as an optional third field has a fixed
-    // operand count, NIN == n_in — validated on the host: no run-time test per operand and element for them
-    constexpr bool kFixedOperands = OP != ATX_COMB_SUM && OP != ATX_COMB_Q_TO_R && OP != ATX_COMB_R_TO_Q;
+    constexpr bool kLevels = comb_op(OP).reads_level();  // level_param[level] is read (when given one)
+    // an operator with a fixed operand count has NIN == n_in — validated on the host: no run-time test per operand and element (the
+    // others: the n-ary sum and the two humidity conversions that take the pressure as an optional third field)
+    constexpr bool kFixedOperands = comb_op(OP).n_in > 0;
     constexpr bool kShared1 = OP == ATX_COMB_ORAS6;  // operand 1 is ONE field [n_pts] shared by every level, not a stack
     const bool small_rows = vec_per_row < (1 << 20);  // columns layout: (row, col) from 32-bit arithmetic
     const float inv_vec_per_row = __builtin_amdgcn_rcpf((float)vec_per_row);
-    // ATX_COMB_ASSIGN 1: a workgroup takes a contiguous run of chunks, not every gridDim.x-th one — under the 65536-workgroup cap the grid
-    // stride is a power of two (1 GiB for f64) and drifting workgroups were suspected of aliasing onto the same HBM channels.  The same
-    // experiment on the per-point chunked kernel measured contiguous runs 10 % slower (profiles/r03_pointwise_ab_README.md), so 0 stays.
-#ifndef ATX_COMB_ASSIGN
-#define ATX_COMB_ASSIGN 0
-#endif
-#if ATX_COMB_ASSIGN == 1
-    const int64_t n_chunks = (total + kChunk - 1) / kChunk;
-    const int64_t per = (n_chunks + gridDim.x - 1) / gridDim.x;
-    const int64_t first = (int64_t)blockIdx.x * per * kChunk;
-    const int64_t last = first + per * kChunk < total ? first + per * kChunk : total;
-    for (int64_t base = first; base < last; base += kChunk) {
-#else
     for (int64_t base = (int64_t)blockIdx.x * kChunk; base < total; base += (int64_t)gridDim.x * kChunk) {
-#endif
         const int64_t row_b = base / vec_per_row;  // uniform
         const int col_b = (int)(base - row_b * vec_per_row);
         V x[U][NIN];
@@ -407,12 +380,9 @@ combine_kernel(CombArgs a, int flags, int n_in, int n_out, int64_t n_rows, int64
                 // nearest multiple of vec_per_row, and three roundings of 2^-24 (the hardware reciprocal: 2^-23) move the product by at most
                 // (1 + 512.5 / vec_per_row) x 1.8e-7 — smaller for every vec_per_row below 2.8e6 (tests/test_host_api.py checks the arithmetic
                 // over 6 000 divisors with the reciprocal off by an ulp either way).  6 instructions instead of the ~16 of an integer division,
-                // per vector, in every multi-input operator.  ATX_COMB_INT_DIV=1 restores the division.
-#ifndef ATX_COMB_INT_DIV
-#define ATX_COMB_INT_DIV 0
-#endif
+                // per vector, in every multi-input operator.
                 const int off = col_b + u * kBlock + threadIdx.x;
-                const int dr = ATX_COMB_INT_DIV ? off / vec_per_row : (int)(((float)off + 0.5f) * inv_vec_per_row);
+                const int dr = (int)(((float)off + 0.5f) * inv_vec_per_row);
                 row = row_b + dr;
                 col = (int64_t)(off - dr * vec_per_row) * VEC;
             } else {
@@ -458,6 +428,15 @@ combine_kernel(CombArgs a, int flags, int n_in, int n_out, int64_t n_rows, int64
     }
 }
 
+// f(std::integral_constant<int, op>{}) for the run-time operator: every operator gets its own kernels
+template <int OP = 0, typename F>
+static void with_comb_op(int op, F&& f) {
+    if constexpr (OP < ATX_COMB_COUNT_) {
+        if (op == OP) f(std::integral_constant<int, OP>{});
+        else with_comb_op<OP + 1>(op, f);
+    }
+}
+
 template <typename T>
 static int combine_typed(const CombArgs& a, int op, int flags, int n_in, int n_out, int64_t n_pts, int n_lev, int64_t pitch,
                          int layout, const double* level_param, hipStream_t st) {
@@ -467,54 +446,25 @@ static int combine_typed(const CombArgs& a, int op, int flags, int n_in, int n_o
     for (int k = 0; k < n_out; ++k) vec_ok = vec_ok && aligned16(a.out[k]);
     const int64_t n_rows = layout == ATX_COLUMNS ? n_pts : n_lev;
     const int64_t row_len = layout == ATX_COLUMNS ? n_lev : n_pts;
-    const int per_block = kBlock * comb_unroll(n_in <= 3 ? n_in : ATX_COMB_MAX_INPUTS, (int)sizeof(T), op);
+    const int per_block = kBlock * comb_unroll(n_in <= 3 ? n_in : ATX_COMB_MAX_INPUTS, op);
     int64_t blocks = (n_rows * (pitch / (vec_ok ? VEC : 1)) + per_block - 1) / per_block;
-    if (blocks > comb_grid_cap((int)sizeof(T), op)) blocks = comb_grid_cap((int)sizeof(T), op);
+    if (blocks > 0x7fffffffll) blocks = 0x7fffffffll;
     if (blocks < 1) blocks = 1;
-#define ATX_COMB_LAUNCH(V_, N_, OP_)                                                                                            \
-    hipLaunchKernelGGL((combine_kernel<T, V_, N_, OP_>), dim3((unsigned)blocks), dim3(kBlock), 0, st, a, flags, n_in, n_out, n_rows, \
+    with_comb_op(op, [&](auto op_) {
+        constexpr int OP = decltype(op_)::value;
+        with_flag(vec_ok, [&](auto wide) {
+            constexpr int V = decltype(wide)::value ? VEC : 1;
+#define ATX_COMB_LAUNCH(N_)                                                                                                        \
+    hipLaunchKernelGGL((combine_kernel<T, V, N_, OP>), dim3((unsigned)blocks), dim3(kBlock), 0, st, a, flags, n_in, n_out, n_rows, \
                        row_len, pitch, layout, n_lev, level_param)
-#define ATX_COMB_CASE(OP_, N_)                 \
-    case OP_:                                  \
-        if (vec_ok) ATX_COMB_LAUNCH(VEC, N_, OP_); \
-        else ATX_COMB_LAUNCH(1, N_, OP_);      \
-        break
-    switch (op) {  // the operand count of every operator but the n-ary sum is fixed (validated by the caller)
-        ATX_COMB_CASE(ATX_COMB_SNOW_DEPTH_M, 2);
-        ATX_COMB_CASE(ATX_COMB_SNOW_COVER, 2);
-        ATX_COMB_CASE(ATX_COMB_COS_SIN, 1);
-        ATX_COMB_CASE(ATX_COMB_ATAN2, 2);
-        ATX_COMB_CASE(ATX_COMB_W_TO_WZ, 3);
-        ATX_COMB_CASE(ATX_COMB_WZ_TO_W, 3);
-        ATX_COMB_CASE(ATX_COMB_SUB, 2);
-        ATX_COMB_CASE(ATX_COMB_XY_TO_POLAR, 2);
-        ATX_COMB_CASE(ATX_COMB_POLAR_TO_XY, 2);
-        ATX_COMB_CASE(ATX_COMB_OPERA_CLIP, 2);
-        ATX_COMB_CASE(ATX_COMB_OPERA_PREPROCESS, 3);
-        ATX_COMB_CASE(ATX_COMB_ORAS6, 2);
-        ATX_COMB_CASE(ATX_COMB_LOOKUP, 1);
-        ATX_COMB_CASE(ATX_COMB_R_TO_D, 2);
-        ATX_COMB_CASE(ATX_COMB_D_TO_R, 2);
-        ATX_COMB_CASE(ATX_COMB_Q_TO_R, 3);
-        ATX_COMB_CASE(ATX_COMB_R_TO_Q, 3);
-        ATX_COMB_CASE(ATX_COMB_Q_TO_D, 2);
-        ATX_COMB_CASE(ATX_COMB_D_TO_Q, 2);
-        default:  // ATX_COMB_SUM
-            if (vec_ok) {
-                if (n_in <= 1) ATX_COMB_LAUNCH(VEC, 1, ATX_COMB_SUM);
-                else if (n_in == 2) ATX_COMB_LAUNCH(VEC, 2, ATX_COMB_SUM);
-                else if (n_in == 3) ATX_COMB_LAUNCH(VEC, 3, ATX_COMB_SUM);
-                else ATX_COMB_LAUNCH(VEC, ATX_COMB_MAX_INPUTS, ATX_COMB_SUM);
-            } else {
-                if (n_in <= 1) ATX_COMB_LAUNCH(1, 1, ATX_COMB_SUM);
-                else if (n_in == 2) ATX_COMB_LAUNCH(1, 2, ATX_COMB_SUM);
-                else if (n_in == 3) ATX_COMB_LAUNCH(1, 3, ATX_COMB_SUM);
-                else ATX_COMB_LAUNCH(1, ATX_COMB_MAX_INPUTS, ATX_COMB_SUM);
-            }
-            break;
-    }
-#undef ATX_COMB_CASE
+            if constexpr (comb_op(OP).bound() > 0) ATX_COMB_LAUNCH(comb_op(OP).bound());  // (n_in validated by the caller)
+            else if (n_in <= 1) ATX_COMB_LAUNCH(1);
+            else if (n_in == 2) ATX_COMB_LAUNCH(2);
+            else if (n_in == 3) ATX_COMB_LAUNCH(3);
+            else ATX_COMB_LAUNCH(ATX_COMB_MAX_INPUTS);
 #undef ATX_COMB_LAUNCH
+        });
+    });
     ATX_LAUNCH_CHECK("combine_stack");
     return ATX_OK;
 }
@@ -526,21 +476,18 @@ using namespace atx;
 extern "C" int atx_combine_stack(int op, const void* const* inputs, int32_t n_in, void* const* outputs, int32_t n_out,
                                  int64_t n_pts, int64_t n_lev, int64_t pitch, int dtype, int layout,
                                  const double* level_param, int32_t flags, void* stream) {
-    static const int kIn[ATX_COMB_COUNT_] = {2, 2, 1, 2, 3, 3, -1, 2, 2, 2, 2, 3, 2, 1, 2, 2, -2, -2, 2, 2};  // -1: any number, -2: two or three
-    static const int kOut[ATX_COMB_COUNT_] = {1, 1, 2, 1, 1, 1, 1, 1, 2, 2, 2, 2, 1, 1, 1, 1, 1, 1, 1, 1};
     ATX_REQUIRE(op >= 0 && op < ATX_COMB_COUNT_, ATX_EINVAL, "atx_combine_stack: bad operator %d", op);
     ATX_REQUIRE(inputs && outputs, ATX_EINVAL, "atx_combine_stack: null pointer table");
     ATX_REQUIRE(n_in >= 1 && n_in <= ATX_COMB_MAX_INPUTS, ATX_EINVAL, "atx_combine_stack: n_in=%d outside [1, %d]", n_in, ATX_COMB_MAX_INPUTS);
-    ATX_REQUIRE(kIn[op] < 0 || kIn[op] == n_in, ATX_EINVAL, "atx_combine_stack: operator %d takes %d inputs, got %d", op, kIn[op], n_in);
-    ATX_REQUIRE(kIn[op] != -2 || n_in == 2 || n_in == 3, ATX_EINVAL, "atx_combine_stack: operator %d takes 2 or 3 inputs, got %d", op, n_in);
-    ATX_REQUIRE(kOut[op] == n_out, ATX_EINVAL, "atx_combine_stack: operator %d gives %d outputs, got %d", op, kOut[op], n_out);
+    const CombOp what = comb_op(op);
+    ATX_REQUIRE(what.n_in < 0 || what.n_in == n_in, ATX_EINVAL, "atx_combine_stack: operator %d takes %d inputs, got %d", op, what.n_in, n_in);
+    ATX_REQUIRE(what.n_in != kTwoOrThree || n_in == 2 || n_in == 3, ATX_EINVAL, "atx_combine_stack: operator %d takes 2 or 3 inputs, got %d", op, n_in);
+    ATX_REQUIRE(what.n_out == n_out, ATX_EINVAL, "atx_combine_stack: operator %d gives %d outputs, got %d", op, what.n_out, n_out);
     ATX_REQUIRE(dtype == ATX_F32 || dtype == ATX_F64, ATX_EINVAL, "atx_combine_stack: bad dtype %d", dtype);
     ATX_REQUIRE(layout == ATX_COLUMNS || layout == ATX_FIELDS, ATX_EINVAL, "atx_combine_stack: bad layout %d", layout);
     ATX_REQUIRE(n_pts >= 0 && n_lev > 0 && n_lev <= INT32_MAX, ATX_EINVAL, "atx_combine_stack: bad sizes");
     ATX_REQUIRE(pitch >= (layout == ATX_COLUMNS ? n_lev : n_pts), ATX_ESHAPE, "atx_combine_stack: pitch %lld too small", (long long)pitch);
-    const bool reads_param = op == ATX_COMB_W_TO_WZ || op == ATX_COMB_WZ_TO_W || (op >= ATX_COMB_OPERA_CLIP && op <= ATX_COMB_LOOKUP) ||
-                             ((op == ATX_COMB_Q_TO_R || op == ATX_COMB_R_TO_Q) && n_in == 2);
-    ATX_REQUIRE(level_param || !reads_param, ATX_EINVAL, "atx_combine_stack: operator %d needs level_param", op);
+    ATX_REQUIRE(level_param || !what.needs_param(n_in), ATX_EINVAL, "atx_combine_stack: operator %d needs level_param", op);
     CombArgs a{};
     for (int k = 0; k < n_in; ++k) {
         ATX_REQUIRE(inputs[k] || n_pts == 0, ATX_EINVAL, "atx_combine_stack: null input %d", k);  // (an empty stack may have no storage)

@@ -3,21 +3,20 @@
 // engine's native HBM layout).
 //
 // A workgroup moves TP points x LC levels through LDS.  On the FIELDS side a wave
-// touches 256 contiguous bytes of one level (35 KB LDS tiles, 4 workgroups per CU: measured best;
-// 128-B tiles -5 %, 512-B tiles -30 %); on the COLUMNS side the TP columns of
+// touches kTpBytes contiguous bytes of one level (35 KB LDS tiles, 4 workgroups per CU);
+// on the COLUMNS side the TP columns of
 // the tile form one contiguous TP*pitch run, swept by consecutive lanes.  The LDS
 // tile is [point][level] with an odd row length (in 4-byte words for f32) so both
 // phases are bank-conflict free for f32 and at most 2-way for f64.
+// What decided the tile, the access kinds and the routes: HISTORY.md, "The combine and relayout kernels' A/B knobs, frozen".
 #include "atx_common.hpp"
 
 namespace atx {
 
-// global accesses of the transposes: every element is read once and written once.  Non-temporal accesses measured in round 3
-// (profiles/r03_relayout_nt_experiment.log): towards columns +6 % f32 / +3 % f64 (1.32 -> 1.25 ms, 2.64 -> 2.55 ms), towards fields
-// -10 % / -2 % (that direction runs on 4-byte accesses) — so they are used towards columns only.
-#ifndef ATX_TP_NT
-#define ATX_TP_NT 1
-#endif
+constexpr int kTpBytes = 256;  // contiguous bytes per level of a tile on the fields side
+
+// global accesses of the transposes: every element is read once and written once.  They are non-temporal towards columns only (NT =
+// TO_COLUMNS): the other direction, which runs on 4-byte accesses, loses with them.
 template <bool NT, typename X>
 __device__ __forceinline__ X tp_load(const X* p) {
     if constexpr (NT) return __builtin_nontemporal_load(p);
@@ -30,22 +29,13 @@ __device__ __forceinline__ void tp_store(X* p, X v) {
 }
 template <bool NT, typename T, int N>
 __device__ __forceinline__ Pack<T, N> tp_load_vec(const T* p) {
-    if constexpr (NT && N > 1) {
-        typedef T NV __attribute__((ext_vector_type(N)));
-        NV v = __builtin_nontemporal_load(reinterpret_cast<const NV*>(p));
-        return *reinterpret_cast<Pack<T, N>*>(&v);
-    } else {
-        return *reinterpret_cast<const Pack<T, N>*>(p);
-    }
+    if constexpr (NT) return pw_load_nt<T, N>(p);
+    else return *reinterpret_cast<const Pack<T, N>*>(p);
 }
 template <bool NT, typename T, int N>
 __device__ __forceinline__ void tp_store_vec(T* p, const Pack<T, N>& v) {
-    if constexpr (NT && N > 1) {
-        typedef T NV __attribute__((ext_vector_type(N)));
-        __builtin_nontemporal_store(*reinterpret_cast<const NV*>(&v), reinterpret_cast<NV*>(p));
-    } else {
-        *reinterpret_cast<Pack<T, N>*>(p) = v;
-    }
+    if constexpr (NT) pw_store_nt<T, N>(p, v);
+    else *reinterpret_cast<Pack<T, N>*>(p) = v;
 }
 
 // (p, l) of item i = p * nl + l advanced by kBlock items without a division per element (nl is a run-time 137: the quotient and
@@ -71,12 +61,12 @@ transpose_kernel(const T* __restrict__ src, T* __restrict__ dst, int64_t n_pts, 
 #pragma unroll 4
         for (int i = tid; i < nl * TP; i += kBlock) {
             const int l = i / TP, p = i - l * TP;  // (TPC > 0: a shift and a mask)
-            if (p < np) tile[p * LCpad + l] = tp_load<TO_COLUMNS && ATX_TP_NT>(src + (int64_t)(l0 + l) * src_pitch + p0 + p);
+            if (p < np) tile[p * LCpad + l] = tp_load<TO_COLUMNS>(src + (int64_t)(l0 + l) * src_pitch + p0 + p);
         }
         __syncthreads();
         int p = tid / nl, l = tid - p * nl;
         for (int i = tid; i < np * nl; i += kBlock) {
-            tp_store<TO_COLUMNS && ATX_TP_NT>(dst + (p0 + p) * dst_pitch + l0 + l, tile[p * LCpad + l]);
+            tp_store<TO_COLUMNS>(dst + (p0 + p) * dst_pitch + l0 + l, tile[p * LCpad + l]);
             p += dq;
             l += dr;
             if (l >= nl) {
@@ -88,7 +78,7 @@ transpose_kernel(const T* __restrict__ src, T* __restrict__ dst, int64_t n_pts, 
         int p = tid / nl, l = tid - p * nl;
 #pragma unroll 4
         for (int i = tid; i < np * nl; i += kBlock) {
-            tile[p * LCpad + l] = tp_load<TO_COLUMNS && ATX_TP_NT>(src + (p0 + p) * src_pitch + l0 + l);
+            tile[p * LCpad + l] = tp_load<TO_COLUMNS>(src + (p0 + p) * src_pitch + l0 + l);
             p += dq;
             l += dr;
             if (l >= nl) {
@@ -99,7 +89,7 @@ transpose_kernel(const T* __restrict__ src, T* __restrict__ dst, int64_t n_pts, 
         __syncthreads();
         for (int i = tid; i < nl * TP; i += kBlock) {
             const int lv = i / TP, pp = i - lv * TP;
-            if (pp < np) tp_store<TO_COLUMNS && ATX_TP_NT>(dst + (int64_t)(l0 + lv) * dst_pitch + p0 + pp, tile[pp * LCpad + lv]);
+            if (pp < np) tp_store<TO_COLUMNS>(dst + (int64_t)(l0 + lv) * dst_pitch + p0 + pp, tile[pp * LCpad + lv]);
         }
     }
 }
@@ -132,7 +122,7 @@ transpose_vec_kernel(const T* __restrict__ src, T* __restrict__ dst, int64_t n_p
             const int l = i / PV, pv = i - l * PV;
             const int p = pv * VEC;
             if (p + VEC <= np) {
-                const V v = tp_load_vec<TO_COLUMNS && ATX_TP_NT, T, VEC>(src + (int64_t)(l0 + l) * fields_pitch + p0 + p);
+                const V v = tp_load_vec<TO_COLUMNS, T, VEC>(src + (int64_t)(l0 + l) * fields_pitch + p0 + p);
 #pragma unroll
                 for (int e = 0; e < VEC; ++e) tile[(p + e) * LCpad + l] = v.v[e];
             } else {
@@ -146,12 +136,12 @@ transpose_vec_kernel(const T* __restrict__ src, T* __restrict__ dst, int64_t n_p
             V v;
 #pragma unroll
             for (int e = 0; e < VEC; ++e) v.v[e] = (c * VEC + e < nl) ? tile[p * LCpad + c * VEC + e] : T(0);
-            tp_store_vec<TO_COLUMNS && ATX_TP_NT, T, VEC>(dst + (p0 + p) * cols_pitch + l0 + c * VEC, v);
+            tp_store_vec<TO_COLUMNS, T, VEC>(dst + (p0 + p) * cols_pitch + l0 + c * VEC, v);
         }
     } else {
         for (int i = tid; i < np * CV; i += kBlock) {
             const int p = i / CV, c = i - p * CV;
-            const V v = tp_load_vec<TO_COLUMNS && ATX_TP_NT, T, VEC>(src + (p0 + p) * cols_pitch + l0 + c * VEC);
+            const V v = tp_load_vec<TO_COLUMNS, T, VEC>(src + (p0 + p) * cols_pitch + l0 + c * VEC);
 #pragma unroll
             for (int e = 0; e < VEC; ++e)
                 if (c * VEC + e < nl) tile[p * LCpad + c * VEC + e] = v.v[e];
@@ -164,7 +154,7 @@ transpose_vec_kernel(const T* __restrict__ src, T* __restrict__ dst, int64_t n_p
                 V v;
 #pragma unroll
                 for (int e = 0; e < VEC; ++e) v.v[e] = tile[(p + e) * LCpad + l];
-                tp_store_vec<TO_COLUMNS && ATX_TP_NT, T, VEC>(dst + (int64_t)(l0 + l) * fields_pitch + p0 + p, v);
+                tp_store_vec<TO_COLUMNS, T, VEC>(dst + (int64_t)(l0 + l) * fields_pitch + p0 + p, v);
             } else {
                 for (int e = 0; e < VEC; ++e)
                     if (p + e < np) dst[(int64_t)(l0 + l) * fields_pitch + p0 + p + e] = tile[(p + e) * LCpad + l];
@@ -199,42 +189,31 @@ static int relayout_typed(const void* src_, void* dst_, int64_t n_pts, int n_lev
         ATX_LAUNCH_CHECK("pitched_copy");
         return ATX_OK;
     }
-#ifndef ATX_TP_BYTES
-#define ATX_TP_BYTES 256  // re-measured with the vector kernel (137 levels of O1280, ms c->f / f->c): 128 B: 1.65 / 1.47 f32, 2.69 / 2.92 f64;
-#endif                    // 256 B: 1.59-1.66 / 1.32-1.44 f32, 2.52 / 2.66 f64; 384 B and 512 B slower (LDS tiles cut the occupancy)
-    const int TP = ATX_TP_BYTES / (int)sizeof(T);  // contiguous bytes per level on the fields side
-#ifndef ATX_TP_LC
-#define ATX_TP_LC 0  // levels per tile; 0: all of them up to 160, else 128
-#endif
-    int LC = ATX_TP_LC > 0 ? (n_lev < ATX_TP_LC ? n_lev : ATX_TP_LC) : (n_lev < 160 ? n_lev : 128);
+    constexpr int TP = kTpBytes / (int)sizeof(T);  // points per tile: a power of two, which the scalar kernel takes as a template argument
+    static_assert(TP > 0 && (TP & (TP - 1)) == 0, "transpose_kernel<T, ., TP> divides by shifts");
+    const int LC = n_lev < 160 ? n_lev : 128;  // levels per tile: all of them up to 160, else 128
     const int LCpad = LC | 1;
     const size_t lds = (size_t)TP * LCpad * sizeof(T);
     const unsigned gx = (unsigned)((n_pts + TP - 1) / TP);
     const unsigned gy = (unsigned)((n_lev + LC - 1) / LC);
     ATX_REQUIRE(gy <= 65535, ATX_ENOTIMPL, "atx_relayout: too many level chunks");
-#ifndef ATX_TP_VEC
-#define ATX_TP_VEC 1
-#endif
     {
         constexpr int VEC = Vec16<T>::N;
         const int64_t cols_pitch = dst_layout == ATX_COLUMNS ? dp : sp, fields_pitch = dst_layout == ATX_COLUMNS ? sp : dp;
         const int64_t covered = ((int64_t)(n_lev + VEC - 1) / VEC) * VEC;
-        const bool vec = ATX_TP_VEC && aligned16(src_) && aligned16(dst_) && cols_pitch % VEC == 0 && fields_pitch % VEC == 0 &&
+        const bool vec = aligned16(src_) && aligned16(dst_) && cols_pitch % VEC == 0 && fields_pitch % VEC == 0 &&
                          covered <= cols_pitch && (gy == 1 || LC % VEC == 0) && TP % VEC == 0;
-        // measured (137 levels of O1280): towards columns 2.14 -> 1.44 ms f32, 3.20 -> 2.89 ms f64; towards fields the scalar
-        // kernel is as fast (f32) or faster (f64: 2.69 vs 3.16 ms), so only the columns direction takes the vector kernel
+        // only the columns direction takes the vector kernel: towards fields the scalar kernel is as fast (f32) or faster (f64)
         if (vec && dst_layout == ATX_COLUMNS) {
             hipLaunchKernelGGL((transpose_vec_kernel<T, true>), dim3(gx, gy), dim3(kBlock), lds, st, src, dst, n_pts, n_lev, sp, dp, TP, LC, LCpad);
             ATX_LAUNCH_CHECK("transpose_vec");
             return ATX_OK;
         }
     }
-    constexpr int kTileBytes = ATX_TP_BYTES;
-    constexpr int TPC = (kTileBytes / (int)sizeof(T)) > 0 && ((kTileBytes / (int)sizeof(T)) & ((kTileBytes / (int)sizeof(T)) - 1)) == 0 ? kTileBytes / (int)sizeof(T) : 0;
     if (dst_layout == ATX_COLUMNS)
-        hipLaunchKernelGGL((transpose_kernel<T, true, TPC>), dim3(gx, gy), dim3(kBlock), lds, st, src, dst, n_pts, n_lev, sp, dp, TP, LC, LCpad);
+        hipLaunchKernelGGL((transpose_kernel<T, true, TP>), dim3(gx, gy), dim3(kBlock), lds, st, src, dst, n_pts, n_lev, sp, dp, TP, LC, LCpad);
     else
-        hipLaunchKernelGGL((transpose_kernel<T, false, TPC>), dim3(gx, gy), dim3(kBlock), lds, st, src, dst, n_pts, n_lev, sp, dp, TP, LC, LCpad);
+        hipLaunchKernelGGL((transpose_kernel<T, false, TP>), dim3(gx, gy), dim3(kBlock), lds, st, src, dst, n_pts, n_lev, sp, dp, TP, LC, LCpad);
     ATX_LAUNCH_CHECK("transpose");
     return ATX_OK;
 }
@@ -351,11 +330,10 @@ select_fields_kernel(const T* __restrict__ src, T* __restrict__ dst, LevelMap ma
     // a row copy: 16 bytes per lane when both rows start on a 16-byte boundary (4-byte accesses ran a float32 row at 0.62 of the HBM
     // peak against 0.74 for float64; round 4), the <= VEC - 1 trailing points element by element
     constexpr int VEC = Vec16<T>::N;
-    using V = Pack<T, VEC>;
     if (((reinterpret_cast<uintptr_t>(s) | reinterpret_cast<uintptr_t>(d)) & 15u) == 0) {
         const int64_t nv = n_pts / VEC;
         for (int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x; v < nv; v += (int64_t)gridDim.x * kBlock)
-            tp_store_vec<true, T, VEC>(d + v * VEC, tp_load_vec<true, T, VEC>(s + v * VEC));  // read once, written once: non-temporal
+            pw_store_nt<T, VEC>(d + v * VEC, pw_load_nt<T, VEC>(s + v * VEC));  // read once, written once: non-temporal
         for (int64_t p = nv * VEC + (int64_t)blockIdx.x * kBlock + threadIdx.x; p < n_pts; p += (int64_t)gridDim.x * kBlock) d[p] = s[p];
         return;
     }
@@ -398,10 +376,7 @@ static int select_typed(const void* src_, void* dst_, const int32_t* level_map, 
             const int W = (lmax + VEC) / VEC * VEC - lo;
             const bool aligned = aligned16(src) && aligned16(dst) && sp % VEC == 0 && dp % VEC == 0 && (int64_t)lo + W <= sp && j0 % VEC == 0 &&
                                  (int64_t)j0 + ((nj + VEC - 1) / VEC) * VEC <= dp;
-#ifndef ATX_SELECT_SLAB
-#define ATX_SELECT_SLAB 1
-#endif
-            if (ATX_SELECT_SLAB && aligned && lines > 0 && (int64_t)W * (int64_t)sizeof(T) * 10 <= (int64_t)lines * 128 * 13) {
+            if (aligned && lines > 0 && (int64_t)W * (int64_t)sizeof(T) * 10 <= (int64_t)lines * 128 * 13) {
                 const int wpad = (W % 32 == 0) ? W + VEC : W;  // rows a multiple of 128 bytes apart would put a column of the tile into one LDS bank
                 int tps = (int)((32 * 1024 - (size_t)nj * sizeof(int32_t)) / ((size_t)wpad * sizeof(T)));
                 tps = tps > 64 ? 64 : (tps < 1 ? 1 : tps);

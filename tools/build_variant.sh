@@ -2,8 +2,9 @@
 # Build an A/B variant of libatx.so into anemoi-transform_amd/lib/variants/ (git-ignored, travels to the GPU box).
 #   bash tools/build_variant.sh NAME [-DATX_KNOB=VALUE ...]          current sources with extra defines
 #   bash tools/build_variant.sh NAME --rev <git-rev> [-D...]          the csrc/ + include/ of an earlier commit
-# The knobs that are left are those of atx_combine.hip, atx_relayout.hip and atx_common.hpp.  The per-point and the gather kernels' knobs
-# are frozen (HISTORY.md): their other sides need a --rev build of a commit that still had them (402a730 for the gather).
+# The knobs that are left choose the math routes (ATX_FAST_EXP, ATX_FAST_LOG, ATX_FAST_SINCOS, ATX_SNOW_TANH, ATX_FMA_SGPR, ATX_SINCOS_FMA) and
+# the grid cap (ATX_MAX_GRID).  The per-point, the gather, the combine and the relayout kernels' knobs are frozen (HISTORY.md): their other
+# sides need a --rev build of a commit that still had them (402a730 for the gather, e6acba1 for combine and relayout).
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 NAME=$1; shift

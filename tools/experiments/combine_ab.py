@@ -4,7 +4,11 @@
     python tools/experiments/combine_ab.py --libs head=anemoi-transform_amd/lib/libatx.so u1=anemoi-transform_amd/lib/variants/libatx_c_u1.so ...
 
 Cases: difference (2 -> 1), cos+sin (1 -> 2), snow_cover (2 -> 1) on a field with snow in regions and with a thin cover everywhere
-(tanh on every element), w_to_wz (3 -> 1); float32 and float64.  atx_stream_copy of one stack is the yardstick."""
+(tanh on every element), w_to_wz (3 -> 1); float32 and float64.  atx_stream_copy of one stack is the yardstick.
+
+The switches this swept (ATX_COMB_U_F32 / _F64 / _OPERA, ATX_COMB_CAP_F64, ATX_COMB_NT, ATX_COMB_NT_LOAD, ATX_COMB_ASSIGN, ATX_COMB_INT_DIV,
+ATX_HUMIDITY_IEEE_DIV) are frozen — HISTORY.md, "The combine and relayout kernels' A/B knobs, frozen"; their other sides need a
+`bash tools/build_variant.sh NAME --rev e6acba1 -DATX_COMB_...=VALUE` build."""
 
 from __future__ import annotations
 

@@ -1,5 +1,8 @@
 #!/usr/bin/env python3
-"""atx_relayout both ways over 137 levels of O1280 — run once per library build (tile shapes: ATX_TP_BYTES, ATX_TP_LC)."""
+"""atx_relayout both ways over 137 levels of O1280 — run once per library build (tile shapes: ATX_TP_BYTES, ATX_TP_LC).
+Both switches, ATX_TP_NT and ATX_TP_VEC are frozen (HISTORY.md, "The combine and relayout kernels' A/B knobs, frozen"): another tile needs a
+`bash tools/build_variant.sh NAME --rev e6acba1 -DATX_TP_BYTES=... -DATX_TP_LC=...` build, run with
+ATX_LIBRARY=anemoi-transform_amd/lib/variants/libatx_NAME.so."""
 from __future__ import annotations
 
 import os

@@ -1,5 +1,8 @@
 #!/usr/bin/env python3
-"""atx_select_levels on a 137-level O1280 column stack: every other level, the first 68, one level — median HIP-event time and bit-equality."""
+"""atx_select_levels on a 137-level O1280 column stack: every other level, the first 68, one level — median HIP-event time and bit-equality.
+The slab route it was written to judge is fixed (ATX_SELECT_SLAB is frozen at 1 — HISTORY.md, "The combine and relayout kernels' A/B knobs,
+frozen"); the element-by-element kernel on every map needs a `bash tools/build_variant.sh noslab --rev e6acba1 -DATX_SELECT_SLAB=0` build, run
+with ATX_LIBRARY=anemoi-transform_amd/lib/variants/libatx_noslab.so."""
 from __future__ import annotations
 
 import os

@@ -56,7 +56,9 @@ def main():
                     "atx_reduce.hip), each with a checksum of what it computed on the seeded stack")
     ap.add_argument("--only-regrid", action="store_true", help="only the gather rows (atx_regrid_columns.inc, atx_regrid_fields.inc), each with a "
                     "checksum of what one call writes into a zeroed output stack")
-    ap.add_argument("--lib", nargs="+", default=[], metavar="NAME=PATH", help="with --only-regrid: time these builds of libatx.so side by side in "
+    ap.add_argument("--only-combine", action="store_true", help="only the multi-input, layout and level-selection rows (atx_combine.hip, atx_relayout.hip), "
+                    "each with a checksum of what one call writes into zeroed outputs")
+    ap.add_argument("--lib", nargs="+", action="extend", default=[], metavar="NAME=PATH", help="with --only-regrid or --only-combine: time these builds of libatx.so side by side in "
                     "one process, alternating, --rounds rounds (the first one is the reference)")
     ap.add_argument("--rounds", type=int, default=8)
     args = ap.parse_args()
@@ -289,7 +291,10 @@ def main():
             torch.cuda.empty_cache()
 
     def checksum(out):
-        """Order-sensitive 128-bit checksum of a tensor's bytes, summed on the device in wrapping int64; anything else by its repr."""
+        """Order-sensitive 128-bit checksum of a tensor's bytes, summed on the device in wrapping int64 (of several tensors: one after
+        the other); anything else by its repr."""
+        if isinstance(out, (list, tuple)):
+            return "".join(checksum(o) for o in out)
         if not torch.is_tensor(out):
             return repr(out)
         w = out.contiguous().view(-1).view(torch.int32 if out.element_size() == 4 else (torch.int64 if out.element_size() == 8 else torch.uint8))
@@ -363,12 +368,45 @@ def main():
         del f, g
         torch.cuda.empty_cache()
 
+    def side_by_side(rows, libs, rounds):
+        """rows: (name, call, one_call, algorithmic bytes, note).  Every library times every row in each of `rounds` rounds, one process,
+        after one round that is thrown away (code objects, clocks), the libraries alternating and taking turns to go first; the
+        per-round medians go to `<name>_ms`, and the digests of one_call() must agree."""
+        times = {(name, lib): [] for name, *_ in rows for lib in libs}
+        before = native.use_library(None)
+        for r in range(rounds + 1):
+            for lib in (list(libs) if r % 2 else list(libs)[::-1]):
+                native.use_library(libs[lib])
+                for name, call, *_ in rows:
+                    ms = timeit(call)
+                    if r:  # round 0 warms up
+                        times[name, lib].append(ms)
+        for name, call, one_call, alg_bytes, note in rows:
+            digests = {}
+            for lib, handle in libs.items():
+                native.use_library(handle)
+                digests[lib] = checksum(one_call())
+            ref, *others = libs
+            lo, hi = min(times[name, ref]), max(times[name, ref])
+            res[name] = {"algorithmic_bytes": alg_bytes, "note": note, "digest": digests[ref], "digests_equal": len(set(digests.values())) == 1}
+            line = f"{name:74s}"
+            for lib in libs:
+                med = float(np.median(times[name, lib]))
+                res[name][f"{lib}_ms"] = times[name, lib]
+                res[name][f"{lib}_median_ms"] = med
+                line += f" {lib} {med:8.4f}"
+            for lib in others:
+                med = res[name][f"{lib}_median_ms"]
+                res[name][f"{lib}_minus_{ref}_pct"] = 100.0 * (med / res[name][f"{ref}_median_ms"] - 1.0)
+                res[name][f"{lib}_within_{ref}_spread"] = bool(lo <= med <= hi)
+                line += f"  {res[name][f'{lib}_minus_{ref}_pct']:+5.2f} %  in [{lo:.4f}, {hi:.4f}]: {lo <= med <= hi}"
+            print(line + ("" if res[name]["digests_equal"] else "  DIGESTS DIFFER"), flush=True)
+        native.use_library(before)
+
     def regrid_rows(tdt, B, tag, x, idx, w, libs=None, rounds=1):
         """The rows that run kernels of atx_regrid_columns.inc and atx_regrid_fields.inc, on the seeded stack `x`.  `digest` is the
         checksum of what ONE call of the row writes into an output stack zeroed first (padding slots are never written).  With
-        `libs` ({name: handle}, the first one the reference): every library times every row in each of `rounds` rounds, one
-        process, after one round that is thrown away (code objects, clocks), the libraries alternating and taking turns to go
-        first; the per-round medians go to `<name>_ms` and the digests must agree.  (This mode keeps every plan alive until the end.)"""
+        `libs` ({name: handle}, the first one the reference): side_by_side() over all rows.  (This mode keeps every plan alive until the end.)"""
         from anemoi_transform_amd.gather import target_order_for
 
         rows = []
@@ -460,36 +498,112 @@ def main():
 
         if not libs:
             return
-        times = {(name, lib): [] for name, *_ in rows for lib in libs}
-        before = native.use_library(None)
-        for r in range(rounds + 1):
-            for lib in (list(libs) if r % 2 else list(libs)[::-1]):
-                native.use_library(libs[lib])
-                for name, call, *_ in rows:
-                    ms = timeit(call)
-                    if r:  # round 0 warms up
-                        times[name, lib].append(ms)
-        for name, call, one_call, alg_bytes, note in rows:
-            digests = {}
-            for lib, handle in libs.items():
-                native.use_library(handle)
-                digests[lib] = checksum(one_call())
-            ref, *others = libs
-            lo, hi = min(times[name, ref]), max(times[name, ref])
-            res[name] = {"algorithmic_bytes": alg_bytes, "note": note, "digest": digests[ref], "digests_equal": len(set(digests.values())) == 1}
-            line = f"{name:74s}"
-            for lib in libs:
-                med = float(np.median(times[name, lib]))
-                res[name][f"{lib}_ms"] = times[name, lib]
-                res[name][f"{lib}_median_ms"] = med
-                line += f" {lib} {med:8.4f}"
-            for lib in others:
-                med = res[name][f"{lib}_median_ms"]
-                res[name][f"{lib}_minus_{ref}_pct"] = 100.0 * (med / res[name][f"{ref}_median_ms"] - 1.0)
-                res[name][f"{lib}_within_{ref}_spread"] = bool(lo <= med <= hi)
-                line += f"  {res[name][f'{lib}_minus_{ref}_pct']:+5.2f} %  in [{lo:.4f}, {hi:.4f}]: {lo <= med <= hi}"
-            print(line + ("" if res[name]["digests_equal"] else "  DIGESTS DIFFER"), flush=True)
-        native.use_library(before)
+        side_by_side(rows, libs, rounds)
+
+    def combine_rows(tdt, B, tag, x, libs=None, rounds=1):
+        """The rows that run kernels of atx_combine.hip and atx_relayout.hip (multi-input operators, layout conversion, level
+        selection), on the seeded stack `x`.  `digest` is the checksum of what ONE call of the row writes into outputs zeroed first.
+        With `libs`: side_by_side() over each block of rows as it comes, so that a block's operands are freed before the next one's."""
+        gen = torch.Generator(device=dev).manual_seed(L)
+        rand = lambda *shape: torch.rand(shape, device=dev, generator=gen)  # noqa: E731
+        stack_bytes = n_src * L * B
+        rows = []
+
+        def row(name, fn, outs, alg_bytes, note=""):
+            def one_call():
+                for o in outs:
+                    o.zero_()
+                fn()
+                return outs
+
+            rows.append((name, fn, one_call, alg_bytes, note))
+
+        def combine(name, op, ins, outs, alg_bytes, note="", n_lev=L, **kw):
+            row(f"combine {name} {tag}", lambda: native.combine_stack(op, ins, outs, n_pts=n_src, n_lev=n_lev, pitch=outs[0].stride(0), layout=COLUMNS, **kw),
+                outs, alg_bytes, note)
+
+        def finish():
+            if libs:
+                side_by_side(rows, libs, rounds)
+            else:
+                for name, fn, one_call, alg_bytes, note in rows:
+                    record(name, timeit(fn), alg_bytes, note)
+                    res[name]["digest"] = checksum(one_call())
+            rows.clear()
+            torch.cuda.empty_cache()
+
+        y, z = x.new_like(), x.new_like()
+        y.data.copy_(x.data)
+        # snow depth (m of water equivalent) and density as they occur — in REGIONS, as on a real field (points are stored by
+        # latitude): ~55 % of the points bare (sd = 0), ~35 % deep snow, ~10 % a thin cover where tanh really has to be evaluated;
+        # density 100-400 kg/m3
+        sd, thin, rsn = x.new_like(), x.new_like(), x.new_like()
+        u = (torch.arange(n_src, device=dev, dtype=torch.float64) / n_src).unsqueeze(1).expand(n_src, L)
+        sd.data[:, :L] = torch.where(u < 0.55, torch.zeros_like(u), torch.where(u < 0.9, 0.05 + u, 1e-4 * u)).to(tdt)
+        rsn.data[:, :L] = (100.0 + 300.0 * rand(n_src, L)).to(tdt)
+        thin.data.fill_(1e-5)  # 4000 * (1000 * 1e-5 / rsn) / rsn < 2.65 everywhere: tanh on every element
+        del u
+        combine("snow_cover (2->1)", native.COMB_SNOW_COVER, [sd.data, rsn.data], [z.data], 3 * stack_bytes, "regions: 55 % bare, 35 % deep snow, 10 % thin cover (tanh evaluated)")
+        combine("snow_cover (2->1), thin cover everywhere", native.COMB_SNOW_COVER, [thin.data, rsn.data], [z.data], 3 * stack_bytes, "worst case: tanh evaluated on every element")
+        combine("difference (2->1, accum_to_interval)", native.COMB_SUB, [x.data, y.data], [z.data], 3 * stack_bytes)
+        finish()
+        del sd, thin, rsn
+        combine("cos_sin (1->2)", native.COMB_COS_SIN, [x.data], [y.data, z.data], 3 * stack_bytes)
+        finish()  # (y holds cos x from here on)
+        # ---- the numpy-only domain filters (filters/domain.py)
+        lim = torch.full((L,), 10000.0, dtype=torch.float64, device=dev)
+        w2, dm = x.new_like(), x.new_like()
+        dm.data[:, :L] = torch.randint(0, 4, (n_src, L), device=dev, generator=gen).to(tdt)
+        combine("opera_clipping (2->2)", native.COMB_OPERA_CLIP, [x.data, y.data], [z.data, w2.data], 4 * stack_bytes, level_param=lim)
+        combine("opera_preprocessing (3->2)", native.COMB_OPERA_PREPROCESS, [x.data, y.data, dm.data], [z.data, w2.data], 5 * stack_bytes, level_param=lim)
+        finish()
+        del dm, w2
+        # humidity conversions: q in [1e-6, 2e-2], t in [190, 320] K — water, mixed and ice branches of the saturation curve all present
+        qh, th = x.new_like(), x.new_like()
+        qh.data[:, :L] = (10.0 ** (-6.0 + 4.3 * rand(n_src, L))).to(tdt)
+        th.data[:, :L] = (190.0 + 130.0 * rand(n_src, L)).to(tdt)
+        plev = torch.linspace(1.0, 1000.0, L, dtype=torch.float64, device=dev)
+        combine("q_to_r (2->1)", native.COMB_Q_TO_R, [qh.data, th.data], [z.data], 3 * stack_bytes, "one or two exp per element (mixed phase)", level_param=plev)
+        combine("r_to_d (2->1)", native.COMB_R_TO_D, [y.data, th.data], [z.data], 3 * stack_bytes, "one exp and one log per element")
+        finish()
+        del qh, th
+        # one ORAS6 group: 14 fields and the ice concentration they share
+        o_in, o_out = Stack.empty(n_src, 14, tdt, dev, COLUMNS), Stack.empty(n_src, 14, tdt, dev, COLUMNS)
+        o_in.data.copy_(torch.randn(o_in.data.shape, device=dev, generator=gen))
+        ice = rand(n_src).to(tdt)
+        kinds = torch.tensor([0, 1, 1, 1, 4, 4, 1, 2, 3, 1, 1, 1, 2, 5], dtype=torch.float64, device=dev)
+        combine("oras6_clipping (14 fields of one date)", native.COMB_ORAS6, [o_in.data, ice], [o_out.data], (2 * 14 + 1) * n_src * B,
+                "one launch per group; the shared ice field is read once per point", n_lev=14, level_param=kinds)
+        cls = Stack.empty(n_src, 1, tdt, dev, COLUMNS)
+        cls.data[:, 0] = torch.randint(0, 21, (n_src,), device=dev, generator=gen).to(tdt)
+        val = cls.new_like()
+        tab = torch.tensor([21.0] + [float(i) for i in range(21)], dtype=torch.float64, device=dev)
+        combine("lookup (land_parameters, 1 field)", native.COMB_LOOKUP, [cls.data], [val.data], 2 * n_src * B, "26 MB / 53 MB: launch-latency sized", n_lev=1, level_param=tab)
+        finish()
+        del o_in, o_out, ice, cls, val, z
+        # ---- layout
+        f = Stack.empty(n_src, L, tdt, dev, FIELDS)
+        row(f"relayout columns->fields {tag}", lambda: native.relayout(x.data, f.data, n_pts=n_src, n_lev=L, src_pitch=x.pitch, dst_pitch=f.pitch,
+            src_layout=COLUMNS, dst_layout=FIELDS), [f.data], 2 * stack_bytes)
+        finish()  # (f holds x from here on)
+        row(f"relayout fields->columns {tag}", lambda: native.relayout(f.data, y.data, n_pts=n_src, n_lev=L, src_pitch=f.pitch, dst_pitch=y.pitch,
+            src_layout=FIELDS, dst_layout=COLUMNS), [y.data], 2 * stack_bytes)
+        # ---- level gather (re-listing / sub-selecting the fields of a stack, operand stacks of the multi-input filters)
+        half, one_lev = Stack.empty(n_src, 68, tdt, dev, COLUMNS), Stack.empty(n_src, 1, tdt, dev, COLUMNS)
+        row(f"select 68 of {L} levels (every other one) {tag}", lambda: native.select_levels(x.data, half.data, list(range(0, L - 1, 2)), n_pts=n_src, n_src_lev=L,
+            src_pitch=x.pitch, dst_pitch=half.pitch, layout=COLUMNS), [half.data], 2 * n_src * 68 * B, "atx_select_levels; the source lines are read whole: 3x the algorithmic bytes")
+        row(f"select 1 of {L} levels {tag}", lambda: native.select_levels(x.data, one_lev.data, [77], n_pts=n_src, n_src_lev=L, src_pitch=x.pitch,
+            dst_pitch=one_lev.pitch, layout=COLUMNS), [one_lev.data], 2 * n_src * B, "one field out of a column stack: a 64-byte sector per point is the least that can move")
+        finish()
+
+    if args.only_combine:
+        libs = {name: native.open_library(os.path.abspath(path)) for name, path in (spec.split("=", 1) for spec in args.lib)}
+        for tdt, B, tag in ((torch.float32, 4, "f32"), (torch.float64, 8, "f64")):
+            combine_rows(tdt, B, tag, bench.synth_stack(src_grid, L, tdt, dev, 0, COLUMNS), libs, args.rounds)
+            torch.cuda.empty_cache()
+        if args.out:
+            json.dump(res, open(args.out, "w"), indent=1)
+        return
 
     if args.only_regrid:
         libs = {name: native.open_library(os.path.abspath(path)) for name, path in (spec.split("=", 1) for spec in args.lib)}
@@ -594,78 +708,10 @@ def main():
         y = x.new_like()
         record(f"(ceiling) torch copy_ of the stack {tag}", timeit(lambda: y.data.copy_(x.data)), 2 * x.data.numel() * B,
                "device-to-device copy of the same bytes: the practical read+write streaming rate")
-        stack_bytes = n_src * L * B
         pointwise_rows(tdt, B, tag, x)
-        # ---- multi-input
-        z = x.new_like()
-        # snow depth (m of water equivalent) and density as they occur — in REGIONS, as on a real field (points are stored by
-        # latitude): ~55 % of the points bare (sd = 0), ~35 % deep snow, ~10 % a thin cover where tanh really has to be evaluated;
-        # density 100-400 kg/m3
-        sd, rsn = x.new_like(), x.new_like()
-        u = (torch.arange(n_src, device=dev, dtype=torch.float64) / n_src).unsqueeze(1).expand(n_src, L)
-        sd.data[:, :L] = torch.where(u < 0.55, torch.zeros_like(u), torch.where(u < 0.9, 0.05 + u, 1e-4 * u)).to(tdt)
-        rsn.data[:, :L] = (100.0 + 300.0 * torch.rand(n_src, L, device=dev)).to(tdt)
-        del u
-        record(f"combine snow_cover (2->1) {tag}", timeit(lambda: native.combine_stack(native.COMB_SNOW_COVER, [sd.data, rsn.data], [z.data],
-               n_pts=n_src, n_lev=L, pitch=x.pitch, layout=COLUMNS)), 3 * stack_bytes, "regions: 55 % bare, 35 % deep snow, 10 % thin cover (tanh evaluated)")
-        sd.data.fill_(1e-5)  # 4000 * (1000 * 1e-5 / rsn) / rsn < 2.65 everywhere: tanh on every element
-        record(f"combine snow_cover (2->1) {tag}, thin cover everywhere", timeit(lambda: native.combine_stack(native.COMB_SNOW_COVER, [sd.data, rsn.data], [z.data],
-               n_pts=n_src, n_lev=L, pitch=x.pitch, layout=COLUMNS)), 3 * stack_bytes, "worst case: tanh evaluated on every element")
-        del sd, rsn
-        record(f"combine difference (2->1, accum_to_interval) {tag}", timeit(lambda: native.combine_stack(native.COMB_SUB, [x.data, y.data], [z.data],
-               n_pts=n_src, n_lev=L, pitch=x.pitch, layout=COLUMNS)), 3 * stack_bytes)
-        record(f"combine cos_sin (1->2) {tag}", timeit(lambda: native.combine_stack(native.COMB_COS_SIN, [x.data], [y.data, z.data],
-               n_pts=n_src, n_lev=L, pitch=x.pitch, layout=COLUMNS)), 3 * stack_bytes)
-        # ---- the numpy-only domain filters (filters/domain.py)
-        lim = torch.full((L,), 10000.0, dtype=torch.float64, device=dev)
-        w2 = x.new_like()
-        record(f"combine opera_clipping (2->2) {tag}", timeit(lambda: native.combine_stack(native.COMB_OPERA_CLIP, [x.data, y.data], [z.data, w2.data],
-               n_pts=n_src, n_lev=L, pitch=x.pitch, layout=COLUMNS, level_param=lim)), 4 * stack_bytes)
-        dm = x.new_like()
-        dm.data[:, :L] = torch.randint(0, 4, (n_src, L), device=dev).to(tdt)
-        record(f"combine opera_preprocessing (3->2) {tag}", timeit(lambda: native.combine_stack(native.COMB_OPERA_PREPROCESS, [x.data, y.data, dm.data], [z.data, w2.data],
-               n_pts=n_src, n_lev=L, pitch=x.pitch, layout=COLUMNS, level_param=lim)), 5 * stack_bytes)
-        del dm, w2
-        # humidity conversions: q in [1e-6, 2e-2], t in [190, 320] K — water, mixed and ice branches of the saturation curve all present
-        qh, th = x.new_like(), x.new_like()
-        qh.data[:, :L] = (10.0 ** (-6.0 + 4.3 * torch.rand(n_src, L, device=dev))).to(tdt)
-        th.data[:, :L] = (190.0 + 130.0 * torch.rand(n_src, L, device=dev)).to(tdt)
-        plev = torch.linspace(1.0, 1000.0, L, dtype=torch.float64, device=dev)
-        record(f"combine q_to_r (2->1) {tag}", timeit(lambda: native.combine_stack(native.COMB_Q_TO_R, [qh.data, th.data], [z.data],
-               n_pts=n_src, n_lev=L, pitch=x.pitch, layout=COLUMNS, level_param=plev)), 3 * stack_bytes, "one or two exp per element (mixed phase)")
-        record(f"combine r_to_d (2->1) {tag}", timeit(lambda: native.combine_stack(native.COMB_R_TO_D, [y.data, th.data], [z.data],
-               n_pts=n_src, n_lev=L, pitch=x.pitch, layout=COLUMNS)), 3 * stack_bytes, "one exp and one log per element")
-        del qh, th
-        # one ORAS6 group: 14 fields and the ice concentration they share
-        o_in, o_out = Stack.empty(n_src, 14, tdt, dev, COLUMNS), Stack.empty(n_src, 14, tdt, dev, COLUMNS)
-        o_in.data.normal_()
-        ice = torch.rand(n_src, device=dev).to(tdt)
-        kinds = torch.tensor([0, 1, 1, 1, 4, 4, 1, 2, 3, 1, 1, 1, 2, 5], dtype=torch.float64, device=dev)
-        record(f"combine oras6_clipping (14 fields of one date) {tag}", timeit(lambda: native.combine_stack(native.COMB_ORAS6, [o_in.data, ice], [o_out.data],
-               n_pts=n_src, n_lev=14, pitch=o_in.pitch, layout=COLUMNS, level_param=kinds)), (2 * 14 + 1) * n_src * B,
-               "one launch per group; the shared ice field is read once per point")
-        cls = Stack.empty(n_src, 1, tdt, dev, COLUMNS)
-        cls.data[:, 0] = torch.randint(0, 21, (n_src,), device=dev).to(tdt)
-        val = cls.new_like()
-        tab = torch.tensor([21.0] + [float(i) for i in range(21)], dtype=torch.float64, device=dev)
-        record(f"combine lookup (land_parameters, 1 field) {tag}", timeit(lambda: native.combine_stack(native.COMB_LOOKUP, [cls.data], [val.data],
-               n_pts=n_src, n_lev=1, pitch=cls.pitch, layout=COLUMNS, level_param=tab)), 2 * n_src * B, "26 MB / 53 MB: launch-latency sized")
-        del o_in, o_out, ice, cls, val
-        # ---- layout
-        f = Stack.empty(n_src, L, tdt, dev, FIELDS)
-        record(f"relayout columns->fields {tag}", timeit(lambda: native.relayout(x.data, f.data, n_pts=n_src, n_lev=L, src_pitch=x.pitch,
-               dst_pitch=f.pitch, src_layout=COLUMNS, dst_layout=FIELDS)), 2 * stack_bytes)
-        record(f"relayout fields->columns {tag}", timeit(lambda: native.relayout(f.data, y.data, n_pts=n_src, n_lev=L, src_pitch=f.pitch,
-               dst_pitch=y.pitch, src_layout=FIELDS, dst_layout=COLUMNS)), 2 * stack_bytes)
-        # ---- level gather (re-listing / sub-selecting the fields of a stack, operand stacks of the multi-input filters)
-        half = Stack.empty(n_src, 68, tdt, dev, COLUMNS)
-        record(f"select 68 of {L} levels (every other one) {tag}", timeit(lambda: native.select_levels(x.data, half.data, list(range(0, L - 1, 2)), n_pts=n_src, n_src_lev=L,
-               src_pitch=x.pitch, dst_pitch=half.pitch, layout=COLUMNS)), 2 * n_src * 68 * B, "atx_select_levels; the source lines are read whole: 3x the algorithmic bytes")
-        one_lev = Stack.empty(n_src, 1, tdt, dev, COLUMNS)
-        record(f"select 1 of {L} levels {tag}", timeit(lambda: native.select_levels(x.data, one_lev.data, [77], n_pts=n_src, n_src_lev=L, src_pitch=x.pitch,
-               dst_pitch=one_lev.pitch, layout=COLUMNS)), 2 * n_src * B, "one field out of a column stack: a 64-byte sector per point is the least that can move")
-        del half, one_lev
-        del x, y, z, f
+        del y
+        combine_rows(tdt, B, tag, x)
+        del x
         torch.cuda.empty_cache()
 
     # ---- k-NN precompute
