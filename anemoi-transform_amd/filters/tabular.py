@@ -9,8 +9,9 @@ filter finds them resident.
 Between those steps recipes add per-row derived columns: ``add_forcings`` (solar and calendar forcings, ``obs.forcings`` ->
 ``atx_obs_forcings``), ``add_azimuth`` and ``add_msg_angles`` (satellite viewing geometry, ``obs.view_angles`` ->
 ``atx_obs_view_angles``) and ``radiance_to_brightness_temperature`` (the inverse Planck law for CrIS, ``obs.brightness_temperature`` ->
-``atx_obs_planck_bt``).  Each is transcendental arithmetic over every row — one launch over columns that stay in HBM, so a chain such
-as ``superob | add_forcings | irregular_to_grid`` keeps a table of device tensors resident from raw rows to the stack.
+``atx_obs_planck_bt``) and ``add_healpix`` (the NESTED HEALPix pixel of every row, ``healpix.ang2pix`` -> ``atx_healpix_ang2pix``).  Each is
+arithmetic over every row — one launch over columns that stay in HBM, so a chain such as
+``superob | add_forcings | add_healpix | irregular_to_grid`` keeps a table of device tensors resident from raw rows to the stack.
 
 A table is a pandas DataFrame (when pandas can be imported) or a plain mapping ``name -> 1-D array / device tensor``.
 
@@ -22,9 +23,12 @@ Deviations from the reference, each said once when it first matters (``core.say_
   * value columns must be numeric: they are read as float64, as the reference's float64 grids read them.  The per-row filters read
     latitude, longitude, spacecraft position and radiance columns as float64 as well (the reference would compute a float32 column
     in float32).
-  * ``"h<nside>"`` grids need healpy and raise ``NotImplementedError``.
+  * ``"h<nside>"`` grid names raise ``NotImplementedError``: the grid itself is ``healpix.grid(nside)``; the names are not wired to it yet.
   * ``superob``: the caller's table is not modified, and rows of equal ``date`` keep the first-appearance order of their groups.
   * ``add_azimuth``: the caller's table is not modified (the reference writes the new column into its argument).
+  * ``add_healpix``: the caller's table is not modified either; healpy's ``ang2pix`` is restated, not called (``healpix`` module: equal
+    away from pixel edges, where the last bit of cos / sin decides), and a row without a pixel (NaN or out-of-range latitude, non-finite
+    longitude) raises ``ValueError``.
 The other tabular filters of the reference (row-dropping, renaming and masking bookkeeping in pandas, with no arithmetic for the
 device to do) are not built: DESIGN.md §7.
 """
@@ -39,7 +43,7 @@ from typing import Any
 import numpy as np
 import torch
 
-from .. import obs
+from .. import healpix, obs
 from ..core import Filter, filter_registry, say_once
 from ..fields import MISSING, Field, FieldList, new_field_from_stack
 from ..grids import lookup
@@ -613,6 +617,38 @@ class RadianceToBrightnessTemperature(Filter):
         return {renamed.get(c, c): ((tb[row[c]] if resident else tb[row[c]].cpu().numpy()) if c in row else table[c]) for c in names}
 
 
+class AddHealpix(Filter):
+    """Adds ``healpix_idx_{nside}``, the NESTED HEALPix pixel of every row's ``longitude`` / ``latitude``, as the last column
+    (R: filters/tabular/add_healpix.py:18-51: ``hp.ang2pix(nside, lon, lat, nest=True, lonlat=True)``).  ``nside <= 0`` raises
+    ``ValueError`` at construction, as in the reference; an ``nside`` that is not a power of two raises it at ``forward``, where healpy's
+    ``check_nside`` would.  int64, one launch (``healpix.ang2pix`` -> ``atx_healpix_ang2pix``); a table of device tensors stays one.
+
+    Deviations: the caller's table is not modified (the reference writes the column into its argument); the two columns are read as
+    float64; a NaN or out-of-range latitude or a non-finite longitude raises ``ValueError``; healpy is restated, not called — pinned by
+    the reference's literals and equal to the exact geometry away from pixel edges (``healpix`` module)."""
+
+    def __init__(self, *, nside: int = 32) -> None:
+        if nside <= 0:
+            raise ValueError("nside must be a positive integer.")
+        self.nside = nside
+        healpix.parity_note()
+        say_once(LOG, (type(self), "table"), "add_healpix: the caller's table is not modified (the reference writes the index column "
+                 "into its argument)", level=logging.INFO)
+        say_once(LOG, (type(self), "float64"), "add_healpix: latitude and longitude are read as float64", level=logging.INFO)
+        say_once(LOG, (type(self), "bad-rows"), "add_healpix: a NaN or out-of-range latitude or a non-finite longitude raises ValueError "
+                 "(healpy's own check of theta is restated from memory and is not pinned by the reference's tests)", level=logging.INFO)
+
+    def __repr__(self) -> str:
+        return f"AddHealpix(nside={self.nside})"
+
+    def forward(self, table: Any) -> Any:
+        _require(table, ["latitude", "longitude"])
+        healpix.check_nside(self.nside, nest=True)
+        resident, dev = _table_device(table)
+        index = healpix.ang2pix(self.nside, table["longitude"], table["latitude"], nest=True, dev=dev)
+        return _with_columns(table, {f"healpix_idx_{self.nside}": index}, resident)
+
+
 filter_registry.register("irregular_to_grid", IrregularToGrid)
 filter_registry.register("assign_to_grid", AssignToGrid)
 filter_registry.register("superob", SuperOb)
@@ -620,3 +656,4 @@ filter_registry.register("add_forcings", AddForcings)
 filter_registry.register("add_azimuth", AddAzimuth)
 filter_registry.register("add_msg_angles", AddMSGAngles)
 filter_registry.register("radiance_to_brightness_temperature", RadianceToBrightnessTemperature)
+filter_registry.register("add_healpix", AddHealpix)

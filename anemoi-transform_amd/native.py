@@ -116,6 +116,7 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     "atx_obs_forcings": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_uint32, c_void_p, c_int64, c_void_p]),
     "atx_obs_view_angles": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_uint32, c_void_p, c_int64, c_void_p]),
     "atx_obs_planck_bt": (c_int, [c_void_p, c_int64, c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "atx_healpix_ang2pix": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "atx_mask_build": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_double, c_int, c_void_p]),
     "atx_mask_count": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
     "atx_mask_to_index_workspace": (c_size_t, [c_int64]),
@@ -561,6 +562,20 @@ def obs_planck_bt(radiance, a, b, out) -> None:
     in_pitch = radiance.stride(0) if n_ch > 1 else max(n, 1)
     out_pitch = out.stride(0) if n_ch > 1 else max(n, 1)
     _call("atx_obs_planck_bt", _ptr(radiance), n, n_ch, in_pitch, _ptr(a), _ptr(b), _ptr(out), out_pitch, _stream())
+
+
+HEALPIX_RING, HEALPIX_NEST = 0, 1  # atx_healpix_scheme
+
+
+def healpix_ang2pix(longitude, latitude, nside: int, nest: bool, out, n_bad) -> None:
+    """``out[i]`` (int64 ``[n]``): the HEALPix pixel of ``(longitude[i], latitude[i])`` (float64 ``[n]``, degrees) at ``nside``, NESTED
+    or RING — ``atx_healpix_ang2pix``.  A row without a pixel (NaN or out-of-range latitude, non-finite longitude) holds -1;
+    ``n_bad`` (int64 ``[1]`` on the device) counts them.  Does not synchronise."""
+    n = out.numel()
+    _rows(longitude, latitude, n=n)
+    assert out.dtype == torch.int64 and out.is_contiguous() and n_bad.dtype == torch.int64 and n_bad.numel() == 1
+    _call("atx_healpix_ang2pix", _ptr(longitude), _ptr(latitude), n, int(nside), HEALPIX_NEST if nest else HEALPIX_RING, _ptr(out), _ptr(n_bad),
+          _stream())
 
 
 def mask_build(m, mask, *, n, stride=1, cmp, threshold=0.0) -> None:

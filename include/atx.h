@@ -68,7 +68,8 @@
 extern "C" {
 #endif
 
-#define ATX_VERSION 420 /* 0.4.2 — additions only, so the number stays: atx_obs_forcings / atx_obs_view_angles / atx_obs_planck_bt (per-row
+#define ATX_VERSION 420 /* 0.4.2 — additions only, so the number stays: atx_healpix_ang2pix (HEALPix pixel indices per row) with its
+                           * atx_healpix_scheme enum; atx_obs_forcings / atx_obs_view_angles / atx_obs_planck_bt (per-row
                            * observation operators); atx_obs_group_mean / atx_obs_group_argmin (superob: per-group
                            * means by pandas' row-order Kahan rule and the nearest row of every group); atx_obs_best_per_cell / atx_obs_fill_stack (observation tables
                            * onto a grid: a keyed arg-min and the gather that fills the stack); atx_rotate_vectors_stack (vector components between projection
@@ -465,6 +466,21 @@ ATX_API int atx_obs_view_angles(const double* latitude, const double* longitude,
  *   R: filters/tabular/radiance_to_brightness_temperature.py:96-113 */
 ATX_API int atx_obs_planck_bt(const double* radiance, int64_t n, int32_t n_ch, int64_t in_pitch, const double* a, const double* b, double* out,
                               int64_t out_pitch, void* stream);
+
+/* pix[i] = the HEALPix pixel of (longitude[i], latitude[i]) degrees at resolution nside, in the RING or the NESTED ordering: healpy's
+ * ang2pix(nside, lon, lat, nest, lonlat=True), that is lonlat2thetaphi (theta = pi/2 - radians(lat), phi = radians(lon)) followed by
+ * healpix_cxx's loc2pix, restated in float64 in the operation order of the source (Gorski et al. 2005, ApJ 622, 759).  Away from pixel
+ * edges the index is the exact geometry's; on an edge the last bit of cos / sin of theta decides between the two neighbours.
+ * A row without a pixel — latitude NaN or with theta outside [0, pi], longitude NaN or infinite — gets pix[i] = -1, and *n_bad
+ * (device, set by this call whenever n > 0) counts such rows.
+ *   longitude, latitude  device double [n], degrees
+ *   nside                1 .. 2^29; ATX_HEALPIX_NEST needs a power of two, ATX_HEALPIX_RING takes any
+ *   pix                  device int64 [n]
+ * n < 0, nside out of range or not a power of two under NEST, a scheme other than the two, a null pointer with n > 0: ATX_EINVAL.
+ *   R: filters/tabular/add_healpix.py:43-51 (NEST); filters/tabular/support/superob.py:28-40 (the RING order of "h<nside>" grids) */
+typedef enum { ATX_HEALPIX_RING = 0, ATX_HEALPIX_NEST = 1 } atx_healpix_scheme;
+ATX_API int atx_healpix_ang2pix(const double* longitude, const double* latitude, int64_t n, int64_t nside, int scheme /* atx_healpix_scheme */,
+                                int64_t* pix, int64_t* n_bad, void* stream);
 
 /* ---- masks ------------------------------------------------------------------ */
 

@@ -1,0 +1,228 @@
+"""HEALPix without a GPU: the numpy restatement (tests/healpix_restatement.py) against the literals of the reference's own tests
+(tests/golden/healpix.json) and against exact geometry, ``healpix.grid`` against the scalar ``pix2ang``, the two orderings tied together
+through the pixel centres, the C ABI of ``atx_healpix_ang2pix`` and the surface of the ``add_healpix`` filter."""
+
+from __future__ import annotations
+
+import subprocess
+
+import numpy as np
+import pytest
+from scipy.spatial import cKDTree
+
+import __graft_entry__ as graft
+from anemoi_transform_amd import healpix, native
+from anemoi_transform_amd.filters import create_filter_by_name, filter_registry
+from anemoi_transform_amd.filters.tabular import AddHealpix
+
+import healpix_restatement as R
+
+GOLDEN = R.load_golden()
+
+
+# ---- the reference's literals -----------------------------------------------------------------------------------------------------
+def test_restatement_reproduces_the_nine_nested_literals():
+    assert GOLDEN["nside"] == 16 and len(GOLDEN["healpix_idx_16"]) == 9
+    got = R.ang2pix(16, GOLDEN["longitude"], GOLDEN["latitude"], nest=True)
+    assert got.dtype == np.int64 and got.tolist() == GOLDEN["healpix_idx_16"]
+
+
+def test_grid_16_through_ckdtree_gives_the_nine_ring_literals():
+    lat, lon = healpix.grid(16)
+    distance, index = cKDTree(np.column_stack([lat, lon])).query(np.column_stack([GOLDEN["latitude"], GOLDEN["longitude"]]))
+    assert index.tolist() == GOLDEN["grid_index_h16"]
+    assert np.allclose(distance, GOLDEN["distance"])
+
+
+# ---- the grid -----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("nside", [1, 2, 3, 16])
+def test_grid_equals_the_scalar_pix2ang(nside):
+    """The vectorised grid against healpix_cxx's pix2loc pixel by pixel.  Both evaluate the same float64 statement; numpy's array loops
+    of arccos / arctan2 and the C library's scalar functions may differ in the last bit (1 ulp of a theta <= pi is 4.4e-16 rad =
+    2.5e-14 degrees, and `90 - .` rounds once more), hence 1e-13 degrees rather than equality."""
+    lat, lon = healpix.grid(nside)
+    assert lat.shape == lon.shape == (12 * nside * nside,) == (healpix.npix(nside),) and lat.dtype == lon.dtype == np.float64
+    want = np.array([R.grid_point(nside, p) for p in range(R.npix(nside))])
+    assert np.abs(lat - want[:, 0]).max() <= 1e-13 and np.abs(lon - want[:, 1]).max() <= 1e-13
+    assert (np.diff(lat) <= 0).all()  # ring order: north to south
+    assert (lon > -180).all() and (lon <= 180).all()
+    theta, phi = healpix.pix2ang_ring(nside, [0, healpix.npix(nside) - 1])
+    assert np.allclose([theta[0] + theta[1]], [np.pi]) and np.allclose(phi[0] + phi[1], 2 * np.pi)
+
+
+def test_grid_and_npix_refuse_a_bad_nside():
+    for bad in (0, -1, 2**29 + 1, 1.5, True):
+        with pytest.raises(ValueError, match="nside"):
+            healpix.npix(bad)
+    with pytest.raises(ValueError, match="nside"):
+        healpix.grid(0)
+    with pytest.raises(ValueError, match="outside"):
+        healpix.pix2ang_ring(1, [12])
+
+
+@pytest.mark.parametrize("nside", [1, 2, 3, 5, 16, 64])
+def test_ring_ang2pix_of_every_pixel_centre_is_that_pixel(nside):
+    lat, lon = healpix.grid(nside)
+    assert np.array_equal(R.ang2pix(nside, lon, lat, nest=False), np.arange(R.npix(nside)))
+
+
+@pytest.mark.parametrize("nside", [1, 2, 16, 64])
+def test_nest_and_ring_are_tied_together_by_the_pixel_centres(nside):
+    """NESTED indices of the RING centres are a bijection onto 0 .. npix - 1; the map it defines turns the NESTED index of any point into
+    its RING index — no conversion formula involved."""
+    lat, lon = healpix.grid(nside)
+    nest_of_ring = R.ang2pix(nside, lon, lat, nest=True)
+    assert np.array_equal(np.sort(nest_of_ring), np.arange(R.npix(nside)))
+    ring_of_nest = np.empty(R.npix(nside), dtype=np.int64)
+    ring_of_nest[nest_of_ring] = np.arange(R.npix(nside))
+    rlon, rlat = R.random_rows(20000)
+    assert np.array_equal(R.ang2pix(nside, rlon, rlat, nest=False), ring_of_nest[R.ang2pix(nside, rlon, rlat, nest=True)])
+
+
+# ---- the float64 statement against exact geometry ------------------------------------------------------------------------------------
+N_EXACT = 20000
+_EXACT: dict = {}
+
+
+def _exact_rows():
+    if not _EXACT:
+        lon, lat = R.random_rows(N_EXACT)
+        _EXACT.update(lon=lon, lat=lat, rows=R.exact_rows(lon, lat))
+    return _EXACT
+
+
+def test_generator_reaches_what_it_is_for():
+    lon, lat = R.random_rows(N_EXACT)
+    assert lon.min() < -350 and lon.max() > 710 and np.abs(lat).max() <= 90
+    polar = np.abs(lat) >= 80
+    assert 0.25 <= polar.mean() <= 0.30 and (lat[polar] > 0).any() and (lat[polar] < 0).any()
+    z = np.sin(np.radians(lat))
+    assert (np.abs(z) <= 2 / 3).sum() > N_EXACT // 3 and ((np.abs(z) > 2 / 3) & (np.abs(z) < 0.99)).sum() > N_EXACT // 10
+
+
+@pytest.mark.parametrize("order", [0, 4, 10, 20, 29])
+def test_statement_truncates_to_the_exact_floor_on_decided_rows(order):
+    """A row is decided when every exact pre-truncation value is farther than 2^-44 * nside from an integer, tt farther than 2^-44 from
+    one, and |za - 2/3| > 2^-48.  The margin: the float64 statement's worst distance from the exact value is about 25 * 2^-52 * nside
+    (printed below; tt = lon / 90 up to 8 carries the roundings of lon * (pi / 180) * (2 / pi), nside * (0.5 + tt -+ 0.75 z) adds its own);
+    2^-44 is about ten times that.  At most 1 row in 1000 may be left out."""
+    nside = 1 << order
+    case = _exact_rows()
+    got = R.parts(nside, case["lon"], case["lat"])
+    exact = R.exact_parts(nside, case["rows"], got)
+    decided = (exact["gap"] > 2.0**-44 * nside) & (exact["tt_gap"] > 2.0**-44) & (exact["za_gap"] > 2.0**-48)
+    left_out = int((~decided).sum())
+    print(f"order {order}: {left_out} of {N_EXACT} rows undecided; the statement lies within {exact['off'].max() / (2.0**-52 * nside):.1f} "
+          "x 2^-52 x nside of the exact values")
+    assert left_out <= N_EXACT // 1000
+    for name in ("eq", "ntt", "jp", "jm", "ip"):
+        assert np.array_equal(got[name][decided], exact[name][decided]), name
+    for nest in (True, False):
+        want = R.assemble(nside, nest, exact["eq"], exact["jp"], exact["jm"], exact["ntt"], exact["ip"], exact["z"])
+        assert np.array_equal(R.ang2pix(nside, case["lon"], case["lat"], nest)[decided], want[decided]), nest
+
+
+@pytest.mark.parametrize("nside,nest", [(s, True) for s in R.NEST_NSIDES] + [(s, False) for s in R.RING_NSIDES])
+def test_candidate_sets_of_the_device_comparison_are_single(nside, nest):
+    """The condition under which test_gpu_healpix.py compares the kernel with the restatement, checked before anything runs on a GPU: of
+    the rows the launches take, at most 1 in 1000 changes its index when numpy's z and sth move by up to 2 ulps."""
+    lon, lat = R.random_rows(max(R.ROWS))
+    sets = R.candidates(nside, lon, lat, nest)
+    many = int((~(sets == sets[0]).all(axis=0)).sum())
+    print(f"nside {nside} {'nest' if nest else 'ring'}: {many} of {lon.size} rows have more than one candidate index")
+    assert sets.shape == ((2 * R.ULPS + 1) ** 2, lon.size) and np.array_equal(sets[len(sets) // 2], R.ang2pix(nside, lon, lat, nest))
+    assert many <= lon.size // 1000
+    assert sets.min() >= 0 and sets.max() < R.npix(nside)
+
+
+def test_special_rows_reach_the_branch_edges_and_enough_of_them_are_decided():
+    lon, lat = R.special_rows()
+    theta, _ = R.theta_phi(lon, lat)
+    assert R.valid(lon, lat).all() and (theta == 0).any() and (theta == np.pi).any()
+    assert ((theta < 0.01) & (theta > 0.0099)).any() and ((theta > 0.01) & (theta < 0.0101)).any()
+    za = np.abs(np.cos(theta))
+    assert (za <= R.TWOTHIRD).any() and ((za > R.TWOTHIRD) & (za < R.TWOTHIRD + 1e-15)).any()
+    for nest, nsides in ((True, R.NEST_NSIDES), (False, R.RING_NSIDES)):
+        for nside in nsides:
+            sets = R.candidates(nside, lon, lat, nest)
+            kept = int((sets == sets[0]).all(axis=0).sum())
+            print(f"nside {nside} {'nest' if nest else 'ring'}: {kept} of {lon.size} special rows have one candidate index")
+            assert kept >= 40
+
+
+def test_restatement_marks_rows_without_a_pixel():
+    lat = np.array([np.nan, 90.0001, -91.0, 10.0, 90.0, -90.0, 0.0])
+    lon = np.array([0.0, 0.0, 0.0, np.inf, 0.0, 0.0, np.nan])
+    assert R.valid(lon, lat).tolist() == [False, False, False, False, True, True, False]
+    got = R.ang2pix(16, lon, lat)
+    assert got.tolist() == [-1, -1, -1, -1, 255, 2048, -1]  # the poles themselves have pixels: the last of face 0, the first of face 8
+
+
+# ---- the C ABI ----------------------------------------------------------------------------------------------------------------------
+def test_entry_point_is_declared_bound_and_exported():
+    name = "atx_healpix_ang2pix"
+    nm = subprocess.run(["nm", "-D", "--defined-only", graft.LIB], capture_output=True, text=True, check=True).stdout
+    exported = {line.split()[-1] for line in nm.splitlines() if line.strip()}
+    assert name in graft.exported_names(), f"{name} is not declared in include/atx.h"
+    assert name in native.SIGNATURES, f"{name} is not bound in native.py"
+    assert name in exported, f"{name} is not exported by libatx.so"
+    assert native.load().atx_version() == 420  # an addition only
+    assert (native.HEALPIX_RING, native.HEALPIX_NEST) == (0, 1)
+
+
+def test_abi_argument_validation_without_a_gpu():
+    lib = native.load()
+
+    def call(n=0, nside=16, scheme=1):
+        return lib.atx_healpix_ang2pix(None, None, n, nside, scheme, None, None, None)
+
+    assert call() == call(scheme=0) == call(nside=1) == call(nside=2**29) == native.OK  # no rows: nothing to do, nothing dereferenced
+    assert call(nside=3, scheme=0) == native.OK  # RING takes any nside
+    assert call(n=-1) == native.EINVAL
+    assert call(nside=0) == native.EINVAL and call(nside=-16) == native.EINVAL and call(nside=2**29 + 1) == native.EINVAL
+    assert call(nside=2**30) == native.EINVAL and b"2^29" in lib.atx_last_error()
+    assert call(nside=3) == native.EINVAL and b"power of two" in lib.atx_last_error()
+    assert call(nside=2**29 - 1, scheme=1) == native.EINVAL
+    assert call(scheme=2) == native.EINVAL and call(scheme=-1) == native.EINVAL and b"scheme" in lib.atx_last_error()
+    assert call(n=10) == native.EINVAL and b"null" in lib.atx_last_error()  # found before any launch
+
+
+# ---- the filter's surface ---------------------------------------------------------------------------------------------------------
+def test_filter_is_registered_with_the_reference_signature():
+    assert filter_registry.is_registered("add_healpix")
+    f = create_filter_by_name("add_healpix", nside=16)
+    assert isinstance(f, AddHealpix) and f.nside == 16 and repr(f) == "AddHealpix(nside=16)"
+    assert create_filter_by_name("add_healpix").nside == 32  # the reference's default
+    with pytest.raises(TypeError):
+        AddHealpix(16)  # keyword-only, as in the reference
+
+
+@pytest.mark.parametrize("nside", [-1, 0])
+def test_bad_nside_raises_at_construction(nside):
+    with pytest.raises(ValueError, match="positive"):
+        create_filter_by_name("add_healpix", nside=nside)
+
+
+def test_missing_columns_raise_before_anything_touches_the_device():
+    f = create_filter_by_name("add_healpix", nside=16)
+    with pytest.raises(ValueError, match="missing columns: {'longitude'}"):
+        f({"latitude": np.zeros(3)})
+    with pytest.raises(ValueError, match="missing columns: {'latitude'}"):
+        f({"longitude": np.zeros(3), "value": np.zeros(3)})
+    with pytest.raises(ValueError, match="power of 2"):
+        create_filter_by_name("add_healpix", nside=12)({"latitude": np.zeros(3), "longitude": np.zeros(3)})
+
+
+def test_parity_note_is_said_once_at_construction(caplog):
+    import logging
+
+    from anemoi_transform_amd.core import reset_notes
+
+    reset_notes()
+    with caplog.at_level(logging.DEBUG, logger="anemoi_transform_amd"):
+        create_filter_by_name("add_healpix", nside=16)
+        create_filter_by_name("add_healpix", nside=32)
+    notes = [r for r in caplog.records if "healpy's ang2pix is restated" in r.getMessage()]
+    assert [r.levelno for r in notes] == [logging.WARNING, logging.DEBUG] and "pixel edges" in notes[0].getMessage()
+    infos = [r.getMessage() for r in caplog.records if r.levelno == logging.INFO]
+    assert len(infos) == 3 and any("not modified" in m for m in infos) and any("float64" in m for m in infos) and any("ValueError" in m for m in infos)

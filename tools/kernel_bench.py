@@ -50,8 +50,10 @@ def main():
                     "to end beside the reference's statement in pandas on this host); --only-obs runs them after its own rows")
     ap.add_argument("--only-rowops", action="store_true", help="only the per-row observation kernels (atx_obs_forcings, atx_obs_view_angles, "
                     "atx_obs_planck_bt) at --rows rows, rows/s beside the reference's numpy statements on this host")
+    ap.add_argument("--only-healpix", action="store_true", help="only the HEALPix kernel (atx_healpix_ang2pix) at --rows rows: nest at nside 32 and "
+                    "2^29, ring at nside 32, rows/s beside the vectorised numpy restatement on this host (profiles/healpix_bench.json)")
     ap.add_argument("--rows", type=int, default=10_000_000)
-    ap.add_argument("--commit", default=None, help="recorded in the --only-rowops result: the commit the library was built from")
+    ap.add_argument("--commit", default=None, help="recorded in the --only-rowops / --only-healpix result: the commit the library was built from")
     ap.add_argument("--only-pointwise", action="store_true", help="only the per-point, mask and reduction rows (atx_pointwise.hip, atx_mask.hip, "
                     "atx_reduce.hip), each with a checksum of what it computed on the seeded stack")
     ap.add_argument("--only-regrid", action="store_true", help="only the gather rows (atx_regrid_columns.inc, atx_regrid_fields.inc), each with a "
@@ -664,6 +666,38 @@ def main():
             record(label, ms, alg, note)
             res[label].update(rows_per_s=n_rows / (ms * 1e-3), numpy_rows_per_s=host[key], numpy_rows=m, commit=args.commit)
             print(f"{'':42s} {n_rows / (ms * 1e-3):.3e} rows/s; numpy on this host, one process, {m} rows: {host[key]:.3e} rows/s", flush=True)
+
+    def healpix_rows():
+        """atx_healpix_ang2pix at args.rows rows: rows/s and the fraction of the HBM peak on its 24 algorithmic bytes per row (it is
+        VALU-bound: one float64 sincos, an fmod and a sqrt per row), beside the vectorised numpy restatement
+        (tests/healpix_restatement.py) on this host, one process, at a tenth of the rows."""
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import healpix_restatement as R
+
+        n = args.rows
+        lon, lat = R.random_rows(n, seed=n)
+        d_lon, d_lat = torch.from_numpy(lon).to(dev), torch.from_numpy(lat).to(dev)
+        out = torch.empty(n, dtype=torch.int64, device=dev)
+        n_bad = torch.zeros(1, dtype=torch.int64, device=dev)
+        m = n // 10
+        for nside, nest in ((32, True), (1 << 29, True), (32, False)):
+            t0 = time.perf_counter()
+            want = R.ang2pix(nside, lon[:m], lat[:m], nest)
+            host = m / (time.perf_counter() - t0)
+            ms = timeit(lambda: native.healpix_ang2pix(d_lon, d_lat, nside, nest, out, n_bad), n=9)
+            differ = int((out[:m].cpu().numpy() != want).sum())  # rows on a pixel edge, where the last bit of cos / sin decides
+            label = f"healpix_ang2pix {'nest' if nest else 'ring'} nside {nside} {n:.0e} rows"
+            record(label, ms, n * 24, "one sincos, one fmod and one sqrt per row; two columns in, one out")
+            res[label].update(rows_per_s=n / (ms * 1e-3), numpy_rows_per_s=host, numpy_rows=m, rows_unlike_numpy=differ, n_bad=int(n_bad.item()),
+                              commit=args.commit)
+            print(f"{'':42s} {n / (ms * 1e-3):.3e} rows/s; numpy on this host, one process, {m} rows: {host:.3e} rows/s; {differ} of {m} rows "
+                  "differ from numpy's", flush=True)
+
+    if args.only_healpix:
+        healpix_rows()
+        if args.out:
+            json.dump(res, open(args.out, "w"), indent=1)
+        return
 
     if args.only_rowops:
         rowops_rows()
