@@ -10,7 +10,9 @@ Registered names:
                   r_to_d, d_to_r, q_to_r, r_to_q, q_to_r_height_with_p, r_to_q_height_with_p
                                                              (multi-input, filters/domain.py)
                   rotate_winds, unrotate_winds               (vector frames, filters/winds.py)
-  tabular         irregular_to_grid, assign_to_grid          (observation tables onto a grid, filters/tabular.py)
+  tabular         irregular_to_grid, assign_to_grid, superob (observation tables onto a grid, filters/tabular.py)
+                  add_forcings, add_azimuth, add_msg_angles, radiance_to_brightness_temperature, add_healpix,
+                  fill_orography, geopotential_to_height_tabular   (per-row columns, filters/tabular.py)
                   rename_fields, clear_step, repeat_members, earthkitfieldlambda, empty,
                   icon_refinement_level   (re-labelling / re-listing, filters/metadata.py)
   dispatchers     mask (alias apply_mask), remove_nans (alias drop_nans),
@@ -19,15 +21,20 @@ Registered names:
 
 The dispatchers pick the field filter from the configuration keys exactly as the
 reference does; configurations that select the *tabular* (pandas) half of a
-dispatcher raise ``NotImplementedError``.  Observations enter the field path
-through ``irregular_to_grid`` (with ``assign_to_grid`` before it): a table goes
-to the device once and comes out as one HBM stack of gridded fields.  The rest
-of the reference's tabular family is per-row pandas bookkeeping with no field
-output and stays out.
+dispatcher raise ``NotImplementedError`` — except ``geopotential_to_height``,
+whose tabular half is built: given a DataFrame or a plain mapping of columns it
+calls ``geopotential_to_height_tabular`` with its ``geopotential`` and ``height``
+keys (``height`` defaults to ``"orog"`` there, as in the reference).
+Observations enter the field path through ``irregular_to_grid`` (with
+``assign_to_grid`` before it): a table goes to the device once and comes out as
+one HBM stack of gridded fields.  The rest of the reference's tabular family is
+row-dropping, renaming and masking bookkeeping in pandas with no field output
+and stays out.
 """
 
 from __future__ import annotations
 
+from collections.abc import Mapping
 from typing import Any
 
 from ..core import DispatchingFilter, Filter, filter_registry
@@ -43,6 +50,7 @@ from . import tabular as _tabular_filters  # noqa: E402
 from . import winds as _winds  # noqa: E402
 from .masks import MaskVariable, RemoveNaNs as RemoveNaNsFields
 from .pointwise import Clipper, ImputeNaNs as ImputeNaNsFields, Orography
+from .tabular import GeopotentialToHeightTabular
 
 
 def _tabular(name: str) -> NotImplementedError:
@@ -92,12 +100,22 @@ class GeopotentialToHeight(DispatchingFilter):
         if "height" not in config:
             config["height"] = config.pop("orography", "orog")
         self.field_filter = Orography(geopotential=config["geopotential"], orography=config["height"])
+        self.tabular_filter = GeopotentialToHeightTabular(geopotential=config["geopotential"], height=config["height"])
 
     def forward_fields(self, data: Any) -> Any:
         return self.field_filter.forward(data)
 
     def backward_fields(self, data: Any) -> Any:
         return self.field_filter.backward(data)
+
+    def forward_tabular(self, data: Any) -> Any:
+        return self.tabular_filter.forward(data)
+
+    def forward_fallback(self, data: Any) -> Any:
+        # a table is a DataFrame or a plain mapping name -> column (filters/tabular.py)
+        if isinstance(data, Mapping):
+            return self.forward_tabular(data)
+        return super().forward_fallback(data)
 
     def patch_data_request(self, data_request: dict) -> dict:
         return self.field_filter.patch_data_request(data_request)

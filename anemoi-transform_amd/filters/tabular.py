@@ -13,6 +13,11 @@ Between those steps recipes add per-row derived columns: ``add_forcings`` (solar
 arithmetic over every row — one launch over columns that stay in HBM, so a chain such as
 ``superob | add_forcings | add_healpix | irregular_to_grid`` keeps a table of device tensors resident from raw rows to the stack.
 
+The station-height pair sits there too: ``fill_orography`` replaces missing station altitudes (NaN or 9999.0) by the height of the
+nearest point of a high-resolution orography — two searches and one gather per such row, ``obs.fill_heights`` ->
+``atx_obs_fill_heights``, the orography resident in HBM per filter instance — and ``geopotential_to_height_tabular`` divides a column
+by 9.80665 (numpy for host columns, torch true division for device tensors: one IEEE division either way, no kernel).
+
 A table is a pandas DataFrame (when pandas can be imported) or a plain mapping ``name -> 1-D array / device tensor``.
 
 Deviations from the reference, each said once when it first matters (``core.say_once``):
@@ -29,6 +34,10 @@ Deviations from the reference, each said once when it first matters (``core.say_
   * ``add_healpix``: the caller's table is not modified either; healpy's ``ang2pix`` is restated, not called (``healpix`` module: equal
     away from pixel edges, where the last bit of cos / sin decides), and a row without a pixel (NaN or out-of-range latitude, non-finite
     longitude) raises ``ValueError``.
+  * ``fill_orography``: the caller's table is not modified; the columns are read as float64 and the filled column is float64; the
+    orography's axes must be 1-D, finite, non-empty and free of repeated values (the reference's answer on a repeated value is
+    arbitrary); rows with two equally near axis entries are answered by the host's cKDTree, so every row is the reference's.
+  * ``geopotential_to_height_tabular``: the caller's table is not modified; the column is read as float64.
 The other tabular filters of the reference (row-dropping, renaming and masking bookkeeping in pandas, with no arithmetic for the
 device to do) are not built: DESIGN.md §7.
 """
@@ -649,6 +658,112 @@ class AddHealpix(Filter):
         return _with_columns(table, {f"healpix_idx_{self.nside}": index}, resident)
 
 
+class FillHeights(Filter):
+    """Fills the missing station altitudes of a table from a high-resolution orography (R: filters/tabular/fill_heights.py:23-91,
+    support/utils.py:24-55 ``get_heights``).  A row whose ``station_altitude`` is NaN or exactly 9999.0 gets ``heights[i, j]`` of the
+    orography file, ``i`` / ``j`` the entries of the file's latitude / longitude axis nearest to the row's ``latitude`` /
+    ``longitude`` as ``cKDTree(np.c_[axis]).query`` decides it — per axis, in degrees, WITHOUT wrap-around in longitude (359.9 against
+    an axis 0 .. 359 gives 359: the reference's behaviour, kept), the end of an axis for a row beyond it.  Every other row keeps its
+    bits.  One launch over columns that stay in HBM (``obs.fill_heights`` -> ``atx_obs_fill_heights``); rows with two equally near
+    entries on an axis are answered by the host's cKDTree, so every row is the reference's.  A table without the altitude column
+    raises ``ValueError``; a row to fill with a NaN or infinite coordinate raises it too (cKDTree refuses such a query).
+
+    The file is opened once per instance, on first use (``_open_orography``); its axes are sorted and uploaded with the heights once
+    (``obs.HeightGrid``).  Returns the kind of table it was given; a table of device tensors stays one.
+
+    Deviations: the caller's table is not modified (the reference writes into its argument); the three columns are read as float64
+    and the filled column is float64; both axes of the file must be 1-D, finite, non-empty and without repeated values, and the
+    heights ``[n_lat, n_lon]`` (the reference's answer on a repeated axis value is arbitrary)."""
+
+    def __init__(self, *, orography_file: str, station_altitude: str = "stalt", orography_altitude: str = "z",
+                 orography_latitude: str = "latitude", orography_longitude: str = "longitude") -> None:
+        self.orography_file = orography_file
+        self.station_altitude = station_altitude
+        self.orography_altitude = orography_altitude
+        self.orography_latitude = orography_latitude
+        self.orography_longitude = orography_longitude
+        self._grid: obs.HeightGrid | None = None
+        say_once(LOG, (type(self), "table"), "fill_orography: the caller's table is not modified (the reference writes the filled "
+                 "altitudes into its argument)", level=logging.INFO)
+        say_once(LOG, (type(self), "float64"), "fill_orography: latitude, longitude and the station altitude are read as float64, and "
+                 "the filled column is float64", level=logging.INFO)
+        say_once(LOG, (type(self), "axes"), "fill_orography: both orography axes must be 1-D, finite, non-empty and without repeated "
+                 "values, and the heights [n_lat, n_lon]; anything else raises ValueError", level=logging.INFO)
+
+    def __repr__(self) -> str:
+        return f"FillHeights({self.station_altitude!r}, orography_file={self.orography_file!r})"
+
+    @staticmethod
+    def _open_orography(path: str, altitude: str, latitude: str, longitude: str) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """``(latitude axis, longitude axis, heights)`` of the file (R: fill_heights.py:74-77) — static and patchable, as
+        ``IrregularToGrid._define_grid``.  An ``.npz`` holding the three named arrays is read with numpy; anything else goes to
+        ``xarray.open_dataset`` when xarray can be imported."""
+        if str(path).endswith(".npz"):
+            with np.load(path) as data:
+                missing = [name for name in (latitude, longitude, altitude) if name not in data.files]
+                if missing:
+                    raise ValueError(f"{path}: no arrays named {missing}; the file holds {list(data.files)}")
+                return data[latitude], data[longitude], data[altitude]
+        try:
+            import xarray as xr
+        except ImportError:
+            raise ValueError(f"cannot read the orography {path!r}: give an .npz file holding the arrays {latitude!r}, {longitude!r} and "
+                             f"{altitude!r}, or install xarray for everything xarray.open_dataset reads") from None
+        ds = xr.open_dataset(path)
+        return np.array(ds[latitude]), np.array(ds[longitude]), np.array(ds[altitude])
+
+    def grid(self) -> obs.HeightGrid:
+        """The orography in HBM: read, checked, sorted and uploaded on first use, then kept."""
+        if self._grid is None:
+            self._grid = obs.HeightGrid(*self._open_orography(self.orography_file, self.orography_altitude, self.orography_latitude,
+                                                              self.orography_longitude))
+        return self._grid
+
+    def forward(self, table: Any) -> Any:
+        _require(table, [self.station_altitude])
+        _require(table, ["latitude", "longitude"])
+        grid = self.grid()  # the file's checks come before anything touches the device
+        resident = any(isinstance(table[c], torch.Tensor) for c in _column_names(table))
+        filled = obs.fill_heights(grid, table["latitude"], table["longitude"], table[self.station_altitude])
+        return _with_columns(table, {self.station_altitude: filled}, resident)
+
+
+class GeopotentialToHeightTabular(Filter):
+    """``table[height] = table[geopotential] / 9.80665`` (R: filters/tabular/geopotential_to_height.py:20-52); ``height`` defaults to
+    the geopotential column, which is then replaced.  One IEEE division in float64: numpy for host columns, torch true division for
+    device tensors — the same bits, so no kernel.  A table without the geopotential column raises ``ValueError``.
+
+    Deviations: the caller's table is not modified; the column is read as float64."""
+
+    G = 9.80665
+
+    def __init__(self, *, geopotential: str, height: str | None = None) -> None:
+        self.geopotential = geopotential
+        self.height = height if height else geopotential
+        say_once(LOG, (type(self), "deviations"), "geopotential_to_height_tabular: the caller's table is not modified (the reference "
+                 "writes the height column into its argument), and the geopotential is read as float64", level=logging.INFO)
+
+    def __repr__(self) -> str:
+        return f"GeopotentialToHeightTabular({self.geopotential!r} -> {self.height!r})"
+
+    def forward(self, table: Any) -> Any:
+        _require(table, [self.geopotential])
+        z = table[self.geopotential]
+        if isinstance(z, torch.Tensor):
+            if z.dtype.is_complex or z.dtype == torch.bool:
+                raise ValueError(f"a numeric column is needed, got {z.dtype}")
+            # the divisor as a tensor on z's device: torch turns division by a Python number into a multiplication by its
+            # reciprocal on the device, which is two roundings and not numpy's quotient
+            height = torch.true_divide(z.to(torch.float64), torch.full((), self.G, dtype=torch.float64, device=z.device))
+        elif _is_dataframe(table):
+            return table.assign(**{self.height: z.astype(np.float64) / self.G})
+        else:
+            height = np.asarray(obs._host_array(z), dtype=np.float64) / self.G
+        return {**table, self.height: height}
+
+
+filter_registry.register("fill_orography", FillHeights)
+filter_registry.register("geopotential_to_height_tabular", GeopotentialToHeightTabular)
 filter_registry.register("irregular_to_grid", IrregularToGrid)
 filter_registry.register("assign_to_grid", AssignToGrid)
 filter_registry.register("superob", SuperOb)

@@ -117,6 +117,11 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     "atx_obs_view_angles": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_uint32, c_void_p, c_int64, c_void_p]),
     "atx_obs_planck_bt": (c_int, [c_void_p, c_int64, c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "atx_healpix_ang2pix": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "atx_obs_fill_heights": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p,
+         c_void_p, c_void_p, c_void_p],
+    ),
     "atx_mask_build": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_double, c_int, c_void_p]),
     "atx_mask_count": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
     "atx_mask_to_index_workspace": (c_size_t, [c_int64]),
@@ -576,6 +581,30 @@ def healpix_ang2pix(longitude, latitude, nside: int, nest: bool, out, n_bad) -> 
     assert out.dtype == torch.int64 and out.is_contiguous() and n_bad.dtype == torch.int64 and n_bad.numel() == 1
     _call("atx_healpix_ang2pix", _ptr(longitude), _ptr(latitude), n, int(nside), HEALPIX_NEST if nest else HEALPIX_RING, _ptr(out), _ptr(n_bad),
           _stream())
+
+
+FILL_TIE_LATITUDE, FILL_TIE_LONGITUDE = 1, 2  # the bits of atx_obs_fill_heights' flags
+
+
+def obs_fill_heights(latitude, longitude, altitude, lat_axis, lat_perm, lon_axis, lon_perm, heights, out, flags, counters) -> None:
+    """``out[r]`` (float64 ``[n]``): ``altitude[r]`` bit for bit, or — where it is NaN or 9999.0 — ``heights[i, j]`` at the axis entries
+    nearest to ``(latitude[r], longitude[r])`` by cKDTree's measure — ``atx_obs_fill_heights``.  The axes (float64) come sorted ascending
+    with their int32 permutations back to file order; ``heights``: float32 or float64 ``[n_lat, n_lon]`` in file order (rows may be
+    pitched).  ``flags`` (uint8 ``[n]``): ``FILL_TIE_*`` bits where an axis has two equally near entries and the caller has to answer;
+    ``counters`` (int64 ``[3]`` on the device, set by the call): rows given a value, flagged rows, rows to fill whose coordinates are not
+    finite.  Does not synchronise."""
+    n = out.numel()
+    _rows(latitude, longitude, altitude, out, n=n)
+    n_lat, n_lon = lat_axis.numel(), lon_axis.numel()
+    for axis, perm in ((lat_axis, lat_perm), (lon_axis, lon_perm)):
+        assert axis.dtype == torch.float64 and perm.dtype == torch.int32 and axis.is_contiguous() and perm.is_contiguous()
+        assert axis.dim() == 1 and perm.numel() == axis.numel()
+    assert heights.dim() == 2 and tuple(heights.shape) == (n_lat, n_lon) and (heights.stride(1) == 1 or n_lon <= 1)
+    assert flags.dtype == torch.uint8 and flags.is_contiguous() and flags.numel() == n
+    assert counters.dtype == torch.int64 and counters.is_contiguous() and counters.numel() == 3
+    pitch = heights.stride(0) if n_lat > 1 else max(n_lon, 1)
+    _call("atx_obs_fill_heights", _ptr(latitude), _ptr(longitude), _ptr(altitude), n, _ptr(lat_axis), _ptr(lat_perm), n_lat, _ptr(lon_axis),
+          _ptr(lon_perm), n_lon, _ptr(heights), pitch, dtype_code(heights.dtype), _ptr(out), _ptr(flags), _ptr(counters), _stream())
 
 
 def mask_build(m, mask, *, n, stride=1, cmp, threshold=0.0) -> None:

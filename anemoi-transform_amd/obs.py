@@ -20,6 +20,10 @@ The third part is the per-row derived columns that recipes put between those ste
 add_msg_angles.py, radiance_to_brightness_temperature.py): ``forcings``, ``view_angles`` and ``brightness_temperature``, one launch each
 (``atx_obs_forcings``, ``atx_obs_view_angles``, ``atx_obs_planck_bt``) over columns that stay in HBM, and ``meteosat_position``, the
 sub-satellite table of ``add_msg_angles`` (torch on the device).
+
+The fourth is ``fill_orography`` (R: filters/tabular/fill_heights.py, support/utils.py:24-55): ``HeightGrid`` keeps an orography in HBM
+with its axes sorted, and ``fill_heights`` replaces the missing station altitudes of a table by the nearest orography height in one
+launch (``atx_obs_fill_heights``); rows with two equally near axis entries go back to the host's ``cKDTree``.
 """
 
 from __future__ import annotations
@@ -492,3 +496,111 @@ def brightness_temperature(radiance: torch.Tensor, wavenumber: Any, out: torch.T
     out = torch.empty_like(radiance) if out is None else out
     native.obs_planck_bt(radiance, a, b, out)
     return out
+
+
+# ---- station heights from an orography (R: filters/tabular/fill_heights.py, support/utils.py:24-55 get_heights) ---------------------
+FILL_SENTINEL = 9999.0  # R: fill_heights.py:80 — a station altitude of exactly 9999.0 is missing, as NaN is
+
+
+def _check_axis(name: str, axis: Any) -> np.ndarray:
+    a = np.asarray(_host_array(axis))
+    if a.ndim != 1 or a.size == 0:
+        raise ValueError(f"orography {name} axis must be 1-D and non-empty, got shape {a.shape}")
+    if a.dtype.kind not in "iuf":
+        raise ValueError(f"orography {name} axis must be numeric, got dtype {a.dtype}")
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if not np.isfinite(a).all():
+        raise ValueError(f"orography {name} axis holds values that are not finite")
+    return a
+
+
+class HeightGrid:
+    """An orography resident in HBM, as ``fill_heights`` searches it: both axes sorted ascending with the int32 permutations back to
+    file order, and the heights in file order in their own dtype (float32 or float64; anything else numeric is widened to float64).
+    Built once — the ``fill_orography`` filter keeps one per instance, as ``winds.py`` keeps its frame table.
+
+    ``latitudes`` / ``longitudes``: 1-D, finite, non-empty, with distinct values, in any order; ``heights``: ``[n_lat, n_lon]``, a
+    numpy array (uploaded) or a device tensor whose rows may be pitched (used in place).  Anything else raises ``ValueError`` before
+    anything touches the device.  The host keeps the two axes for the rows whose nearest entry is a tie: those are answered by
+    ``cKDTree`` itself, one tree per axis, built on first need (``tree``)."""
+
+    def __init__(self, latitudes: Any, longitudes: Any, heights: Any, dev: torch.device | None = None) -> None:
+        self.axes = (_check_axis("latitude", latitudes), _check_axis("longitude", longitudes))
+        shape = tuple(heights.shape) if hasattr(heights, "shape") else np.shape(heights)
+        if shape != (self.axes[0].size, self.axes[1].size):
+            raise ValueError(f"orography heights have shape {shape}, the axes need {(self.axes[0].size, self.axes[1].size)}")
+        self.order = tuple(np.argsort(a, kind="stable") for a in self.axes)
+        self.sorted = tuple(a[o] for a, o in zip(self.axes, self.order))
+        for name, s in zip(("latitude", "longitude"), self.sorted):
+            if (np.diff(s) <= 0).any():  # -0.0 and 0.0 are one value
+                raise ValueError(f"orography {name} axis repeats a value; which of the two the reference takes is arbitrary")
+        if isinstance(heights, torch.Tensor):
+            if heights.dtype not in (torch.float32, torch.float64) or (heights.stride(1) != 1 and shape[1] > 1):
+                raise ValueError(f"device heights must be float32 or float64 with contiguous rows, got {heights.dtype}, strides {heights.stride()}")
+            dev = heights.device if heights.is_cuda else (_stack.device() if dev is None else dev)
+            self.heights = heights.to(dev)
+        else:
+            h = np.asarray(_host_array(heights))
+            if h.dtype.kind not in "iuf":
+                raise ValueError(f"orography heights must be numeric, got dtype {h.dtype}")
+            h = np.ascontiguousarray(h, dtype=h.dtype if h.dtype in (np.float32, np.float64) else np.float64)
+            dev = _stack.device() if dev is None else dev
+            self.heights = torch.from_numpy(h).to(dev)
+        self.device = self.heights.device
+        self.d_sorted = tuple(_device(s, self.device) for s in self.sorted)
+        self.d_order = tuple(_device(o.astype(np.int32), self.device) for o in self.order)
+        self._trees: list[Any] = [None, None]
+
+    def tree(self, axis: int) -> Any:
+        """The reference's ``cKDTree(np.c_[axis])`` over the axis in FILE order (0: latitude, 1: longitude), built once."""
+        if self._trees[axis] is None:
+            from scipy.spatial import cKDTree
+
+            self._trees[axis] = cKDTree(np.c_[self.axes[axis]])
+        return self._trees[axis]
+
+    def nearest(self, axis: int, q: np.ndarray, tie: np.ndarray) -> np.ndarray:
+        """File-order index of the entry nearest to every finite ``q``: cKDTree's own answer where ``tie``, elsewhere the strict
+        arg-min of the float64 squares, which is cKDTree's whatever its build."""
+        s, n = self.sorted[axis], self.sorted[axis].size
+        hi = np.minimum(np.searchsorted(s, q, side="left"), n - 1)
+        lo = np.maximum(hi - 1, 0)
+        with np.errstate(over="ignore"):
+            index = self.order[axis][np.where((s[lo] - q) * (s[lo] - q) < (s[hi] - q) * (s[hi] - q), lo, hi)]
+        if tie.any():
+            _, found = self.tree(axis).query(q[tie].reshape(-1, 1))
+            if (found >= n).any():  # every square overflowed: cKDTree finds no neighbour, and the reference's indexing would raise
+                raise ValueError(f"fill_heights: {int((found >= n).sum())} rows lie too far from the orography for a float64 distance")
+            index[tie] = found
+        return index
+
+
+def fill_heights(grid: HeightGrid, latitude: Any, longitude: Any, altitude: Any, *, return_counts: bool = False) -> Any:
+    """The station altitudes with the missing ones (NaN or 9999.0) taken from the orography ``grid``, a float64 device column — one
+    launch of ``atx_obs_fill_heights`` (R: fill_heights.py:68-91, support/utils.py:24-55).  A row to fill gets ``heights[i, j]`` at
+    the axis entries nearest to its latitude and longitude, each as ``cKDTree(np.c_[axis]).query`` decides it: no wrap-around in
+    longitude, the end of the axis beyond it.  Every other row keeps its bits.  Rows the kernel flags — two equally near entries on
+    an axis — are answered by ``grid.tree(axis)`` and one torch index into the resident heights, so every row is the reference's.
+
+    Columns are numpy arrays, pandas Series or device tensors, read as float64.  A row to fill whose latitude or longitude is NaN
+    or infinite raises ``ValueError`` naming how many there are (synchronises).  ``return_counts``: also ``(filled, flagged)``."""
+    dev = grid.device
+    lat, lon, alt = float_column(latitude, dev), float_column(longitude, dev), float_column(altitude, dev)
+    n = alt.numel()
+    if not lat.numel() == lon.numel() == n:
+        raise ValueError(f"columns differ in length: latitude {lat.numel()}, longitude {lon.numel()}, altitude {n}")
+    out = torch.empty(n, dtype=torch.float64, device=dev)
+    flags = torch.empty(n, dtype=torch.uint8, device=dev)
+    counters = torch.zeros(3, dtype=torch.int64, device=dev)
+    native.obs_fill_heights(lat, lon, alt, grid.d_sorted[0], grid.d_order[0], grid.d_sorted[1], grid.d_order[1], grid.heights, out, flags,
+                            counters)
+    filled, flagged, bad = (int(c) for c in counters.cpu())
+    if bad:
+        raise ValueError(f"fill_heights: {bad} of {filled + bad} rows to fill have a latitude or longitude that is not finite")
+    if flagged:
+        rows = torch.nonzero(flags).reshape(-1)
+        bits = flags[rows].cpu().numpy()
+        i = grid.nearest(0, lat[rows].cpu().numpy(), (bits & native.FILL_TIE_LATITUDE) != 0)
+        j = grid.nearest(1, lon[rows].cpu().numpy(), (bits & native.FILL_TIE_LONGITUDE) != 0)
+        out[rows] = grid.heights[_device(i.astype(np.int64), dev), _device(j.astype(np.int64), dev)].to(torch.float64)
+    return (out, (filled, flagged)) if return_counts else out

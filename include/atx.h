@@ -68,8 +68,8 @@
 extern "C" {
 #endif
 
-#define ATX_VERSION 420 /* 0.4.2 — additions only, so the number stays: atx_healpix_ang2pix (HEALPix pixel indices per row) with its
-                           * atx_healpix_scheme enum; atx_obs_forcings / atx_obs_view_angles / atx_obs_planck_bt (per-row
+#define ATX_VERSION 420 /* 0.4.2 — additions only, so the number stays: atx_obs_fill_heights (missing station altitudes from an
+                           * orography); atx_healpix_ang2pix (HEALPix pixel indices per row) with its atx_healpix_scheme enum; atx_obs_forcings / atx_obs_view_angles / atx_obs_planck_bt (per-row
                            * observation operators); atx_obs_group_mean / atx_obs_group_argmin (superob: per-group
                            * means by pandas' row-order Kahan rule and the nearest row of every group); atx_obs_best_per_cell / atx_obs_fill_stack (observation tables
                            * onto a grid: a keyed arg-min and the gather that fills the stack); atx_rotate_vectors_stack (vector components between projection
@@ -481,6 +481,30 @@ ATX_API int atx_obs_planck_bt(const double* radiance, int64_t n, int32_t n_ch, i
 typedef enum { ATX_HEALPIX_RING = 0, ATX_HEALPIX_NEST = 1 } atx_healpix_scheme;
 ATX_API int atx_healpix_ang2pix(const double* longitude, const double* latitude, int64_t n, int64_t nside, int scheme /* atx_healpix_scheme */,
                                 int64_t* pix, int64_t* n_bad, void* stream);
+
+/* out[r] = altitude[r], bit for bit, unless altitude[r] is NaN or the sentinel 9999.0; then out[r] = heights[i, j] widened to double,
+ * with i (j) the entry of the orography's latitude (longitude) axis nearest to latitude[r] (longitude[r]): the arg-min of the float64
+ * square (a - q) * (a - q), which is what a one-dimensional cKDTree query returns.  No wrap-around in longitude; a query beyond an
+ * axis end takes the end.  Both axes come SORTED ASCENDING with the permutation back to file order (axis[p] is entry perm[p] of the
+ * file), heights in file order: heights[i * heights_pitch + j], 64-bit indices.
+ * Which of two equally near entries cKDTree returns is an artefact of its build and is not decided here: where the square of either
+ * sorted neighbour of the winner equals the winner's, flags[r] gets ATX_FILL_TIE_LATITUDE / ATX_FILL_TIE_LONGITUDE and out[r] holds the
+ * value at the kernel's own candidate; the caller answers that axis again.  Without the bit the winner's square is strictly the axis'
+ * smallest.  A row to fill whose latitude or longitude is NaN or infinite gets NaN and no flag (cKDTree refuses such a query).
+ * counters (device int64 [3], zeroed and set by this call, n == 0 included): rows given a value from heights, rows among them with a
+ * flag, rows to fill with a coordinate that is not finite.  Kept rows may hold anything in latitude / longitude.
+ *   latitude, longitude, altitude   device double [n]
+ *   lat_axis, lon_axis              device double [n_lat], [n_lon], strictly ascending and finite (the caller checks)
+ *   lat_perm, lon_perm              device int32 [n_lat], [n_lon], permutations
+ *   heights                         device float / double (dtype), n_lat rows of n_lon, heights_pitch elements apart
+ *   out  device double [n]          flags  device uint8 [n], written for every row
+ * n < 0, an axis length outside 1 .. 2^31 - 1, a dtype other than the two, a null pointer: ATX_EINVAL.  heights_pitch < n_lon: ATX_ESHAPE.
+ *   R: filters/tabular/fill_heights.py:68-91 (the rows), filters/tabular/support/utils.py:24-55 (get_heights) */
+enum { ATX_FILL_TIE_LATITUDE = 1, ATX_FILL_TIE_LONGITUDE = 2 };
+ATX_API int atx_obs_fill_heights(const double* latitude, const double* longitude, const double* altitude, int64_t n, const double* lat_axis,
+                                 const int32_t* lat_perm, int64_t n_lat, const double* lon_axis, const int32_t* lon_perm, int64_t n_lon,
+                                 const void* heights, int64_t heights_pitch, int dtype /* atx_dtype */, double* out, uint8_t* flags,
+                                 int64_t* counters, void* stream);
 
 /* ---- masks ------------------------------------------------------------------ */
 

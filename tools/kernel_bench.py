@@ -52,6 +52,9 @@ def main():
                     "atx_obs_planck_bt) at --rows rows, rows/s beside the reference's numpy statements on this host")
     ap.add_argument("--only-healpix", action="store_true", help="only the HEALPix kernel (atx_healpix_ang2pix) at --rows rows: nest at nside 32 and "
                     "2^29, ring at nside 32, rows/s beside the vectorised numpy restatement on this host (profiles/healpix_bench.json)")
+    ap.add_argument("--only-fill-heights", action="store_true", help="only the station-height kernel (atx_obs_fill_heights) at --rows rows, half of "
+                    "them to fill, against a 1801 x 3600 float32 orography: rows/s beside cKDTree and fancy indexing on this host, and four rows "
+                    "that take the kernel apart (profiles/fill_heights_bench.json)")
     ap.add_argument("--rows", type=int, default=10_000_000)
     ap.add_argument("--commit", default=None, help="recorded in the --only-rowops / --only-healpix result: the commit the library was built from")
     ap.add_argument("--only-pointwise", action="store_true", help="only the per-point, mask and reduction rows (atx_pointwise.hip, atx_mask.hip, "
@@ -692,6 +695,69 @@ def main():
                               commit=args.commit)
             print(f"{'':42s} {n / (ms * 1e-3):.3e} rows/s; numpy on this host, one process, {m} rows: {host:.3e} rows/s; {differ} of {m} rows "
                   "differ from numpy's", flush=True)
+
+    def fill_heights_rows():
+        """atx_obs_fill_heights at args.rows rows against a 1801 x 3600 float32 orography (0.1 degrees, 26 MB), half of the rows to
+        fill — beside the restatement (one cKDTree per axis and fancy indexing, tests/fill_heights_restatement.py) on this host, one
+        process, at a tenth of the rows.  Three more rows take the kernel apart with EVERY row to fill: against a 2 x 2 orography (one
+        search step per axis, four heights: the row traffic and the counters alone), against the full orography with all rows inside
+        one cell (full-depth searches whose reads are the same for every lane, one cache line of heights) and with rows anywhere
+        (scattered axis reads and the random gather on top)."""
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import fill_heights_restatement as R
+        from anemoi_transform_amd import obs
+
+        n = args.rows
+        rng = np.random.default_rng(n)
+        lat_axis, lon_axis = np.linspace(90.0, -90.0, 1801), np.arange(3600) * 0.1  # north to south, as orography files come
+        h = R.heights(1801, 3600, np.float32)
+        grid = obs.HeightGrid(lat_axis, lon_axis, h, dev)
+        small = obs.HeightGrid(np.array([-45.0, 45.0]), np.array([0.0, 180.0]), np.arange(4, dtype=np.float32).reshape(2, 2), dev)
+        lat, lon = rng.uniform(-90.0, 90.0, n), rng.uniform(0.0, 360.0, n)
+        alt = rng.uniform(-400.0, 8800.0, n)
+        alt[rng.random(n) < 0.5] = np.nan
+        m = max(n // 10, 1)
+        t0 = time.perf_counter()
+        want = R.fill(lat_axis, lon_axis, h, lat[:m], lon[:m], alt[:m])
+        host = m / (time.perf_counter() - t0)
+        d_lat, d_lon, d_alt = (torch.from_numpy(a).to(dev) for a in (lat, lon, alt))
+        d_nan = torch.full((n,), float("nan"), dtype=torch.float64, device=dev)
+        d_lat1, d_lon1 = (torch.from_numpy(a).to(dev) for a in (rng.uniform(12.26, 12.34, n), rng.uniform(77.06, 77.14, n)))
+        out = torch.empty(n, dtype=torch.float64, device=dev)
+        flags = torch.empty(n, dtype=torch.uint8, device=dev)
+        counters = torch.zeros(3, dtype=torch.int64, device=dev)
+
+        def run(g, la, lo, al, order=None):
+            order = g.d_order if order is None else order
+            return lambda: native.obs_fill_heights(la, lo, al, g.d_sorted[0], order[0], g.d_sorted[1], order[1], g.heights, out, flags, counters)
+
+        first = tuple(torch.zeros_like(o) for o in grid.d_order)  # every row gathers heights[0, 0]: the searches without the gather
+
+        for label, call, note in (
+                (f"fill_heights 1801x3600 f32 {n:.0e} rows, half to fill", run(grid, d_lat, d_lon, d_alt), "the flagship shape"),
+                (f"fill_heights 2x2 f32 {n:.0e} rows, all to fill", run(small, d_lat, d_lon, d_nan), "row traffic and counters alone"),
+                (f"fill_heights 1801x3600 f32 {n:.0e} rows, all to fill in one cell", run(grid, d_lat1, d_lon1, d_nan),
+                 "plus two full-depth searches with lane-uniform reads; one line of heights"),
+                (f"fill_heights 1801x3600 f32 {n:.0e} rows, all to fill anywhere, gather from one element", run(grid, d_lat, d_lon, d_nan, first),
+                 "the searches read the axes at scattered positions; permutations zeroed, so every gather reads heights[0, 0]"),
+                (f"fill_heights 1801x3600 f32 {n:.0e} rows, all to fill anywhere", run(grid, d_lat, d_lon, d_nan),
+                 "plus the random gather")):
+            ms = timeit(call, n=9)
+            filled, flagged, bad = counters.cpu().tolist()
+            record(label, ms, n * 33, f"{note}; three columns in, one column and one flag byte out")
+            res[label].update(rows_per_s=n / (ms * 1e-3), filled=filled, flagged=flagged, not_finite=bad, commit=args.commit)
+            print(f"{'':42s} {n / (ms * 1e-3):.3e} rows/s; {filled} filled, {flagged} flagged", flush=True)
+        label = f"fill_heights 1801x3600 f32 {n:.0e} rows, half to fill"
+        got = obs.fill_heights(grid, d_lat[:m], d_lon[:m], d_alt[:m]).cpu().numpy()
+        differ = int((got.view(np.int64) != want.view(np.int64)).sum())
+        res[label].update(scipy_rows_per_s=host, scipy_rows=m, rows_unlike_scipy=differ)
+        print(f"{'':42s} cKDTree + fancy indexing on this host, one process, {m} rows: {host:.3e} rows/s; {differ} of {m} rows differ", flush=True)
+
+    if args.only_fill_heights:
+        fill_heights_rows()
+        if args.out:
+            json.dump(res, open(args.out, "w"), indent=1)
+        return
 
     if args.only_healpix:
         healpix_rows()
