@@ -15,21 +15,13 @@
 // one row per lane, 256-lane workgroups, a grid-stride loop under a grid cap; consecutive lanes touch consecutive elements of every
 // column, and the outputs are rows of one [n_out, pitch] block, so every load and store of a wave is one contiguous 512-byte run.
 // Which outputs are wanted is uniform over the launch: the branches on it are scalar.
-#include "atx_common.hpp"
+#include "atx_obs_rows.hpp"
 
 namespace atx {
 
 constexpr int64_t kNaT = INT64_MIN;                    // numpy's / pandas' NaT
 constexpr int64_t kNsPerSecond = 1000000000ll;
 constexpr int64_t kNsPerDay = 86400ll * kNsPerSecond;
-constexpr double kPi = 3.141592653589793;              // np.pi
-constexpr double kRad = kPi / 180.0;                   // np.deg2rad / np.radians: x * (pi / 180)
-constexpr double kDeg = 180.0 / kPi;                   // np.degrees: x * (180 / pi)
-constexpr int kRowGrid = 1 << 20;                      // grid cap: 2^28 rows before a lane takes a second one
-
-__device__ __forceinline__ void row_sincos(double x, double& sn, double& cs) {
-    if (!sincos_moderate(x, sn, cs)) sincos(x, &sn, &cs);  // |x| >= 1e5, infinite, NaN
-}
 
 // numpy's float `%`: fmod, then the result takes the sign of the divisor (b > 0 here).
 __device__ __forceinline__ double numpy_mod(double a, double b) {
@@ -247,11 +239,6 @@ obs_planck_bt_kernel(const double* __restrict__ radiance, int64_t n, int64_t in_
         const double floored = (R >= 1e-300 || R != R) ? R : 1e-300;  // np.maximum(R, 1e-300): a NaN stays
         dst[i] = b_ch / log1p(a_ch / floored);
     }
-}
-
-static unsigned row_grid(int64_t n) {
-    const int64_t blocks = (n + kBlock - 1) / kBlock;
-    return (unsigned)(blocks < kRowGrid ? blocks : kRowGrid);
 }
 
 }  // namespace atx

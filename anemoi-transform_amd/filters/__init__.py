@@ -12,7 +12,8 @@ Registered names:
                   rotate_winds, unrotate_winds               (vector frames, filters/winds.py)
   tabular         irregular_to_grid, assign_to_grid, superob (observation tables onto a grid, filters/tabular.py)
                   add_forcings, add_azimuth, add_msg_angles, radiance_to_brightness_temperature, add_healpix,
-                  fill_orography, geopotential_to_height_tabular   (per-row columns, filters/tabular.py)
+                  fill_orography, geopotential_to_height_tabular, apply_column_transformations
+                                                             (per-row columns, filters/tabular.py)
                   rename_fields, clear_step, repeat_members, earthkitfieldlambda, empty,
                   icon_refinement_level   (re-labelling / re-listing, filters/metadata.py)
   dispatchers     mask (alias apply_mask), remove_nans (alias drop_nans),

@@ -18,6 +18,10 @@ nearest point of a high-resolution orography — two searches and one gather per
 ``atx_obs_fill_heights``, the orography resident in HBM per filter instance — and ``geopotential_to_height_tabular`` divides a column
 by 9.80665 (numpy for host columns, torch true division for device tensors: one IEEE division either way, no kernel).
 
+``apply_column_transformations`` evaluates ``log``, ``log1p``, ``safe_log``, ``sqrt``, ``exp``, ``abs``, ``sin``, ``sin_deg``, ``cos`` and
+``cos_deg`` over whole columns, in config order and chained: up to 16 of them are one launch (``obs.column_ops`` ->
+``atx_obs_column_ops``), and a transformation that reads an earlier one's target takes it from a register.
+
 A table is a pandas DataFrame (when pandas can be imported) or a plain mapping ``name -> 1-D array / device tensor``.
 
 Deviations from the reference, each said once when it first matters (``core.say_once``):
@@ -38,6 +42,9 @@ Deviations from the reference, each said once when it first matters (``core.say_
     orography's axes must be 1-D, finite, non-empty and free of repeated values (the reference's answer on a repeated value is
     arbitrary); rows with two equally near axis entries are answered by the host's cKDTree, so every row is the reference's.
   * ``geopotential_to_height_tabular``: the caller's table is not modified; the column is read as float64.
+  * ``apply_column_transformations``: float32 and float16 columns are read as float64 and the result is float64 (numpy would stay in
+    float32); a ``source_column`` list of more than one name raises ``NotImplementedError``; numpy's ``RuntimeWarning``s are not
+    reproduced.
 The other tabular filters of the reference (row-dropping, renaming and masking bookkeeping in pandas, with no arithmetic for the
 device to do) are not built: DESIGN.md §7.
 """
@@ -762,6 +769,65 @@ class GeopotentialToHeightTabular(Filter):
         return {**table, self.height: height}
 
 
+def column_ops_parity_note() -> None:
+    """Said once per process, by the first ``apply_column_transformations`` filter: what its values are held to."""
+    say_once(LOG, "column-ops-parity", "apply_column_transformations: sqrt and abs have numpy's bits; log, log1p, safe_log and exp are "
+             "held within 1 ulp of exact arithmetic, sin / cos (and sin_deg / cos_deg of numpy's own x * (pi / 180)) within 1 ulp for "
+             "arguments below 1e5 and 2 ulps beyond — not to numpy's last bit, which is itself up to an ulp from exact")
+
+
+class ApplyColumnTransformations(Filter):
+    """Applies library functions to columns of a table (R: filters/tabular/apply_column_transformations.py:18-138).  ``**config`` maps a
+    target column to ``{"function": name, "source_column": column}``; ``function`` is one of ``log``, ``log1p``, ``safe_log``
+    (``log(x + 1e-10)``), ``sqrt``, ``exp``, ``abs``, ``sin``, ``sin_deg``, ``cos``, ``cos_deg``; ``source_column`` defaults to the target,
+    which is then replaced.  An empty config, a specification that is not a dict or has no ``function``, and an unknown function raise
+    ``ValueError`` at construction; a source column the table lacks raises ``KeyError`` at ``forward``.
+
+    Transformations apply in config order, so a later one sees an earlier one's result.  Up to 16 of them run as ONE launch
+    (``obs.column_ops`` -> ``atx_obs_column_ops``), a chained one taking its operand from a register.  float64 and integer columns give
+    what numpy gives: float64 — and ``abs`` of an integer column keeps its dtype (``torch.abs``, outside the kernel).  A bool or
+    non-numeric source raises ``ValueError``.  A DataFrame gives a DataFrame with existing columns in place and new ones appended in
+    config order (``assign``); a mapping gives a new dict, of device tensors if any input column was one, else of numpy arrays.  The
+    caller's table is untouched.
+
+    Deviations: float32 and float16 columns are read as float64 and the result is float64 (numpy would stay in float32);
+    a ``source_column`` list of more than one name raises ``NotImplementedError`` (in the reference the second column lands in numpy's
+    ``out=`` argument, an accident that is not reproduced); numpy's ``RuntimeWarning``s (log of zero, overflow) are not reproduced."""
+
+    def __init__(self, **config: Any) -> None:
+        if not config:
+            raise ValueError("No columns to transform were specified.")
+        spec = []
+        for target, transform in config.items():
+            if not isinstance(transform, dict) or "function" not in transform:
+                raise ValueError(f"Invalid transformation specification for column {target}: {transform}")
+            if transform["function"] not in obs.COLUMN_FUNCTIONS:  # before the sources, as the reference's constructor has it
+                raise ValueError(f"Invalid transformation: {transform['function']}")
+            source = transform.get("source_column", target)
+            if not isinstance(source, str):
+                source = tuple(source)
+                if len(source) != 1:
+                    raise NotImplementedError(f"column {target}: {len(source)} source columns {source}; every transformation takes one")
+                source = source[0]
+            spec.append((target, source, transform["function"]))
+        self.transformations = spec
+        column_ops_parity_note()
+
+    def __repr__(self) -> str:
+        return "ApplyColumnTransformations(" + ", ".join(f"{t}={f}({s})" for t, s, f in self.transformations) + ")"
+
+    def forward(self, table: Any) -> Any:
+        names = _column_names(table)
+        # obs.column_ops refuses a missing or non-numeric source on the host and only then looks for the device
+        added = obs.column_ops(table, self.transformations)
+        narrow = [s for s, dtype in obs.column_dtypes(table, self.transformations).items() if obs._dtype_kind(dtype) == "f" and dtype.itemsize < 8]
+        if narrow:
+            say_once(LOG, (type(self), "float64"), "apply_column_transformations: float32 and float16 columns (here %s) are read as float64 and "
+                     "the result is float64 (numpy would stay in float32)", narrow, level=logging.INFO)
+        return _with_columns(table, added, any(isinstance(table[c], torch.Tensor) for c in names))
+
+
+filter_registry.register("apply_column_transformations", ApplyColumnTransformations)
 filter_registry.register("fill_orography", FillHeights)
 filter_registry.register("geopotential_to_height_tabular", GeopotentialToHeightTabular)
 filter_registry.register("irregular_to_grid", IrregularToGrid)

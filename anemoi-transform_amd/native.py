@@ -122,6 +122,7 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
         [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p,
          c_void_p, c_void_p, c_void_p],
     ),
+    "atx_obs_column_ops": (c_int, [c_int32, POINTER(c_int32), POINTER(c_int32), POINTER(c_void_p), POINTER(c_void_p), c_int64, c_void_p]),
     "atx_mask_build": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_double, c_int, c_void_p]),
     "atx_mask_count": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
     "atx_mask_to_index_workspace": (c_size_t, [c_int64]),
@@ -605,6 +606,26 @@ def obs_fill_heights(latitude, longitude, altitude, lat_axis, lat_perm, lon_axis
     pitch = heights.stride(0) if n_lat > 1 else max(n_lon, 1)
     _call("atx_obs_fill_heights", _ptr(latitude), _ptr(longitude), _ptr(altitude), n, _ptr(lat_axis), _ptr(lat_perm), n_lat, _ptr(lon_axis),
           _ptr(lon_perm), n_lon, _ptr(heights), pitch, dtype_code(heights.dtype), _ptr(out), _ptr(flags), _ptr(counters), _stream())
+
+
+MAX_COLUMN_OPS = 16
+# the ATX_COLOP_* codes by the reference's function names (R: filters/tabular/apply_column_transformations.py:31-42, in its order)
+COLUMN_OPS = {"log": 0, "log1p": 1, "safe_log": 2, "sqrt": 3, "exp": 4, "abs": 5, "sin": 6, "sin_deg": 7, "cos": 8, "cos_deg": 9}
+
+
+def obs_column_ops(ops, n: int) -> None:
+    """One launch of ``atx_obs_column_ops`` over ``n`` rows.  ``ops``: 1 .. ``MAX_COLUMN_OPS`` tuples ``(code, src, column, out)`` —
+    ``code`` an ATX_COLOP_* value; ``src`` -1 to read ``column`` (a float64 device row of ``n``), or the index of the earlier
+    operation whose result is taken (``column`` is then ignored and may be ``None``); ``out`` a float64 device row of ``n`` or ``None``
+    for an intermediate.  ``out`` may be ``column``.  Does not synchronise."""
+    for _, src, column, out in ops:
+        _rows(column if src < 0 else None, out, n=n)
+    k = len(ops)
+    codes = (c_int32 * k)(*[int(o[0]) for o in ops])
+    srcs = (c_int32 * k)(*[int(o[1]) for o in ops])
+    ins = (c_void_p * k)(*[_ptr(o[2]) if o[1] < 0 else None for o in ops])
+    outs = (c_void_p * k)(*[_ptr(o[3]) for o in ops])
+    _call("atx_obs_column_ops", k, codes, srcs, ins, outs, n, _stream())
 
 
 def mask_build(m, mask, *, n, stride=1, cmp, threshold=0.0) -> None:

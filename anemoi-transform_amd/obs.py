@@ -24,12 +24,17 @@ sub-satellite table of ``add_msg_angles`` (torch on the device).
 The fourth is ``fill_orography`` (R: filters/tabular/fill_heights.py, support/utils.py:24-55): ``HeightGrid`` keeps an orography in HBM
 with its axes sorted, and ``fill_heights`` replaces the missing station altitudes of a table by the nearest orography height in one
 launch (``atx_obs_fill_heights``); rows with two equally near axis entries go back to the host's ``cKDTree``.
+
+The fifth is ``apply_column_transformations`` (R: filters/tabular/apply_column_transformations.py): ``compile_column_program`` turns
+the ordered list of (target, source, function) into runs of at most 16 operations, and ``column_ops`` launches each run once
+(``atx_obs_column_ops``): a transformation that reads an earlier one's target takes it from a register, not from memory.
 """
 
 from __future__ import annotations
 
 import datetime
 import re
+from collections.abc import Mapping
 from typing import Any, NamedTuple, Sequence
 
 import numpy as np
@@ -604,3 +609,133 @@ def fill_heights(grid: HeightGrid, latitude: Any, longitude: Any, altitude: Any,
         j = grid.nearest(1, lon[rows].cpu().numpy(), (bits & native.FILL_TIE_LONGITUDE) != 0)
         out[rows] = grid.heights[_device(i.astype(np.int64), dev), _device(j.astype(np.int64), dev)].to(torch.float64)
     return (out, (filled, flagged)) if return_counts else out
+
+
+# ---- library functions over columns (R: filters/tabular/apply_column_transformations.py) --------------------------------------------
+COLUMN_FUNCTIONS = tuple(native.COLUMN_OPS)  # the reference's ten names, in its order
+
+
+class ColumnOp(NamedTuple):
+    """One operation of a kernel step: ``target = function(source)``.  ``src``: the index, within the step, of the LATEST earlier
+    operation whose target is ``source`` — its result is taken from a register — or -1: the column is read from memory.  ``store``:
+    False where a later operation of the same step has the same target, so nothing is written."""
+    function: str
+    target: str
+    source: str
+    src: int
+    store: bool
+
+
+class KernelStep(NamedTuple):
+    """One launch of ``atx_obs_column_ops``: 1 .. 16 operations."""
+    ops: tuple[ColumnOp, ...]
+
+
+class IntegerAbs(NamedTuple):
+    """``abs`` of an integer column: it keeps its dtype, as ``np.abs`` does, so it runs outside the float64 kernel."""
+    target: str
+    source: str
+
+
+def _dtype_kind(dtype: Any) -> str:
+    """numpy's kind letter of a numpy or torch dtype: b, i, u, f, c — anything else is not numeric."""
+    if isinstance(dtype, torch.dtype):
+        if dtype == torch.bool:
+            return "b"
+        if dtype.is_complex:
+            return "c"
+        return "f" if dtype.is_floating_point else ("u" if str(dtype).startswith("torch.uint") else "i")  # uint8, uint16, uint32, uint64
+    return np.dtype(dtype).kind
+
+
+def compile_column_program(spec: Sequence[tuple[str, str, str]], dtypes: Mapping[str, Any]) -> list[KernelStep | IntegerAbs]:
+    """The ordered transformations ``[(target, source, function), ...]`` over a table whose columns have the (numpy or torch)
+    ``dtypes``, as the steps that compute them: pure host logic.
+
+    A ``KernelStep`` is a run of consecutive transformations, at most ``native.MAX_COLUMN_OPS``; within it a source that an earlier
+    operation of the run wrote is that operation's result (``ColumnOp.src``), and a target that a later operation of the run writes
+    again is not stored.  ``abs`` of a column that is integer AT THAT POINT (a table column, or the result of an earlier integer
+    ``abs``) is an ``IntegerAbs`` and ends the run before it.  Between steps a column goes through memory.
+
+    ``ValueError``: a function that is not one of ``COLUMN_FUNCTIONS``; a source that is bool, complex or not numeric.  ``KeyError``: a
+    source that is neither a column of the table nor an earlier target."""
+    kinds = {name: _dtype_kind(dt) for name, dt in dtypes.items()}
+    steps: list[KernelStep | IntegerAbs] = []
+    run: list[ColumnOp] = []
+
+    def close() -> None:
+        if run:
+            last = {op.target: t for t, op in enumerate(run)}
+            steps.append(KernelStep(tuple(op._replace(store=last[op.target] == t) for t, op in enumerate(run))))
+            run.clear()
+
+    for target, source, function in spec:
+        if function not in native.COLUMN_OPS:
+            raise ValueError(f"Invalid transformation: {function}")
+        if source not in kinds:
+            raise KeyError(f"DataFrame must contain columns {(source,)} for transformation.")
+        if kinds[source] not in "iuf":
+            raise ValueError(f"column {source!r}: a numeric column is needed, got dtype {dtypes.get(source, 'bool')}")
+        if function == "abs" and kinds[source] in "iu":
+            close()
+            steps.append(IntegerAbs(target, source))
+            kinds[target] = kinds[source]
+            continue
+        if len(run) == native.MAX_COLUMN_OPS:
+            close()
+        src = max((t for t, op in enumerate(run) if op.target == source), default=-1)
+        run.append(ColumnOp(function, target, source, src, True))
+        kinds[target] = "f"
+    close()
+    return steps
+
+
+def column_dtypes(columns: Mapping[str, Any], spec: Sequence[tuple[str, str, str]]) -> dict[str, Any]:
+    """The dtypes of the columns of the table that ``spec`` names as sources (``compile_column_program``'s second argument)."""
+    names = {source for _, source, _ in spec} & set(columns.keys())
+    return {name: (columns[name].dtype if isinstance(columns[name], torch.Tensor) else _host_array(columns[name]).dtype) for name in names}
+
+
+def column_ops(columns: Mapping[str, Any], spec: Sequence[tuple[str, str, str]], dev: torch.device | None = None) -> dict[str, torch.Tensor]:
+    """``{target: device row}`` of the transformations ``[(target, source, function), ...]`` applied in order to the table ``columns``
+    (a mapping or DataFrame of numpy arrays, pandas Series or device tensors), in the order the targets first appear
+    (R: apply_column_transformations.py:55-61, :132-138).  One launch of ``atx_obs_column_ops`` per ``KernelStep`` of
+    ``compile_column_program``; a repeated target is fine, the last one stands.
+
+    Sources are read as float64 (``float_column``: a float64 device tensor is used in place, integers convert as numpy's cast does)
+    and results are float64 — except ``abs`` of an integer column, which keeps its dtype (``torch.abs``).  The caller's columns are
+    never written: every target, one equal to its source included, is a fresh row."""
+    spec = [tuple(item) for item in spec]
+    steps = compile_column_program(spec, column_dtypes(columns, spec))  # the host's errors come before anything touches the device
+    if dev is None:  # where the table's device tensors are, else this process's device
+        held = (columns[name] for name in columns.keys())
+        dev = next((c.device for c in held if isinstance(c, torch.Tensor) and c.is_cuda), None) or _stack.device()
+    current: dict[str, Any] = {}  # the targets written so far
+    as_float: dict[str, torch.Tensor] = {}  # float64 device rows of the columns read so far
+
+    def row(name: str) -> torch.Tensor:
+        if name not in as_float:
+            as_float[name] = float_column(current[name] if name in current else columns[name], dev)
+        return as_float[name]
+
+    for step in steps:
+        if isinstance(step, IntegerAbs):
+            col = current[step.source] if step.source in current else columns[step.source]
+            if not isinstance(col, torch.Tensor):
+                col = torch.from_numpy(np.ascontiguousarray(_host_array(col)).reshape(-1))
+            col = col.reshape(-1).to(dev)
+            # an unsigned column is its own absolute value (torch has no abs for most unsigned types)
+            written = {step.target: col.clone() if _dtype_kind(col.dtype) == "u" else torch.abs(col)}
+        else:
+            inputs = [row(op.source) if op.src < 0 else None for op in step.ops]
+            lengths = {c.numel() for c in inputs if c is not None}
+            if len(lengths) > 1:
+                raise ValueError(f"columns differ in length: { {op.source: c.numel() for op, c in zip(step.ops, inputs) if c is not None} }")
+            n = lengths.pop()  # the first operation of a step always reads memory
+            outs = [torch.empty(n, dtype=torch.float64, device=dev) if op.store else None for op in step.ops]
+            native.obs_column_ops([(native.COLUMN_OPS[op.function], op.src, c, o) for op, c, o in zip(step.ops, inputs, outs)], n)
+            written = {op.target: o for op, o in zip(step.ops, outs) if op.store}
+        for name, col in written.items():
+            current[name] = col
+            as_float.pop(name, None)
+    return {target: current[target] for target in dict.fromkeys(t for t, _, _ in spec)}

@@ -68,7 +68,8 @@
 extern "C" {
 #endif
 
-#define ATX_VERSION 420 /* 0.4.2 — additions only, so the number stays: atx_obs_fill_heights (missing station altitudes from an
+#define ATX_VERSION 420 /* 0.4.2 — additions only, so the number stays: atx_obs_column_ops (a program of library functions over
+                           * columns) with its ATX_COLOP_* codes; atx_obs_fill_heights (missing station altitudes from an
                            * orography); atx_healpix_ang2pix (HEALPix pixel indices per row) with its atx_healpix_scheme enum; atx_obs_forcings / atx_obs_view_angles / atx_obs_planck_bt (per-row
                            * observation operators); atx_obs_group_mean / atx_obs_group_argmin (superob: per-group
                            * means by pandas' row-order Kahan rule and the nearest row of every group); atx_obs_best_per_cell / atx_obs_fill_stack (observation tables
@@ -505,6 +506,46 @@ ATX_API int atx_obs_fill_heights(const double* latitude, const double* longitude
                                  const int32_t* lat_perm, int64_t n_lat, const double* lon_axis, const int32_t* lon_perm, int64_t n_lon,
                                  const void* heights, int64_t heights_pitch, int dtype /* atx_dtype */, double* out, uint8_t* flags,
                                  int64_t* counters, void* stream);
+
+/* A program of up to ATX_MAX_COLUMN_OPS single-input functions over float64 columns of n rows, in ONE pass: for t = 0 .. n_ops - 1,
+ *   x = src[t] < 0 ? in[t][r] : (the result of operation src[t] for row r);   y = f_op[t](x);   if (out[t]) out[t][r] = y;
+ * which is what the reference's loop of numpy ufuncs over the columns of a DataFrame computes when a later transformation reads an
+ * earlier one's target.  op[t] is an ATX_COLOP_* code:
+ *   LOG       log(x)                        the library's own routine, <= 1 ulp
+ *   LOG1P     log1p(x)                      the device library's, 1 ulp; x itself for |x| < 2^-54, correctly rounded (the library's log1p(-0.0) is +0.0)
+ *   SAFE_LOG  log(x + 1e-10)                the sum rounded once in float64, as numpy's
+ *   SQRT      sqrt(x)                       correctly rounded: numpy's bits
+ *   EXP       exp(x)                        the library's own routine, <= 1 ulp
+ *   ABS       fabs(x)                       the sign bit cleared: -0.0 -> +0.0, a NaN keeps its payload
+ *   SIN, COS  sin(x), cos(x)                the library's own routine for |x| < 1e5 (< 1 ulp), the device library's beyond (2 ulps)
+ *   SIN_DEG, COS_DEG  sin / cos(x * (pi / 180))   np.deg2rad's product, one rounding, then as SIN / COS
+ * Specials are the functions' own: log(0) = -inf, log(-1) = NaN, log1p(-1) = -inf, sqrt(-0.0) = -0.0, exp overflows to inf,
+ * sin(+-inf) = NaN.  No contraction anywhere.
+ *   op, src   HOST int32 [n_ops]
+ *   in, out   HOST arrays of n_ops DEVICE pointers to double [n]; they are copied into the kernel's arguments, so they may be freed on
+ *             return.  in[t] is read only where src[t] < 0 (anything else there is ignored).  out[t] may be NULL: the result is an
+ *             intermediate, taken by a later operation through src or replaced by a later operation with the same target.  out[t] may
+ *             be any in[.] (in place): a lane loads a column before it stores to it, in program order.
+ * The caller guarantees that no operation reads from memory a column that an EARLIER operation of the same call writes: that
+ * dependency goes through src.  A column that a LATER operation writes may be read.
+ * n_ops outside 1 .. ATX_MAX_COLUMN_OPS, an unknown code, src[t] >= t, in[t] == NULL where src[t] < 0 (n > 0), a null program array,
+ * n < 0: ATX_EINVAL, nothing launched.
+ *   R: filters/tabular/apply_column_transformations.py:18-42 (the ten functions), :55-61 (apply), :132-138 (in order, chained) */
+#define ATX_MAX_COLUMN_OPS 16
+enum {
+    ATX_COLOP_LOG = 0,
+    ATX_COLOP_LOG1P = 1,
+    ATX_COLOP_SAFE_LOG = 2,
+    ATX_COLOP_SQRT = 3,
+    ATX_COLOP_EXP = 4,
+    ATX_COLOP_ABS = 5,
+    ATX_COLOP_SIN = 6,
+    ATX_COLOP_SIN_DEG = 7,
+    ATX_COLOP_COS = 8,
+    ATX_COLOP_COS_DEG = 9
+};
+ATX_API int atx_obs_column_ops(int32_t n_ops, const int32_t* op, const int32_t* src, const double* const* in, double* const* out, int64_t n,
+                               void* stream);
 
 /* ---- masks ------------------------------------------------------------------ */
 
