@@ -7,6 +7,9 @@
 namespace atx {
 
 static thread_local std::string g_last_error;
+// The launch form the calling thread's last atx_pointwise_stack took (atx_last_route): a literal, set by the dispatcher of
+// atx_pointwise.hip.  Diagnostic only.
+__thread const char* g_last_route = "none";
 
 void set_error(const char* fmt, ...) {
     char buf[512];
@@ -28,6 +31,8 @@ int hip_status(hipError_t e, const char* what) {
 extern "C" int atx_version(void) { return ATX_VERSION; }
 
 extern "C" const char* atx_last_error(void) { return atx::g_last_error.c_str(); }
+
+extern "C" const char* atx_last_route(void) { return atx::g_last_route; }
 
 extern "C" const char* atx_strerror(int code) {
     switch (code) {

@@ -16,6 +16,7 @@ namespace atx {
 
 // ---- host-side error plumbing ------------------------------------------------
 void set_error(const char* fmt, ...);  // defined in atx_api.hip
+extern __thread const char* g_last_route;  // defined in atx_api.hip; atx_pointwise.hip names the launch form it takes (atx_last_route)
 int hip_status(hipError_t e, const char* what);
 
 // Internal status, never returned across the C ABI: the per-level operator tables of this call do not fit the 64 KB a workgroup

@@ -579,6 +579,7 @@ static Routed route_sparse(const ColumnsCall<T>& k) {
     const int64_t n_items = k.n_pts * active.n;
     const int64_t blocks = (n_items + kBlock - 1) / kBlock;
     ATX_REQUIRE(blocks <= 0x7fffffffll, ATX_ENOTIMPL, "pointwise: %lld items exceed one launch", (long long)n_items);
+    g_last_route = "sparse";
     hipLaunchKernelGGL((pointwise_cols_sparse_kernel<T, VEC>), dim3((unsigned)blocks), dim3(kBlock), 0, k.st, k.y, n_items, k.n_lev, k.C, k.yp,
                        active, k.prog, k.vec_prog, k.n_stage, k.mask);
     ATX_LAUNCH_CHECK("pointwise_stack_sparse");
@@ -602,6 +603,7 @@ static Routed route_uniform(const ColumnsCall<T>& k) {
     }
     const int need_rc = (two_pieces || (uses_mask && k.mask) || !k.tight) ? 1 : 0;
     const bool nt = !(uses_mask && k.mask);
+    g_last_route = "uniform";
     with_trans_nt(k.transcendental(), nt, [&](auto tr, auto n) {
         hipLaunchKernelGGL((pointwise_cols_uniform_kernel<T, VEC, decltype(tr)::value, decltype(n)::value>), k.vector_grid(), dim3(kBlock), 0, k.st,
                            k.x, k.y, k.n_vec, k.C, k.Cp, uni, uses_mask ? k.mask : nullptr, need_rc, k.in_place, act_bits);
@@ -625,6 +627,7 @@ static Routed route_runs(const ColumnsCall<T>& k) {
     for (int s = 0; s < k.n_stage; ++s)
         for (int r = 0; r < runs.n_run[s]; ++r) uses_mask = uses_mask || runs.op[s][r].use_mask != 0;
     const bool nt = !(uses_mask && k.mask);
+    g_last_route = "runs";
     with_trans_nt(k.transcendental(), nt, [&](auto tr, auto n) {
         hipLaunchKernelGGL((pointwise_cols_runs_kernel<T, VEC, decltype(tr)::value, decltype(n)::value>), k.vector_grid(), dim3(kBlock), 0, k.st,
                            k.x, k.y, k.n_vec, k.C, k.Cp, runs, uses_mask ? k.mask : nullptr);
@@ -643,6 +646,7 @@ static Routed route_table(const ColumnsCall<T>& k) {
     if (!(k.slots && k.tight && k.vec_prog && !k.mask && sizeof(T) == 4 && k.n_stage == 1 && k.one_launch &&
           !program_has_mixed_vectors<T>(k.host_prog, k.n_stage, k.n_lev, VEC)))  // (mixed vectors: the chunked kernel serves them better)
         return std::nullopt;
+    g_last_route = "table";
     hipLaunchKernelGGL((pointwise_cols_table_kernel<T, VEC>), k.vector_grid(), dim3(kBlock), 0, k.st, k.x, k.y, k.n_vec, k.n_lev, k.C, k.prog,
                        k.vec_prog, k.n_stage, k.mask, k.in_place);
     ATX_LAUNCH_CHECK("pointwise_stack");
@@ -666,6 +670,7 @@ static Routed route_typed(const ColumnsCall<T>& k) {
     const unsigned char* level_tables = reinterpret_cast<const unsigned char*>(k.vec_prog) +
                                         level_tables_layout(1, k.n_lev, sizeof(T) == 4 ? ATX_F32 : ATX_F64).levels_offset;
     const bool nt = !(uses_mask && k.mask);
+    g_last_route = "typed";
     with_trans_nt(k.transcendental(), nt, [&](auto tr, auto n) {
         hipLaunchKernelGGL((pointwise_cols_typed_kernel<T, VEC, decltype(tr)::value, decltype(n)::value>), k.vector_grid(), dim3(kBlock), 0, k.st,
                            k.x, k.y, k.n_vec, k.C, level_tables, uses_mask ? k.mask : nullptr, k.in_place);
@@ -690,6 +695,7 @@ static Routed route_levels(const ColumnsCall<T>& k) {
         hipLaunchKernelGGL((pointwise_cols_levels_kernel<T, VEC, decltype(tr)::value, decltype(n)::value>), k.chunk_grid(), dim3(kBlock), lds_levels, k.st,
                            k.x, k.y, k.n_pts, k.n_lev, k.C, k.Cp, k.prog, k.n_stage, k.mask, k.in_place);
     };
+    g_last_route = "levels";
     if (k.transcendental()) launch(std::true_type{}, std::false_type{});
     else with_flag(nt, [&](auto n) { launch(std::false_type{}, n); });
     ATX_LAUNCH_CHECK("pointwise_stack_levels");
@@ -704,6 +710,7 @@ static Routed route_flat(const ColumnsCall<T>& k) {
     const size_t lds_flat = (size_t)k.n_stage * k.C * sizeof(LevelOp<T>) + (size_t)k.C;
     if (lds_flat > 64 * 1024 && k.n_stage > 1) return ATX_SPLIT_PROGRAM;  // the entry point runs the stages in two halves
     ATX_REQUIRE(lds_flat <= 64 * 1024, ATX_ENOTIMPL, "pointwise: one stage over %d levels needs %zu B of LDS", k.n_lev, lds_flat);
+    g_last_route = "flat";
     with_flag(k.transcendental(), [&](auto tr) {  // no exp / log anywhere: the low-register instantiation (8 instead of 4 waves per SIMD in float64)
         hipLaunchKernelGGL((pointwise_cols_flat_kernel<T, VEC, decltype(tr)::value>), k.chunk_grid(), dim3(kBlock), lds_flat, k.st, k.x, k.y, k.n_pts,
                            k.n_lev, k.C, k.prog, k.n_stage, k.mask, k.in_place);
@@ -723,6 +730,7 @@ static Routed route_row_chunk(const ColumnsCall<T>& k) {
     const int64_t chunk = (int64_t)(kBlock / Cg) * kPwUnroll;  // rows one workgroup moves per iteration
     int64_t blocks = (k.n_pts + chunk - 1) / chunk;
     if (blocks > kStreamGrid) blocks = kStreamGrid;
+    g_last_route = k.wide ? "row_chunk" : "row_chunk_scalar";
     if (k.wide)
         hipLaunchKernelGGL((pointwise_cols_kernel<T, VEC>), dim3((unsigned)blocks), dim3(kBlock), lds_rows, k.st, k.x, k.y, k.n_pts, k.n_lev, k.C, k.xp,
                            k.yp, k.prog, k.n_stage, k.mask, k.in_place);
@@ -776,6 +784,7 @@ static int pointwise_fields(const void* x_, void* y_, int64_t n_pts, int n_lev, 
     const bool trans = program_has_transcendental(host_prog, n_stage, n_lev);
     const int mask_vec = (reinterpret_cast<uintptr_t>(mask) % (uintptr_t)vec) == 0 ? 1 : 0;
     const dim3 grid((unsigned)gx_rows, (unsigned)n_lev);
+    g_last_route = vec_ok ? "fields" : "fields_scalar";
     if (vec_ok)  // non-temporal when no mask is read
         with_trans_nt(trans, !uses_mask, [&](auto tr, auto n) {
             hipLaunchKernelGGL((pointwise_fields_rows_kernel<T, VEC, decltype(tr)::value, decltype(n)::value>), grid, dim3(kBlock), 0, st, x, y, n_pts,
@@ -798,6 +807,7 @@ extern "C" int atx_pointwise_stack(const void* x, void* y, int64_t n_pts, int64_
                                    int64_t y_pitch, int dtype, int layout, const atx_level_op* prog,
                                    const atx_level_op* vec_prog, const atx_level_op* host_prog, int32_t n_stage,
                                    const uint8_t* point_mask, void* stream) {
+    g_last_route = "none";  // until a route launches (atx_last_route)
     ATX_REQUIRE(prog && ((x && y) || n_pts == 0), ATX_EINVAL, "atx_pointwise_stack: null pointer");  // (an empty stack may have no storage)
     ATX_REQUIRE(dtype == ATX_F32 || dtype == ATX_F64, ATX_EINVAL, "atx_pointwise_stack: bad dtype %d", dtype);
     ATX_REQUIRE(layout == ATX_COLUMNS || layout == ATX_FIELDS, ATX_EINVAL, "atx_pointwise_stack: bad layout %d", layout);

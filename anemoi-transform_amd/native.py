@@ -59,6 +59,7 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     "atx_version": (c_int, []),
     "atx_last_error": (c_char_p, []),
     "atx_strerror": (c_char_p, [c_int]),
+    "atx_last_route": (c_char_p, []),
     "atx_device_count": (c_int, []),
     "atx_set_tuning": (c_int, [c_int]),
     "atx_regrid_ell": (
@@ -422,6 +423,11 @@ def pointwise_stack(x, y, *, n_pts, n_lev, x_pitch, y_pitch, layout, prog, n_sta
         "atx_pointwise_stack", _ptr(x), _ptr(y), n_pts, n_lev, x_pitch, y_pitch, dtype_code(x.dtype), layout,
         _ptr(prog), vec, host, n_stage, _ptr(point_mask), _stream(),
     )
+
+
+def last_route() -> str:
+    """The launch form this thread's last ``pointwise_stack`` took (``atx_last_route``: a diagnostic, ``"none"`` when it launched nothing)."""
+    return load().atx_last_route().decode()
 
 
 def combine_stack(op: int, inputs, outputs, *, n_pts, n_lev, pitch, layout, level_param=None, flags: int = 0) -> None:

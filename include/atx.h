@@ -151,6 +151,12 @@ typedef struct {
 ATX_API int atx_version(void);
 ATX_API const char* atx_last_error(void);          /* host string, valid until the next failing call of this thread */
 ATX_API const char* atx_strerror(int code);        /* host string, static */
+/* DIAGNOSTIC, not part of the numerical contract: the launch form the calling thread's last atx_pointwise_stack took — "sparse",
+ * "uniform", "runs", "table", "typed", "levels", "flat", "row_chunk", "row_chunk_scalar" (column stacks), "fields", "fields_scalar"
+ * (field-major stacks) — or "none" when that call returned before any launch (no points, an in-place program with nothing to do, an
+ * argument error) and before the first call.  After a program that was run in two halves (per-level tables beyond the LDS) it names
+ * the second half's.  Which form serves which call may change between versions; results never depend on it.  Host string, static. */
+ATX_API const char* atx_last_route(void);
 /* Number of HIP devices visible, or a negative ATX_EHIP. */
 ATX_API int atx_device_count(void);
 /* Tuning hook for benchmarks and tests: tile > 0 runs the ATX_COLUMNS regrid through the TILED kernels with that

@@ -13,7 +13,9 @@ int main(void) {
     /* null pointers are rejected before any launch, with a message */
     if (atx_regrid_ell(NULL, NULL, NULL, NULL, 1, 1, 1, 1, 1, 1, ATX_F32, ATX_COLUMNS, 0, NULL, NULL, NULL, 0, NULL, NULL) != ATX_EINVAL) ++failures;
     if (strstr(atx_last_error(), "null") == NULL) ++failures;
+    if (strcmp(atx_last_route(), "none") != 0) ++failures; /* before the first call */
     if (atx_pointwise_stack(NULL, NULL, 1, 1, 1, 1, ATX_F64, ATX_FIELDS, NULL, NULL, NULL, 1, NULL, NULL) != ATX_EINVAL) ++failures;
+    if (strcmp(atx_last_route(), "none") != 0) ++failures; /* a call that launched nothing */
     if (atx_bcast(NULL, NULL, 0, 0, NULL) != ATX_EINVAL) ++failures;
     if (atx_comm_destroy(NULL) != ATX_OK) ++failures;
     {

@@ -609,9 +609,12 @@ def test_float64_exp_within_one_ulp_of_numpy(dev):
 @pytest.mark.parametrize("program", ["uniform_1", "uniform_4", "uniform_5", "two_pieces", "two_pieces_one_idle", "masked_uniform", "masked_piece",
                                      "transcendental", "per_level"])
 def test_pointwise_kernel_routes_agree(dev, tdtype, np_dtype, in_place, program):
-    """The per-point launch takes one of three kernels on a tight column stack — operators by value (programs uniform over the
-    levels, or two pieces split on a 16-byte boundary; needs the program's host copy), the per-vector table, the chunked kernel —
-    and all three must give the oracle's values and each other's bits.  n_lev = 24: vectors of 4 (f32) and 2 (f64) levels."""
+    """The same program with its companions taken off one by one lands on different launch forms of the per-point dispatcher
+    (``native.last_route()``, asserted below; tests/test_gpu_pointwise_routes.py holds all eleven) — with the host copy AND the
+    per-vector table: `uniform` (operators by value: programs uniform over the levels, or two pieces split on a 16-byte boundary, up
+    to four stages), else `levels`; with the table alone: `table` for one-stage float32 programs without a mask, else `levels`;
+    with neither: `levels` — and all must give the oracle's values and each other's bits.  n_lev = 24: vectors of 4 (f32) and 2
+    (f64) levels; the sparse form never applies (more than a third of the vector columns is active in every program)."""
     import native_double
 
     rng = np.random.default_rng(23)
@@ -654,9 +657,14 @@ def test_pointwise_kernel_routes_agree(dev, tdtype, np_dtype, in_place, program)
         out = src if in_place else src.new_like()
         native.pointwise_stack(src.data, out.data, n_pts=n_pts, n_lev=n_lev, x_pitch=src.pitch, y_pitch=out.pitch, layout=COLUMNS, prog=prog,
                                n_stage=len(stages), point_mask=pm_d)
+        routes.append(native.last_route())
         return out.numpy()
 
+    routes = []
     by_value, table, chunked = run(()), run(("host_prog",)), run(("host_prog", "vec_prog"))
+    full = "levels" if program in ("uniform_5", "per_level") else "uniform"
+    table_only = "table" if (np_dtype == np.float32 and len(stages) == 1 and not uses_mask) else "levels"
+    assert routes == [full, table_only, "levels"], (program, routes)
     want = x.copy()
     for stage in stages:
         for l, (op, use_mask, p0, p1) in enumerate(stage):
