@@ -15,12 +15,16 @@
 #include "atx_common.hpp"
 #include "atx_regrid_decl.hpp"
 
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
 namespace atx {
 
 thread_local int g_tile_override = 0;  // tuning hook (atx_set_tuning): per calling thread, meant for benchmarks and tests (results never depend on it)
+
+// The launch form of this thread's last gather (atx_last_gather_route): filled by the launchers, a second cell beside g_last_route.
+__thread GatherRoute g_gather_route = {nullptr, nullptr, nullptr, nullptr, 0, false, false, false, false, false};
 
 // Entries of a table outside [lo, hi), counted on the device: atx_check_indices (lo = 0), and ATX_VALIDATE with a lower bound of -1
 // where ATX_ELL_PADDED marks absent entries with -1 and, for ordered traversals, over a row table that must stay inside [0, n_tgt).
@@ -96,6 +100,15 @@ static int check_stack_args(const char* fn, const void* src, const void* out, in
 
 using namespace atx;
 
+extern "C" const char* atx_last_gather_route(void) {
+    static thread_local char text[128];
+    const GatherRoute& r = g_gather_route;
+    if (!r.table) return "none";
+    std::snprintf(text, sizeof text, "%s/%s/%s/%s/k%d/%s/%s/%s/%s", r.table, r.kernel, r.split ? "split" : r.epilogue, r.width, r.k,
+                  r.padded ? "padded" : "plain", r.weighted ? "weighted" : "pure", r.stripe ? "stripe" : "range", r.ordered ? "ordered" : "natural");
+    return text;
+}
+
 extern "C" int atx_set_tuning(int tile) {
     g_tile_override = tile;
     return ATX_OK;
@@ -106,6 +119,7 @@ static int regrid_ell_common(const char* fn, const void* const* srcs, void* cons
                              int64_t out_pitch, int dtype, int layout, int32_t flags, const atx_level_op* prog,
                              const atx_level_op* vec_prog, const atx_level_op* host_prog, int32_t n_stage, const uint8_t* tgt_mask,
                              const int32_t* tgt_rows, void* stream) {
+    g_gather_route.table = nullptr;  // "none" until a gather launches (atx_last_gather_route)
     ATX_REQUIRE(srcs && outs && n_stack >= 1, ATX_EINVAL, "%s: needs at least one stack", fn);
     ATX_REQUIRE(!tgt_rows || layout == ATX_COLUMNS, ATX_ENOTIMPL, "%s: an ordered traversal (tgt_rows) is available for ATX_COLUMNS stacks only", fn);
     for (int32_t i = 0; i < n_stack; ++i) {
@@ -151,6 +165,7 @@ static int regrid_ell_common(const char* fn, const void* const* srcs, void* cons
             Epilogue plain;
             plain.tgt_rows = tgt_rows;
             rc = run(plain);
+            g_gather_route.split = true;
             for (int i = 0; i < batch.n && rc == ATX_OK; ++i)
                 rc = atx_pointwise_stack(batch.out[i], batch.out[i], n_tgt, n_lev, out_pitch, out_pitch, dtype, layout, prog, vec_prog, host_prog,
                                          n_stage, tgt_mask, stream);
@@ -191,6 +206,7 @@ static int regrid_csr_common(const char* fn, const void* src, void* out, const i
                              const void* data, int64_t n_src, int64_t n_tgt, int64_t nnz, int64_t n_lev,
                              int64_t src_pitch, int64_t out_pitch, int dtype, int layout, const atx_level_op* prog,
                              int32_t n_stage, const uint8_t* tgt_mask, const int32_t* tgt_rows, void* stream) {
+    g_gather_route.table = nullptr;  // "none" until a gather launches (atx_last_gather_route)
     int st = check_stack_args(fn, src, out, n_src, n_tgt, n_lev, src_pitch, out_pitch, dtype, layout);
     if (st != ATX_OK) return st;
     ATX_REQUIRE(indptr || n_tgt == 0, ATX_EINVAL, "%s: null indptr", fn);
@@ -214,6 +230,7 @@ static int regrid_csr_common(const char* fn, const void* src, void* out, const i
     int rc = run(prog, n_stage, tgt_mask);
     if (rc == ATX_SPLIT_PROGRAM) {  // the fused tables do not fit in LDS: the plain product, then the program on its output in place
         rc = run(nullptr, 0, nullptr);
+        g_gather_route.split = true;
         if (rc == ATX_OK)
             rc = atx_pointwise_stack(out, out, n_tgt, n_lev, out_pitch, out_pitch, dtype, layout, prog, nullptr, nullptr, n_stage, tgt_mask, stream);
     }

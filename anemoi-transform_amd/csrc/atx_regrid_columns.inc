@@ -439,21 +439,22 @@ static int launch_cols_ell(const EllBatch& batch, const int32_t* idx, const T* w
             UniformOps<T> uniform{};
             RunOps<T> runs{};
             const unsigned char* level_tables = nullptr;
-            auto direct = [&](auto kind, const char* what) {
+            auto direct = [&](auto kind, const char* what, const char* epilogue) {
+                g_gather_route = GatherRoute{"cols_ell", "direct", epilogue, VEC == 1 ? "scalar" : "vec", K, PAD, WEIGHTED, stripe != 0, epi.tgt_rows != nullptr, false};
                 hipLaunchKernelGGL((regrid_cols_ell_direct_kernel<T, VEC, K, WEIGHTED, PAD, decltype(kind)::value>), dim3(n_blocks, batch.n),
                                    dim3(kEllBlock), 0, stream, batch, idx, w, n_items, C, src_pitch, out_pitch, n_blocks, 1, uniform, level_tables,
                                    n_stage, tgt_mask, epi.tgt_rows, runs, stripe);
                 ATX_LAUNCH_CHECK(what);
                 return (int)ATX_OK;
             };
-            if (!prog) return direct(IntTag<kEpiNone>{}, "regrid_cols_ell_direct");
-            if (uniform_program<T>(epi, n_lev, VEC, uniform)) return direct(IntTag<kEpiUniform>{}, "regrid_cols_ell_direct_uniform");
+            if (!prog) return direct(IntTag<kEpiNone>{}, "regrid_cols_ell_direct", "none");
+            if (uniform_program<T>(epi, n_lev, VEC, uniform)) return direct(IntTag<kEpiUniform>{}, "regrid_cols_ell_direct_uniform", "uniform");
             // several variables in one column (runs of levels with boundaries anywhere): by value, no table read beside the gather
-            if (runs_level_program<T>(epi.host_prog, n_stage, tgt_mask != nullptr, n_lev, runs)) return direct(IntTag<kEpiRuns>{}, "regrid_cols_ell_direct_runs");
+            if (runs_level_program<T>(epi.host_prog, n_stage, tgt_mask != nullptr, n_lev, runs)) return direct(IntTag<kEpiRuns>{}, "regrid_cols_ell_direct_runs", "runs");
             if (VEC == Vec16<T>::N && madd_family_program(epi, n_lev)) {  // the table is built for 16-byte vectors
                 level_tables = reinterpret_cast<const unsigned char*>(epi.vec_prog) +
                                level_tables_layout(n_stage, n_lev, sizeof(T) == 4 ? ATX_F32 : ATX_F64).levels_offset;
-                return direct(IntTag<kEpiTable>{}, "regrid_cols_ell_direct_table");
+                return direct(IntTag<kEpiTable>{}, "regrid_cols_ell_direct_table", "table");
             }
         }
     }
@@ -470,6 +471,7 @@ static int launch_cols_ell(const EllBatch& batch, const int32_t* idx, const T* w
     if (prog && lds > 64 * 1024) return ATX_SPLIT_PROGRAM;  // the caller gathers without the program and applies it afterwards
     ATX_REQUIRE(lds <= 64 * 1024, ATX_ENOTIMPL, "regrid_ell: tile needs %zu B of LDS (k=%d, n_lev=%d, stages=%d)", lds, k, n_lev, n_stage);
     constexpr int KT = K > 4 ? 0 : K;  // the tiled kernel keeps k > 4 on its runtime-k loop (compile-time k would hold 4 x k vectors per lane)
+    g_gather_route = GatherRoute{"cols_ell", "tiled", prog ? "lds" : "none", VEC == 1 ? "scalar" : "vec", KT, PAD, WEIGHTED, false, epi.tgt_rows != nullptr, false};
     with_flag(prog != nullptr, [&](auto fused) {
         hipLaunchKernelGGL((regrid_cols_ell_kernel<T, VEC, KT, WEIGHTED, decltype(fused)::value, PAD>), dim3(n_tiles, batch.n), dim3(kEllBlock), lds, stream,
                            batch, idx, w, n_tgt, k, n_lev, C, src_pitch, out_pitch, tile, n_tiles, prog, n_stage, tgt_mask, epi.tgt_rows);
@@ -539,6 +541,7 @@ static int launch_cols_csr(const T* src, T* out, const int32_t* indptr, const in
     // averages with rows of ~25: 0.859 -> 0.692 ms f32, 1.901 -> 1.363 ms f64; rows of 3-4 lose 2 % to stripes; 4 and 64 tiles per
     // stripe no better than 16 (profiles/r03_csr_stripes.log, tools/experiments/csr_stripes.py)
     const int stripe = (!rows && mean >= kCsrStripeMinMean) ? kCsrStripe : 0;
+    g_gather_route = GatherRoute{"cols_csr", "tiled", prog ? "lds" : "none", VEC == 1 ? "scalar" : "vec", 0, false, true, stripe != 0, rows != nullptr, false};
     with_flag(prog != nullptr, [&](auto fused) {
         hipLaunchKernelGGL((regrid_cols_csr_kernel<T, VEC, decltype(fused)::value>), dim3(n_tiles), dim3(kBlock), lds, st, src, out, indptr,
                            indices, data, n_tgt, n_lev, C, sp, op, tile, n_tiles, cap, prog, n_stage, m, rows, stripe);

@@ -30,6 +30,20 @@ struct Epilogue {
 
 extern thread_local int g_tile_override;  // atx_set_tuning; defined in atx_regrid.hip
 
+// The launch form of the calling thread's last gather (atx_last_gather_route, a diagnostic): every launcher stores literals and plain
+// integers here immediately before its launch — a few stores, no formatting; atx_regrid.hip builds the string when it is read.  It
+// never decides anything.
+struct GatherRoute {
+    const char* table;     // "cols_ell", "cols_csr", "fields_ell", "fields_csr"; nullptr: nothing launched
+    const char* kernel;    // "direct" / "tiled" (column stacks), "lanes" (fields_ell), "head4" / "head8" / "long" (fields_csr)
+    const char* epilogue;  // "none", "uniform", "runs", "table" (direct), "lds" (tiled, column CSR), "global" (field-major)
+    const char* width;     // "vec" / "scalar" (column stacks), "lane" (field-major: one target per lane)
+    int k;                 // compile-time k as instantiated, 0: the runtime loop (and CSR rows)
+    bool padded, weighted, stripe, ordered;
+    bool split;            // the program did not fit beside the tile: plain gather, then atx_pointwise_stack (set by atx_regrid.hip)
+};
+extern __thread GatherRoute g_gather_route;  // defined in atx_regrid.hip
+
 template <typename T>
 int regrid_ell_typed(const EllBatch& batch, const int32_t* idx, const void* w_, int64_t n_tgt, int k,
                             int n_lev, int64_t sp, int64_t op, int layout, bool pad, const Epilogue& e, hipStream_t st);

@@ -205,6 +205,7 @@ static int launch_fields_ell(const T* src, T* out, const int32_t* idx, const T* 
     const int lev_chunk = pick_lev_chunk(n_lev);
     const unsigned n_chunks = (unsigned)((n_lev + lev_chunk - 1) / lev_chunk);
     ATX_REQUIRE(n_chunks <= 65535, ATX_ENOTIMPL, "regrid_ell: too many level chunks (%u)", n_chunks);
+    g_gather_route = GatherRoute{"fields_ell", "lanes", prog ? "global" : "none", "lane", K, PAD, WEIGHTED, false, false, false};
     with_flag(prog != nullptr, [&](auto fused) {
         hipLaunchKernelGGL((regrid_fields_ell_kernel<T, K, WEIGHTED, decltype(fused)::value, PAD>), dim3(n_tiles, n_chunks), dim3(kBlock), 0, st,
                            src, out, idx, w, n_tgt, k, n_lev, sp, op, lev_chunk, n_tiles, prog, n_stage, m);
@@ -258,6 +259,7 @@ static int regrid_fields_csr(const T* src, T* out, const int32_t* indptr, const 
         const int lev_chunk = pick_lev_chunk(n_lev);
         const unsigned chunks = (unsigned)((n_lev + lev_chunk - 1) / lev_chunk);
         ATX_REQUIRE(chunks <= 65535, ATX_ENOTIMPL, "regrid_csr: too many level chunks (%u)", chunks);
+        g_gather_route = GatherRoute{"fields_csr", mean <= 4.0 ? "head4" : "head8", prog ? "global" : "none", "lane", 0, false, true, false, false, false};
         with_flag(prog != nullptr, [&](auto fused) {
             with_flag(mean <= 4.0, [&](auto four) {
                 hipLaunchKernelGGL((regrid_fields_csr_head_kernel<T, decltype(fused)::value, decltype(four)::value ? 4 : 8>), dim3(n_tiles, chunks),
@@ -269,6 +271,7 @@ static int regrid_fields_csr(const T* src, T* out, const int32_t* indptr, const 
     }
     const unsigned n_chunks = (unsigned)((n_lev + kFieldsChunk - 1) / kFieldsChunk);
     ATX_REQUIRE(n_chunks <= 65535, ATX_ENOTIMPL, "regrid_csr: too many level chunks (%u)", n_chunks);
+    g_gather_route = GatherRoute{"fields_csr", "long", prog ? "global" : "none", "lane", 0, false, true, false, false, false};
     with_flag(prog != nullptr, [&](auto fused) {
         hipLaunchKernelGGL((regrid_fields_csr_kernel<T, decltype(fused)::value>), dim3(n_tiles, n_chunks), dim3(kBlock), 0, st, src, out, indptr, indices,
                            data, n_tgt, n_lev, sp, op, n_tiles, prog, n_stage, m);

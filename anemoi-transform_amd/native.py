@@ -60,6 +60,7 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     "atx_last_error": (c_char_p, []),
     "atx_strerror": (c_char_p, [c_int]),
     "atx_last_route": (c_char_p, []),
+    "atx_last_gather_route": (c_char_p, []),
     "atx_device_count": (c_int, []),
     "atx_set_tuning": (c_int, [c_int]),
     "atx_regrid_ell": (
@@ -163,10 +164,13 @@ def lib_path() -> str:
     return os.environ.get("ATX_LIBRARY") or os.path.join(LIB_DIR, LIB_NAME)
 
 
-def open_library(path: str) -> ctypes.CDLL:
-    """A build of libatx.so with every prototype declared; raises if a symbol of the header is missing."""
+def open_library(path: str, older_build: bool = False) -> ctypes.CDLL:
+    """A build of libatx.so with every prototype declared; raises if a symbol of the header is missing — unless ``older_build`` says the
+    library may predate the header (an A/B timing against an earlier commit): its missing entry points are then left undeclared."""
     handle = ctypes.CDLL(path)
     for name, (restype, argtypes) in SIGNATURES.items():
+        if older_build and not hasattr(handle, name):
+            continue
         fn = getattr(handle, name)  # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes
@@ -428,6 +432,12 @@ def pointwise_stack(x, y, *, n_pts, n_lev, x_pitch, y_pitch, layout, prog, n_sta
 def last_route() -> str:
     """The launch form this thread's last ``pointwise_stack`` took (``atx_last_route``: a diagnostic, ``"none"`` when it launched nothing)."""
     return load().atx_last_route().decode()
+
+
+def last_gather_route() -> str:
+    """The launch form this thread's last ``regrid_ell`` / ``regrid_ell_batch`` / ``regrid_csr`` took (``atx_last_gather_route``: a
+    diagnostic, ``"none"`` when it launched nothing; on the ``split`` fallback ``last_route()`` names the per-point form that finished)."""
+    return load().atx_last_gather_route().decode()
 
 
 def combine_stack(op: int, inputs, outputs, *, n_pts, n_lev, pitch, layout, level_param=None, flags: int = 0) -> None:

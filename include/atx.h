@@ -157,6 +157,24 @@ ATX_API const char* atx_strerror(int code);        /* host string, static */
  * argument error) and before the first call.  After a program that was run in two halves (per-level tables beyond the LDS) it names
  * the second half's.  Which form serves which call may change between versions; results never depend on it.  Host string, static. */
 ATX_API const char* atx_last_route(void);
+/* DIAGNOSTIC, a second cell beside atx_last_route: the launch form the calling thread's last gather (atx_regrid_ell / _batch /
+ * _ordered, atx_regrid_csr / _ordered) took, nine fields joined by '/':
+ *   table      cols_ell | cols_csr | fields_ell | fields_csr              (layout and table)
+ *   kernel     direct | tiled (column stacks); lanes (fields_ell); head4 | head8 | long (fields_csr)
+ *   epilogue   none | uniform | runs | table (direct); none | lds (tiled, cols_csr); none | global (field-major); split when the
+ *              fused program did not fit beside the tile: the plain gather ran and atx_pointwise_stack finished the program in
+ *              place (atx_last_route then names the per-point form that did)
+ *   width      vec | scalar (column stacks: 16-byte vectors or single elements); lane (field-major)
+ *   k<K>       the compile-time k as instantiated, k0 for a runtime loop (the tiled kernel folds k > 4 to 0, padded tables start
+ *              at 3, CSR rows are always k0)
+ *   padded | plain        ATX_ELL_PADDED
+ *   weighted | pure       pure: the k = 1 gather without weights
+ *   range | stripe        how workgroups are dealt to the XCDs
+ *   ordered | natural     whether tgt_rows was given
+ * e.g. "cols_ell/direct/uniform/vec/k4/plain/weighted/range/natural".  "none" before the first call and after a call that launched
+ * nothing (n_tgt == 0, an argument error).  Of a batch cut into several launches it names the last.  Spelling and choice may change
+ * between versions; results never depend on it.  Host string, valid until the calling thread's next read. */
+ATX_API const char* atx_last_gather_route(void);
 /* Number of HIP devices visible, or a negative ATX_EHIP. */
 ATX_API int atx_device_count(void);
 /* Tuning hook for benchmarks and tests: tile > 0 runs the ATX_COLUMNS regrid through the TILED kernels with that

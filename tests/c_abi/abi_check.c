@@ -11,7 +11,9 @@ int main(void) {
     if (atx_version() != ATX_VERSION) { printf("version %d != header %d\n", atx_version(), ATX_VERSION); ++failures; }
     if (strcmp(atx_strerror(ATX_ESHAPE), "shape mismatch") != 0) ++failures;
     /* null pointers are rejected before any launch, with a message */
+    if (strcmp(atx_last_gather_route(), "none") != 0) ++failures; /* before the first call */
     if (atx_regrid_ell(NULL, NULL, NULL, NULL, 1, 1, 1, 1, 1, 1, ATX_F32, ATX_COLUMNS, 0, NULL, NULL, NULL, 0, NULL, NULL) != ATX_EINVAL) ++failures;
+    if (strcmp(atx_last_gather_route(), "none") != 0) ++failures; /* a call that launched nothing */
     if (strstr(atx_last_error(), "null") == NULL) ++failures;
     if (strcmp(atx_last_route(), "none") != 0) ++failures; /* before the first call */
     if (atx_pointwise_stack(NULL, NULL, 1, 1, 1, 1, ATX_F64, ATX_FIELDS, NULL, NULL, NULL, 1, NULL, NULL) != ATX_EINVAL) ++failures;

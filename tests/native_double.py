@@ -70,8 +70,71 @@ def _epilogue(levels: np.ndarray, prog, n_stage, mask, n_lev):
             levels[l] = _apply_op(table[s, l], levels[l].copy(), m)
 
 
+# ---- the gather's launch form, named as the dispatcher decides it (tests/gather_route_checks.py: decide_*) ---------------------------------
+_gather = {"route": "none", "tile": 0}
+
+
+def set_tuning(tile):
+    _gather["tile"] = int(tile)
+
+
+def last_gather_route():
+    """What ``atx_last_gather_route`` says after the same call on the device — the double launches nothing, it only decides."""
+    return _gather["route"]
+
+
+def _program_as_seen(prog, n_stage, n_lev, dtype):
+    if prog is None:
+        return None, False, None
+    vec = getattr(prog, "vec_prog", {}).get(dtype)
+    return _parse_prog(prog, n_stage, n_lev), getattr(prog, "host_prog", None) is not None, None if vec is None else vec.data_ptr()
+
+
+def _name_ell_route(srcs, outs, w, n_tgt, k, n_lev, src_pitch, out_pitch, layout, prog, n_stage, tgt_mask, padded, tgt_rows):
+    import gather_route_checks as G  # (imports this module)
+
+    _gather["route"] = "none"
+    if n_tgt == 0:
+        return
+    T = np.float32 if srcs[0].dtype == torch.float32 else np.float64
+    P, host, vec_ptr = _program_as_seen(prog, n_stage, n_lev, srcs[0].dtype)
+    if layout != COLUMNS:
+        _gather["route"] = G.decide_fields_ell(k, padded, w is not None, P).name()
+        return
+    for first in range(0, len(srcs), G.K.max_batch):  # (of a batch cut into several launches: the last)
+        pointers = [t.data_ptr() for t in list(srcs[first: first + G.K.max_batch]) + list(outs[first: first + G.K.max_batch])]
+        decide = lambda P, host, vec_ptr: G.decide_cols_ell(T, pointers, n_tgt, k, n_lev, src_pitch, out_pitch, padded, w is not None, P, host, vec_ptr,  # noqa: E731
+                                                            tgt_mask is not None, tgt_rows is not None, _gather["tile"])
+        launch = decide(P, host, vec_ptr)
+        if launch is None:  # ATX_SPLIT_PROGRAM: the plain gather, then the program through pointwise_stack
+            launch = decide(None, False, None)
+            launch.epilogue = "split"
+        _gather["route"] = launch.name()
+
+
+def _name_csr_route(src, out, n_tgt, nnz, n_lev, src_pitch, out_pitch, layout, prog, n_stage, tgt_rows):
+    import gather_route_checks as G
+
+    _gather["route"] = "none"
+    if n_tgt == 0:
+        return
+    T = np.float32 if src.dtype == torch.float32 else np.float64
+    P = None if prog is None else _parse_prog(prog, n_stage, n_lev)
+    if layout != COLUMNS:
+        _gather["route"] = G.decide_fields_csr(n_tgt, nnz, P).name()
+        return
+    decide = lambda P: G.decide_cols_csr(T, [src.data_ptr(), out.data_ptr()], n_tgt, nnz, n_lev, src_pitch, out_pitch, P, tgt_rows is not None, _gather["tile"])  # noqa: E731
+    launch = decide(P)
+    if launch is None:
+        launch = decide(None)
+        launch.epilogue = "split"
+    _gather["route"] = launch.name()
+
+
 def regrid_ell(src, out, idx, w, *, n_src, n_tgt, k, n_lev, src_pitch, out_pitch, layout, prog=None, n_stage=0, tgt_mask=None,
-               padded=False, tgt_rows=None):
+               padded=False, tgt_rows=None, _named=False):
+    if not _named:
+        _name_ell_route([src], [out], w, n_tgt, k, n_lev, src_pitch, out_pitch, layout, prog, n_stage, tgt_mask, padded, tgt_rows)
     x = _levels(src, n_src, n_lev, layout)
     y = _levels(out, n_tgt, n_lev, layout)
     index = idx.numpy().reshape(n_tgt, k)
@@ -102,12 +165,15 @@ def bind_regrid_ell(src, out, idx, w, *, stream=None, **kw):
 
 
 def regrid_ell_batch(srcs, outs, idx, w, **kw):
+    _name_ell_route(srcs, outs, w, kw["n_tgt"], kw["k"], kw["n_lev"], kw["src_pitch"], kw["out_pitch"], kw["layout"], kw.get("prog"), kw.get("n_stage", 0),
+                    kw.get("tgt_mask"), kw.get("padded", False), kw.get("tgt_rows"))
     for src, out in zip(srcs, outs):
-        regrid_ell(src, out, idx, w, **kw)
+        regrid_ell(src, out, idx, w, _named=True, **kw)
 
 
 def regrid_csr(src, out, indptr, indices, data, *, n_src, n_tgt, nnz, n_lev, src_pitch, out_pitch, layout, prog=None,
                n_stage=0, tgt_mask=None, tgt_rows=None):
+    _name_csr_route(src, out, n_tgt, nnz, n_lev, src_pitch, out_pitch, layout, prog, n_stage, tgt_rows)
     x = _levels(src, n_src, n_lev, layout)
     y = _levels(out, n_tgt, n_lev, layout)
     rows = None if tgt_rows is None else tgt_rows.numpy()[:n_tgt]
@@ -313,7 +379,7 @@ def cutout_inside(global_xyz, lam_xyz, neighbours):
     return torch.from_numpy(inside)
 
 
-PATCHED = ["KnnIndex", "cutout_inside", "regrid_ell", "bind_regrid_ell", "regrid_ell_batch", "regrid_csr", "check_indices", "pointwise_stack", "last_route", "combine_stack", "mask_build", "mask_count", "mask_to_index",
+PATCHED = ["KnnIndex", "cutout_inside", "regrid_ell", "bind_regrid_ell", "regrid_ell_batch", "regrid_csr", "check_indices", "pointwise_stack", "last_route", "last_gather_route", "set_tuning", "combine_stack", "mask_build", "mask_count", "mask_to_index",
            "reduce", "relayout", "reduce_stack", "select_levels"]
 
 

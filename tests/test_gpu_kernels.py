@@ -209,9 +209,19 @@ def test_regrid_fused_epilogue(dev):
 @pytest.mark.parametrize("program", ["uniform", "per_vector", "three_pieces", "mixed_madd", "mixed_vectors", "two_pieces_general", "masked",
                                      "masked_uniform", "masked_3_stages", "scale_per_level"])
 def test_fused_epilogue_kernel_variants_agree(dev, tdtype, np_dtype, k, padded, program):
-    """The epilogue reaches the gather by three routes — operators by value in the kernel arguments (uniform programs seen
-    through host_prog), the host-built per-vector table (vec_prog), the tiled kernel's LDS table (neither companion) — and
-    all three must give the bits of the oracle's chain `csr @ x` then the per-level statements."""
+    """The epilogue reaches the gather by four routes — on the direct kernel the operators by value (a uniform program or up to four runs
+    of levels, both seen through host_prog) or the host-built per-vector table (multiply-add programs: host_prog AND vec_prog), else the
+    tiled kernel's LDS tables — and every one must give the bits of the oracle's chain `csr @ x` then the per-level statements.
+    Three runs, each asserted to take the route it is here for (`native.last_gather_route()`): the program with its companions (the
+    direct kernel wherever the program is eligible), without vec_prog (the table programs fall to the tiled kernel, the by-value ones
+    stay), without either (the tiled kernel).  A run without host_prog alone used to stand for the table: the dispatcher cannot see a
+    program without host_prog, so that run took the tiled kernel and repeated the third; the table is what the full run of
+    `mixed_madd`, `scale_per_level` and `masked_3_stages` takes, which is now asserted.  The bar is that of
+    tests/gather_route_checks.py: arithmetic levels bit for bit in float32 as in float64, log levels within the budget of
+    tests/ulp_budgets.py."""
+    import gather_route_checks as G
+    from level_program_checks import compare_levels, reference
+
     rng = np.random.default_rng(31)
     n_src, n_tgt, n_lev = 3000, 2111, 21  # 21 levels: a ragged last vector for both dtypes
     x = make_fields(rng, n_lev, n_src, np_dtype)
@@ -222,33 +232,42 @@ def test_fused_epilogue_kernel_variants_agree(dev, tdtype, np_dtype, k, padded, 
         idx = np.where(drop, -1, idx).astype(np.int32)
         w = np.where(drop, 0.0, w).astype(np_dtype)
     mul, aff, cp = (native.OP_MUL, 0, oracle.G, 0.0), (native.OP_AFFINE, 0, 1.0, -273.15), (native.OP_COPY, 0, 0.0, 0.0)
-    if program == "uniform":  # every level the same two operators: eligible for the by-value kernel
-        stages = [[mul] * n_lev, [aff] * n_lev]
-    elif program == "per_vector":  # operators change at vector boundaries of BOTH dtypes (multiples of 4 levels)
-        stages = [[mul if l < 8 else cp for l in range(n_lev)], [aff if l >= 12 else cp for l in range(n_lev)]]
-    elif program == "three_pieces":  # three runs of levels: beyond the two pieces that travel by value -> per-vector table
-        stages = [[mul if l < 4 else (cp if l < 12 else aff) for l in range(n_lev)]]
+    # program -> its stages and the epilogue that serves it when both companions are there
+    if program == "uniform":  # every level the same two operators: by value
+        stages, served = [[mul] * n_lev, [aff] * n_lev], "uniform"
+    elif program == "per_vector":  # per stage two pieces, the change on a vector boundary of BOTH dtypes (multiples of 4 levels): by value
+        stages, served = [[mul if l < 8 else cp for l in range(n_lev)], [aff if l >= 12 else cp for l in range(n_lev)]], "uniform"
+    elif program == "three_pieces":  # three runs of levels: beyond the two pieces of a uniform stage, within the four runs that travel by value
+        stages, served = [[mul if l < 4 else (cp if l < 12 else aff) for l in range(n_lev)]], "runs"
     elif program == "two_pieces_general":  # two pieces, operators outside the multiply-add family (by value: both evaluated, one kept)
         stages = [[(native.OP_CLIP, 0, 250.0, 300.0) if l < 16 else (native.OP_AFFINE_INV, 0, 2.0, 1.0) for l in range(n_lev)],
                   [(native.OP_LOG, 0, 0.0, 0.0) if l < 4 else (native.OP_DIV, 0, 3.0, 0.0) for l in range(n_lev)]]
+        served = "uniform"
     elif program == "masked_uniform":  # convert everywhere, then apply_mask everywhere: by value, with the mask
-        stages = [[aff] * n_lev, [(native.OP_COPY, 1, 0.0, 0.0)] * n_lev]
-    elif program == "mixed_madd":  # operators differ inside a vector, all of the multiply-add family (direct kernel, per-level path)
-        stages = [[mul if l % 3 == 0 else cp for l in range(n_lev)], [aff if l % 2 else cp for l in range(n_lev)]]
+        stages, served = [[aff] * n_lev, [(native.OP_COPY, 1, 0.0, 0.0)] * n_lev], "uniform"
+    elif program == "mixed_madd":  # operators differ inside a vector, all of the multiply-add family: the per-vector table, level by level in a mixed vector
+        stages, served = [[mul if l % 3 == 0 else cp for l in range(n_lev)], [aff if l % 2 else cp for l in range(n_lev)]], "table"
     elif program == "scale_per_level":  # normalisation per level: every level its own parameters (the typed per-level part of vec_prog)
         stages = [[(native.OP_MUL, 0, 1.0 + 0.01 * l, 0.0) for l in range(n_lev)], [(native.OP_AFFINE, 0, 1.0 / (1 + l), -0.37 * l) for l in range(n_lev)]]
+        served = "table"
     elif program == "masked_3_stages":  # BASELINE config 5 with apply_mask: orog_to_z on one level, convert on the others, mask on some
         stages = [[cp] * (n_lev - 1) + [mul], [aff] * (n_lev - 1) + [cp], [(native.OP_COPY, 1 if l % 5 else 0, 0.0, 0.0) for l in range(n_lev)]]
+        served = "table"
     elif program == "mixed_vectors":  # operators differ inside a vector, general operators (tiled kernel)
-        stages = [[mul if l % 3 == 0 else cp for l in range(n_lev)], [aff if l % 2 else (native.OP_CLIP, 0, 250.0, 300.0) for l in range(n_lev)]]
-    else:
-        stages = [[(native.OP_AFFINE, 1 if l in (2, 20) else 0, 2.0, 1.0) for l in range(n_lev)]]
+        stages, served = [[mul if l % 3 == 0 else cp for l in range(n_lev)], [aff if l % 2 else (native.OP_CLIP, 0, 250.0, 300.0) for l in range(n_lev)]], "lds"
+    else:  # the mask on two levels: four runs
+        stages, served = [[(native.OP_AFFINE, 1 if l in (2, 20) else 0, 2.0, 1.0) for l in range(n_lev)]], "runs"
     tmask = rng.random(n_tgt) < 0.3
     tmask_d = to_dev(tmask.astype(np.uint8), dev) if program.startswith("masked") else None
     src = Stack.from_fields(x, dev=dev)
-    idx_d, w_d = to_dev(idx, dev), (to_dev(w, dev) if (k > 1 or padded) else None)
+    weighted = k > 1 or padded
+    idx_d, w_d = to_dev(idx, dev), (to_dev(w, dev) if weighted else None)
 
-    def run(strip):
+    def route(epilogue):
+        name = G.tiled if epilogue == "lds" else G.direct
+        return name(epilogue, k, padded=padded, weighted=weighted)
+
+    def run(strip, epilogue):
         prog = native.level_program(stages, dev)
         for name in strip:
             if name == "vec_prog":
@@ -258,32 +277,24 @@ def test_fused_epilogue_kernel_variants_agree(dev, tdtype, np_dtype, k, padded, 
         out = src.new_like(n_pts=n_tgt)
         native.regrid_ell(src.data, out.data, idx_d, w_d, n_src=n_src, n_tgt=n_tgt, k=k, n_lev=n_lev, src_pitch=src.pitch,
                           out_pitch=out.pitch, layout=COLUMNS, prog=prog, n_stage=len(stages), tgt_mask=tmask_d, padded=padded)
+        assert native.last_gather_route() == route(epilogue), (strip, native.last_gather_route(), route(epilogue))
         return out.numpy()
 
-    full, table_only, tiled = run(()), run(("host_prog",)), run(("host_prog", "vec_prog"))
+    full, by_value_only, tiled = run((), served), run(("vec_prog",), "lds" if served == "table" else served), run(("host_prog", "vec_prog"), "lds")
     # oracle chain
-    if k == 1 and not padded:
-        want = np.stack([oracle.gather_nn(f, idx[:, 0]) for f in x])
+    if not weighted:
+        gathered = np.stack([oracle.gather_nn(f, idx[:, 0]) for f in x])
     else:
         present = idx >= 0
         lengths = present.sum(axis=1)
         indptr = np.concatenate([[0], np.cumsum(lengths)])
-        want = np.stack([oracle.csr_apply(w[present], idx[present], indptr, (n_tgt, n_src), f) for f in x])
-    table = native.LEVEL_OP_DTYPE
-    for stage in stages:
-        for l, (op, use_mask, p0, p1) in enumerate(stage):
-            entry = np.zeros((), dtype=table)
-            entry["op"], entry["use_mask"], entry["p0"], entry["p1"] = op, use_mask, p0, p1
-            import native_double
-
-            want[l] = native_double._apply_op(entry, want[l], tmask if use_mask else None)
-    libm = any(op in (native.OP_LOG, native.OP_EXP) for stage in stages for (op, _, _, _) in stage)  # ocml vs libm: a few ulp
-    for got in (full, table_only, tiled):
-        if (np_dtype == np.float64 or (k == 1 and not padded)) and not libm:
-            assert np.array_equal(got, want, equal_nan=True)
-        else:
-            np.testing.assert_allclose(got, want, rtol=RTOL_F32 if np_dtype == np.float32 else 1e-14, atol=1e-4, equal_nan=True)
-    assert np.array_equal(full, tiled, equal_nan=True) and np.array_equal(table_only, tiled, equal_nan=True)  # same arithmetic, same bits
+        gathered = np.stack([oracle.csr_apply(w[present], idx[present], indptr, (n_tgt, n_src), f) for f in x])
+    chain = tuple(tuple(stage) for stage in stages)
+    want, args = reference(gathered, chain, tmask if tmask_d is not None else None)
+    bits = np.uint32 if np_dtype == np.float32 else np.uint64
+    for got, what in ((full, "with both companions"), (by_value_only, "without vec_prog"), (tiled, "without companions")):
+        compare_levels(np_dtype, chain, got.view(bits), gathered, want, args, f"{program} k={k} {what}", copies_are_bit_copies=not weighted)
+    assert np.array_equal(full.view(bits), tiled.view(bits)) and np.array_equal(by_value_only.view(bits), tiled.view(bits))  # same arithmetic, same bits
 
 
 @pytest.mark.parametrize("tdtype,np_dtype", DTYPES)

@@ -2,10 +2,10 @@
 
 Seeded, so every run draws the same cases: odd sizes around the vector width, the tile sizes and the workgroup size;
 loose pitches (padding poisoned with NaN, which must neither be read into a result nor overwritten); both layouts, both
-dtypes; fixed-k, padded ragged and general CSR operators; epilogue programs with point masks; batches.  Float64
-results must equal numpy / scipy bit for bit, float32 gathers within the 1e-6 relative tolerance of BASELINE.json; the
-per-point programs (no exp / log here) equal numpy's float32 statements bit for bit as well — a failure names the launch
-form (``native.last_route()``); tests/test_gpu_pointwise_routes.py holds each form deterministically.
+dtypes; fixed-k, padded ragged and general CSR operators; epilogue programs with point masks; batches.  Results must equal
+numpy / scipy bit for bit in float32 as in float64: the gathers scipy's csr_matvec in the stack's own width, the fused and the
+per-point programs (no exp / log here) numpy's statements — a failure names the launch form (``native.last_gather_route()``,
+``native.last_route()``); tests/test_gpu_gather_routes.py and tests/test_gpu_pointwise_routes.py hold each form deterministically.
 """
 
 from __future__ import annotations
@@ -123,15 +123,11 @@ def apply_program_host(levels: np.ndarray, ops, mask: np.ndarray | None) -> np.n
     return out
 
 
-def check(got: np.ndarray, want: np.ndarray, what: str, exact: bool = False):
-    if exact:  # bit for bit: NaN where numpy has one, everywhere else numpy's bit pattern (the sign of a zero included)
-        bits = np.uint32 if got.dtype == np.float32 else np.uint64
-        nan = np.isnan(want)
-        assert got.dtype == want.dtype and np.array_equal(np.isnan(got), nan) and np.array_equal(got.view(bits)[~nan], want.view(bits)[~nan]), what
-    elif got.dtype == np.float64:
-        assert np.array_equal(got, want, equal_nan=True), what
-    else:
-        np.testing.assert_allclose(got, want, rtol=1e-6, atol=1e-4, err_msg=what)
+def check(got: np.ndarray, want: np.ndarray, what: str):
+    """Bit for bit, in float32 as in float64: a NaN where numpy has one, everywhere else numpy's bit pattern (the sign of a zero included)."""
+    bits = np.uint32 if got.dtype == np.float32 else np.uint64
+    nan = np.isnan(want)
+    assert got.dtype == want.dtype and np.array_equal(np.isnan(got), nan) and np.array_equal(got.view(bits)[~nan], want.view(bits)[~nan]), what
 
 
 @pytest.mark.parametrize("seed", REGRID_SEEDS)
@@ -198,7 +194,9 @@ def test_random_regrid_cases(dev, seed):
         if with_prog:
             want = apply_program_host(want.astype(np_dtype), ops, mask_host)
         native.set_tuning(0)
-        check(out.values(), want.astype(np_dtype), what)
+        # float32 as float64: scipy's csr_matvec and numpy's statements in the stack's own width, bit for bit (tests/gather_route_checks.py
+        # holds every launch form to that deterministically)
+        check(out.values(), want.astype(np_dtype), what + f" (route {native.last_gather_route()})")
         assert out.padding_untouched(), what + " (padding of the output written)"
 
 
@@ -226,10 +224,10 @@ def test_random_pointwise_and_level_gather_cases(dev, seed):
         kw = dict(n_pts=n_pts, n_lev=n_lev, layout=layout, prog=prog, n_stage=len(ops), point_mask=mask_dev)
         native.pointwise_stack(src.data, dst.data, x_pitch=src.pitch, y_pitch=dst.pitch, **kw)
         want = apply_program_host(x, ops, mask_host)
-        check(dst.values(), want, what + f" out of place (route {native.last_route()})", exact=True)
+        check(dst.values(), want, what + f" out of place (route {native.last_route()})")
         assert dst.padding_untouched() and np.array_equal(src.values(), x, equal_nan=True), what
         native.pointwise_stack(src.data, src.data, x_pitch=src.pitch, y_pitch=src.pitch, **kw)
-        check(src.values(), want, what + f" in place (route {native.last_route()})", exact=True)
+        check(src.values(), want, what + f" in place (route {native.last_route()})")
         assert src.padding_untouched(), what
         # level gather
         n_out = int(rng.integers(1, n_lev + 3))

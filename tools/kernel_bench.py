@@ -602,7 +602,7 @@ def main():
         finish()
 
     if args.only_combine:
-        libs = {name: native.open_library(os.path.abspath(path)) for name, path in (spec.split("=", 1) for spec in args.lib)}
+        libs = {name: native.open_library(os.path.abspath(path), older_build=True) for name, path in (spec.split("=", 1) for spec in args.lib)}
         for tdt, B, tag in ((torch.float32, 4, "f32"), (torch.float64, 8, "f64")):
             combine_rows(tdt, B, tag, bench.synth_stack(src_grid, L, tdt, dev, 0, COLUMNS), libs, args.rounds)
             torch.cuda.empty_cache()
@@ -611,7 +611,7 @@ def main():
         return
 
     if args.only_regrid:
-        libs = {name: native.open_library(os.path.abspath(path)) for name, path in (spec.split("=", 1) for spec in args.lib)}
+        libs = {name: native.open_library(os.path.abspath(path), older_build=True) for name, path in (spec.split("=", 1) for spec in args.lib)}
         idx, w = interp.knn_inverse_distance(src_grid, tgt_grid, k=4)
         for tdt, B, tag in ((torch.float32, 4, "f32"), (torch.float64, 8, "f64")):
             regrid_rows(tdt, B, tag, bench.synth_stack(src_grid, L, tdt, dev, 0, COLUMNS), idx, w, libs, args.rounds)
