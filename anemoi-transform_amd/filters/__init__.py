@@ -14,6 +14,7 @@ Registered names:
                   add_forcings, add_azimuth, add_msg_angles, radiance_to_brightness_temperature, add_healpix,
                   fill_orography, geopotential_to_height_tabular, apply_column_transformations
                                                              (per-row columns, filters/tabular.py)
+                  sort_by, drop_duplicates, drop             (row sets on the device / column bookkeeping, filters/tabular.py)
                   rename_fields, clear_step, repeat_members, earthkitfieldlambda, empty,
                   icon_refinement_level   (re-labelling / re-listing, filters/metadata.py)
   dispatchers     mask (alias apply_mask), remove_nans (alias drop_nans),
@@ -28,9 +29,11 @@ calls ``geopotential_to_height_tabular`` with its ``geopotential`` and ``height`
 keys (``height`` defaults to ``"orog"`` there, as in the reference).
 Observations enter the field path through ``irregular_to_grid`` (with
 ``assign_to_grid`` before it): a table goes to the device once and comes out as
-one HBM stack of gridded fields.  The rest of the reference's tabular family is
-row-dropping, renaming and masking bookkeeping in pandas with no field output
-and stays out.
+one HBM stack of gridded fields.  ``sort_by`` and ``drop_duplicates`` reorder and
+thin a table by pandas' order and equality on the device, ``drop`` removes columns,
+so a chain that needs them stays a mapping of device tensors.  The rest of the
+reference's tabular family is row-dropping, renaming and masking bookkeeping in
+pandas with no field output and stays out.
 """
 
 from __future__ import annotations

@@ -22,6 +22,11 @@ by 9.80665 (numpy for host columns, torch true division for device tensors: one 
 ``cos_deg`` over whole columns, in config order and chained: up to 16 of them are one launch (``obs.column_ops`` ->
 ``atx_obs_column_ops``), and a transformation that reads an earlier one's target takes it from a register.
 
+The row-set filters keep such a chain resident where it reorders or thins the table: ``sort_by`` (a stable multi-key sort by pandas'
+order: ``obs.sort_order`` -> ``atx_obs_order_key`` and the library's stable radix sort), ``drop_duplicates`` (the first row of every
+group of equal key tuples: ``obs.first_rows`` -> ``atx_obs_mark_first``) — both end in ONE gather of every column
+(``obs.take_rows`` -> ``atx_obs_take_rows``) — and ``drop`` (columns leave; host bookkeeping, nothing is copied).
+
 A table is a pandas DataFrame (when pandas can be imported) or a plain mapping ``name -> 1-D array / device tensor``.
 
 Deviations from the reference, each said once when it first matters (``core.say_once``):
@@ -45,8 +50,11 @@ Deviations from the reference, each said once when it first matters (``core.say_
   * ``apply_column_transformations``: float32 and float16 columns are read as float64 and the result is float64 (numpy would stay in
     float32); a ``source_column`` list of more than one name raises ``NotImplementedError``; numpy's ``RuntimeWarning``s are not
     reproduced.
-The other tabular filters of the reference (row-dropping, renaming and masking bookkeeping in pandas, with no arithmetic for the
-device to do) are not built: DESIGN.md §7.
+  * ``sort_by``: a key column that cannot be ordered raises ``ValueError`` (the reference logs the error and returns the frame
+    UNSORTED); an int64 device tensor named ``date`` is nanoseconds with NaT, as everywhere in this module.
+  * ``sort_by`` / ``drop_duplicates``: a uint64 key column raises ``ValueError`` (it has no int64 key); the caller's table is not modified.
+The other tabular filters of the reference (the remaining row-dropping, renaming and masking bookkeeping in pandas) are not built:
+DESIGN.md §7.
 """
 
 from __future__ import annotations
@@ -827,6 +835,130 @@ class ApplyColumnTransformations(Filter):
         return _with_columns(table, added, any(isinstance(table[c], torch.Tensor) for c in names))
 
 
+# ---- row sets: sort_by, drop_duplicates, drop ------------------------------------------------------------------------------------------
+def _table_rows(table: Any) -> int:
+    names = _column_names(table)
+    return len(table) if _is_dataframe(table) else (len(table[names[0]]) if names else 0)
+
+
+def _key_columns(table: Any, names: list[str]) -> tuple[list[Any], list[bool]]:
+    """The key columns ``names`` of the table and, per column, whether it is int64 nanoseconds: a device tensor named ``date``
+    (``obs.to_ns``: an int64 tensor in the date column IS nanoseconds; a datetime64 array says so itself)."""
+    columns = [table[name] for name in names]
+    return columns, [name == "date" and isinstance(c, torch.Tensor) and c.dtype == torch.int64 for name, c in zip(names, columns)]
+
+
+def _take_table(table: Any, rows: torch.Tensor) -> Any:
+    """The rows of the table at the device positions ``rows``, in the kind of the input and never the caller's object: ``iloc`` for a
+    DataFrame (index labels and dtypes are pandas' own); for a mapping a new dict — device tensors through ``obs.take_rows`` if any
+    column was a device tensor (a non-numeric host column cannot live there and stays a host array), else numpy arrays."""
+    if _is_dataframe(table):
+        return table.iloc[rows.cpu().numpy()]
+    names = _column_names(table)
+    resident, dev = _table_device(table)
+    host = None
+    taken: dict[str, Any] = {}
+    if resident:
+        numeric = {name: table[name] for name in names
+                   if isinstance(table[name], torch.Tensor) or getattr(obs._host_array(table[name]).dtype, "kind", "O") in "iufbcMm"}
+        taken = obs.take_rows(numeric, rows, dev=dev)
+    for name in names:
+        if name not in taken:
+            host = rows.cpu().numpy() if host is None else host
+            taken[name] = np.asarray(obs._host_array(table[name]))[host]
+    return {name: taken[name] for name in names}
+
+
+class SortBy(Filter):
+    """Sorts the rows of a table by the columns in ``columns`` (R: filters/tabular/sort_by.py:21-63: ``df.sort_values(by=columns,
+    kind="stable")``): ascending by the key tuple, the first column most significant, missing values (NaN, NaT) of a key last, rows of
+    equal tuples in table order.  The order is pandas', not IEEE's: ``-0.0`` and ``0.0`` tie, int64 keys compare as integers.  The
+    permutation is computed on the device (``obs.sort_order``: ``atx_obs_order_key`` per column, one stable radix sort per key) and
+    applied in one gather of all columns (``obs.take_rows`` -> ``atx_obs_take_rows``); a DataFrame is ``table.iloc[rows]``, so its index
+    labels travel with the rows as in the reference.  A missing column raises ``ValueError``.
+
+    Deviations: a key column that cannot be ordered (a uint64 column, objects without an order) raises ``ValueError`` — the reference
+    logs the error and returns the frame unsorted; the caller's table is not modified."""
+
+    def __init__(self, *, columns: list[str]) -> None:
+        self.columns = [columns] if isinstance(columns, str) else list(columns)
+        say_once(LOG, (type(self), "deviations"), "sort_by: a key column that cannot be ordered raises ValueError (the reference logs "
+                 "the error and returns the table unsorted)", level=logging.INFO)
+
+    def __repr__(self) -> str:
+        return f"SortBy({self.columns})"
+
+    def forward(self, table: Any) -> Any:
+        _require(table, self.columns)
+        if _table_rows(table) == 0 or not self.columns:
+            return table.copy() if _is_dataframe(table) else dict(table)
+        columns, datetimes = _key_columns(table, self.columns)
+        _, dev = _table_device(table)
+        return _take_table(table, obs.sort_order(columns, dev, datetimes=datetimes))
+
+
+class DropDuplicates(Filter):
+    """Keeps the first row, in table order, of every set of rows that are equal in a subset of the columns
+    (R: filters/tabular/drop_duplicates.py:18-62: ``df.drop_duplicates(subset)``).  The subset is ``columns``, or every column whose name
+    starts with ``column_prefix``, or — with neither — all columns; both at once raise ``ValueError`` at construction, a prefix that
+    matches nothing and a missing column raise it at ``forward``.  Equality is pandas': ``-0.0`` equals ``0.0``, every NaN equals every
+    NaN (NaT likewise), int64 compares as integers.  The rows are found on the device (``obs.first_rows``: keys, a stable sort,
+    ``atx_obs_mark_first``) and taken in one gather of all columns (``obs.take_rows``); a DataFrame is ``table.iloc[rows]``.
+
+    Deviations: a uint64 key column raises ``ValueError``; the caller's table is not modified."""
+
+    def __init__(self, *, columns: list[str] | None = None, column_prefix: str | None = None) -> None:
+        if bool(columns) and bool(column_prefix):
+            raise ValueError("Either columns or column_prefix may be specified, but not both.")
+        self.columns = [columns] if isinstance(columns, str) else columns
+        self.column_prefix = column_prefix
+
+    def __repr__(self) -> str:
+        return f"DropDuplicates({self.columns if self.columns else (self.column_prefix + '*' if self.column_prefix else 'all columns')})"
+
+    def forward(self, table: Any) -> Any:
+        names = _column_names(table)
+        if self.columns:
+            subset = list(self.columns)
+            _require(table, subset)
+        elif self.column_prefix:
+            subset = [c for c in names if isinstance(c, str) and c.startswith(self.column_prefix)]
+            if not subset:
+                raise ValueError(f"No columns starting with '{self.column_prefix}' found in DataFrame.")
+        else:
+            subset = names
+        if _table_rows(table) == 0 or not subset:
+            return table.copy() if _is_dataframe(table) else dict(table)
+        columns, datetimes = _key_columns(table, subset)
+        _, dev = _table_device(table)
+        return _take_table(table, obs.first_rows(columns, dev, datetimes=datetimes))
+
+
+class Drop(Filter):
+    """Removes the columns in ``columns`` from a table (R: filters/tabular/drop.py:18-48: ``df.drop(labels=columns, axis=1)``).  No
+    columns raise ``ValueError`` at construction, a missing one at ``forward``.  Host bookkeeping: a DataFrame goes through pandas, a
+    mapping gives a new dict without the names — the remaining columns are the caller's own objects, device tensors included; nothing
+    is copied."""
+
+    def __init__(self, *, columns: list[str]) -> None:
+        if not columns:
+            raise ValueError("No columns to drop were specified.")
+        self.columns = [columns] if isinstance(columns, str) else list(columns)
+
+    def __repr__(self) -> str:
+        return f"Drop({self.columns})"
+
+    def forward(self, table: Any) -> Any:
+        _require(table, self.columns)
+        if _is_dataframe(table):
+            return table.drop(labels=self.columns, axis=1)
+        gone = set(self.columns)
+        return {name: table[name] for name in _column_names(table) if name not in gone}
+
+
+filter_registry.register("sort_by", SortBy)
+filter_registry.register("drop_duplicates", DropDuplicates)
+filter_registry.register("drop", Drop)
 filter_registry.register("apply_column_transformations", ApplyColumnTransformations)
 filter_registry.register("fill_orography", FillHeights)
 filter_registry.register("geopotential_to_height_tabular", GeopotentialToHeightTabular)

@@ -125,6 +125,11 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
          c_void_p, c_void_p, c_void_p],
     ),
     "atx_obs_column_ops": (c_int, [c_int32, POINTER(c_int32), POINTER(c_int32), POINTER(c_void_p), POINTER(c_void_p), c_int64, c_void_p]),
+    "atx_obs_order_key": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p]),
+    "atx_obs_mark_first": (c_int, [c_int32, POINTER(c_void_p), c_void_p, c_int64, c_int, c_void_p, c_void_p]),
+    "atx_obs_take_rows": (
+        c_int, [c_int32, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_int32), c_void_p, c_int64, c_int64, c_void_p, c_void_p],
+    ),
     "atx_mask_build": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_double, c_int, c_void_p]),
     "atx_mask_count": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
     "atx_mask_to_index_workspace": (c_size_t, [c_int64]),
@@ -642,6 +647,57 @@ def obs_column_ops(ops, n: int) -> None:
     ins = (c_void_p * k)(*[_ptr(o[2]) if o[1] < 0 else None for o in ops])
     outs = (c_void_p * k)(*[_ptr(o[3]) for o in ops])
     _call("atx_obs_column_ops", k, codes, srcs, ins, outs, n, _stream())
+
+
+MAX_ROWSET_COLUMNS = 16
+# atx_key_dtype by torch dtype; KEY_DATETIME is int64 nanoseconds with NaT = INT64_MIN and has to be asked for
+KEY_F64, KEY_F32, KEY_I64, KEY_I32, KEY_I16, KEY_I8, KEY_U8, KEY_BOOL, KEY_DATETIME = range(9)
+KEY_DTYPES = {torch.float64: KEY_F64, torch.float32: KEY_F32, torch.int64: KEY_I64, torch.int32: KEY_I32, torch.int16: KEY_I16,
+              torch.int8: KEY_I8, torch.uint8: KEY_U8, torch.bool: KEY_BOOL}
+
+
+def obs_order_key(column, key, code: int | None = None) -> None:
+    """``key[i]`` (int64 ``[n]``): the order key of ``column[i]`` by pandas' rule — ``-0.0`` and ``0.0`` one key, every NaN / NaT one
+    key and the last, integers as integers — ``atx_obs_order_key``.  ``code``: a ``KEY_*`` value, by default the one of the column's
+    dtype (``KEY_DTYPES``); ``KEY_DATETIME`` for int64 nanoseconds.  Does not synchronise."""
+    if code is None:
+        if column.dtype not in KEY_DTYPES:
+            raise ValueError(f"no order key for a {column.dtype} column (float64, float32, int64, int32, int16, int8, uint8, bool)")
+        code = KEY_DTYPES[column.dtype]
+    n = key.numel()
+    assert column.is_contiguous() and column.numel() == n and key.dtype == torch.int64 and key.is_contiguous()
+    assert code != KEY_DATETIME or column.dtype == torch.int64
+    _call("atx_obs_order_key", _ptr(column), n, int(code), _ptr(key), _stream())
+
+
+def obs_mark_first(keys, order, keep, accumulate: bool = False) -> None:
+    """``keep[order[i]] = (i == 0) or any(key[order[i]] != key[order[i - 1]] for key in keys)`` for 1 .. ``MAX_ROWSET_COLUMNS`` int64
+    key rows — ``atx_obs_mark_first``.  ``order``: int64 ``[n]``, a permutation; ``keep``: uint8 ``[n]``, written (``accumulate``: only
+    ever set).  Does not synchronise."""
+    n = keep.numel()
+    for t in (*keys, order):
+        assert t.dtype == torch.int64 and t.is_contiguous() and t.numel() == n
+    assert keep.dtype == torch.uint8 and keep.is_contiguous()
+    k = len(keys)
+    table = (c_void_p * max(k, 1))(*[_ptr(t) for t in keys])
+    _call("atx_obs_mark_first", k, table, _ptr(order), n, 1 if accumulate else 0, _ptr(keep), _stream())
+
+
+def obs_take_rows(columns, outs, rows, n_bad) -> None:
+    """``outs[c][i] = columns[c][rows[i]]`` for 1 .. ``MAX_ROWSET_COLUMNS`` device rows of 1, 2, 4 or 8 bytes per element, any mix —
+    ``atx_obs_take_rows``.  ``rows``: int64 ``[n_out]``; a row index outside the table writes nothing and is counted in ``n_bad`` (int64
+    ``[1]`` on the device, set by the call when ``n_out > 0``).  Does not synchronise."""
+    n_out = rows.numel()
+    n_in = columns[0].numel() if columns else 0
+    assert rows.dtype == torch.int64 and rows.is_contiguous() and n_bad.dtype == torch.int64 and n_bad.numel() == 1
+    for c, o in zip(columns, outs):
+        assert c.is_contiguous() and o.is_contiguous() and c.numel() == n_in and o.numel() == n_out and c.dtype == o.dtype
+    k = len(columns)
+    assert len(outs) == k
+    ins = (c_void_p * max(k, 1))(*[_ptr(c) for c in columns])
+    dst = (c_void_p * max(k, 1))(*[_ptr(o) for o in outs])
+    width = (c_int32 * max(k, 1))(*[c.element_size() for c in columns])
+    _call("atx_obs_take_rows", k, ins, dst, width, _ptr(rows), n_out, n_in, _ptr(n_bad), _stream())
 
 
 def mask_build(m, mask, *, n, stride=1, cmp, threshold=0.0) -> None:

@@ -28,6 +28,11 @@ launch (``atx_obs_fill_heights``); rows with two equally near axis entries go ba
 The fifth is ``apply_column_transformations`` (R: filters/tabular/apply_column_transformations.py): ``compile_column_program`` turns
 the ordered list of (target, source, function) into runs of at most 16 operations, and ``column_ops`` launches each run once
 (``atx_obs_column_ops``): a transformation that reads an earlier one's target takes it from a register, not from memory.
+
+The sixth is the row sets of ``sort_by`` and ``drop_duplicates`` (R: filters/tabular/sort_by.py, drop_duplicates.py): ``order_keys``
+turns a column into int64 keys that order and compare as pandas does (``atx_obs_order_key``), ``sort_order`` is the stable multi-key
+permutation (the library's stable radix sort, one pass per key), ``first_rows`` the first row of every group of equal key tuples
+(``atx_obs_mark_first``), and ``take_rows`` gathers every column of a table by one row list (``atx_obs_take_rows``).
 """
 
 from __future__ import annotations
@@ -739,3 +744,176 @@ def column_ops(columns: Mapping[str, Any], spec: Sequence[tuple[str, str, str]],
             current[name] = col
             as_float.pop(name, None)
     return {target: current[target] for target in dict.fromkeys(t for t, _, _ in spec)}
+
+
+# ---- row sets: pandas' order and equality on the device (R: filters/tabular/sort_by.py, drop_duplicates.py) --------------------------
+def _host_ranks(column: Any) -> np.ndarray:
+    """A non-numeric host column (strings, categoricals, objects) as int64 ranks: equal entries get equal ranks, the ranks ascend as
+    pandas orders the entries, and every missing entry (None, NaN, NaT) gets ONE rank above all others — missing last, and equal to
+    each other, as ``sort_values`` and ``drop_duplicates`` have it.  A categorical ranks by its categories' order, as pandas sorts it.
+    Entries that cannot be ordered (a column mixing strings and numbers) raise ``ValueError``."""
+    if hasattr(column, "cat"):
+        codes = np.asarray(column.cat.codes, dtype=np.int64)
+        return np.where(codes < 0, len(column.cat.categories), codes)
+    a = _host_array(column).reshape(-1)
+    try:
+        try:
+            import pandas as pd
+
+            codes, uniques = pd.factorize(a, sort=True)
+            codes, n_unique = np.asarray(codes, dtype=np.int64), len(uniques)
+            sorted(np.asarray(uniques, dtype=object).tolist())  # factorize puts numbers before strings; sort_values refuses the mix
+        except ImportError:
+            ok = np.array([not (v is None or v != v) for v in a.tolist()], dtype=bool)
+            codes = np.full(a.size, -1, dtype=np.int64)
+            uniques, codes[ok] = np.unique(a[ok], return_inverse=True)
+            n_unique = len(uniques)
+    except TypeError as e:
+        raise ValueError(f"a key column of dtype {a.dtype} holds entries that cannot be ordered: {e}") from None
+    return np.where(codes < 0, n_unique, codes)
+
+
+def order_keys(column: Any, dev: torch.device | None = None, *, datetime: bool = False) -> torch.Tensor:
+    """The int64 device keys of one column by pandas' order and equality (``atx_obs_order_key``): ``key(a) < key(b)`` exactly when
+    ``sort_values`` puts a before b, ``key(a) == key(b)`` exactly when ``drop_duplicates`` takes them for the same value.  ``-0.0`` and
+    ``0.0`` are one key; every NaN and NaT is one key, the largest; int64 compares as integers.  (One date shares NaT's key: INT64_MAX
+    nanoseconds, pandas' ``Timestamp.max``.)
+
+    float64, float32, int64, int32, int16, int8, uint8 and bool columns go to the kernel as they are; float16, uint16 and uint32 are
+    widened exactly first; datetime64 / timedelta64 arrays are int64 nanoseconds with NaT (``datetime=True`` says the same of an int64
+    tensor); uint64 raises ``ValueError`` (it has no int64 key).  Non-numeric columns exist only on the host and are ranked there
+    (``pd.factorize(sort=True)``, missing last); their ranks take the int64 route.  numpy arrays are uploaded, device tensors used in place."""
+    code = None
+    if isinstance(column, torch.Tensor):
+        c = column.reshape(-1)
+        if datetime:
+            if c.dtype != torch.int64:
+                raise ValueError(f"a date tensor must hold int64 nanoseconds, got {c.dtype}")
+            code = native.KEY_DATETIME
+        elif c.dtype in (torch.float16, torch.bfloat16):
+            c = c.to(torch.float32)
+        elif c.dtype in (torch.uint16, torch.uint32):
+            c = c.to(torch.int64)
+        elif c.dtype not in native.KEY_DTYPES:
+            raise ValueError(f"a {c.dtype} column has no int64 order key")
+        dev = c.device if c.is_cuda else (_stack.device() if dev is None else dev)
+        c = c.to(dev).contiguous()
+    else:
+        dev = _stack.device() if dev is None else dev
+        a = None if hasattr(column, "cat") else _host_array(column).reshape(-1)
+        if a is None or a.dtype.kind not in "iufbMm":
+            a = _host_ranks(column)
+        elif a.dtype.kind in "Mm":
+            a = np.ascontiguousarray(a.astype(f"{'datetime64' if a.dtype.kind == 'M' else 'timedelta64'}[ns]")).view(np.int64)
+            code = native.KEY_DATETIME
+        elif a.dtype.kind == "u" and a.dtype.itemsize == 8:
+            raise ValueError("a uint64 column has no int64 order key")
+        elif a.dtype.kind == "u" and a.dtype.itemsize > 1:
+            a = a.astype(np.int64)
+        elif a.dtype.kind == "f" and a.dtype.itemsize == 2:
+            a = a.astype(np.float32)
+        elif a.dtype.kind == "f" and a.dtype.itemsize > 8:
+            raise ValueError(f"a {a.dtype} column has no int64 order key")
+        if datetime and code is None:
+            if a.dtype != np.int64:
+                raise ValueError(f"a date column must hold datetimes or int64 nanoseconds, got {a.dtype}")
+            code = native.KEY_DATETIME
+        c = _device(a.astype(a.dtype.newbyteorder("="), copy=False), dev)
+    key = torch.empty(c.numel(), dtype=torch.int64, device=dev)
+    native.obs_order_key(c, key, code)
+    return key
+
+
+def _row_keys(columns: Sequence[Any], dev: torch.device | None, datetimes: Sequence[bool] | None) -> list[torch.Tensor]:
+    columns = list(columns)
+    if not columns:
+        raise ValueError("at least one key column")
+    if dev is None:
+        dev = next((c.device for c in columns if isinstance(c, torch.Tensor) and c.is_cuda), None) or _stack.device()
+    flags = [False] * len(columns) if datetimes is None else list(datetimes)
+    keys = [order_keys(c, dev, datetime=bool(f)) for c, f in zip(columns, flags)]
+    if len({k.numel() for k in keys}) > 1:
+        raise ValueError(f"key columns differ in length: {[k.numel() for k in keys]}")
+    return keys
+
+
+def _take(columns: Sequence[torch.Tensor], rows: torch.Tensor, check: bool = True) -> list[torch.Tensor]:
+    """``[c[rows] for c in columns]`` for contiguous device rows of equal length: one launch of ``atx_obs_take_rows`` per 16 columns."""
+    columns = list(columns)
+    step = native.MAX_ROWSET_COLUMNS
+    outs = [torch.empty(rows.numel(), dtype=c.dtype, device=rows.device) for c in columns]
+    n_bad = torch.zeros(max((len(columns) + step - 1) // step, 1), dtype=torch.int64, device=rows.device)
+    for j in range(0, len(columns), step):
+        native.obs_take_rows(columns[j:j + step], outs[j:j + step], rows, n_bad[j // step:j // step + 1])
+    if check and columns and rows.numel():
+        bad = int(n_bad[0])  # every launch of the call sees the same rows
+        if bad:
+            raise IndexError(f"take_rows: {bad} of {rows.numel()} row indices lie outside the table's {columns[0].numel()} rows")
+    return outs
+
+
+def _sort_keys(keys: Sequence[torch.Tensor]) -> torch.Tensor:
+    """The stable ascending order of the rows by the tuple of int64 ``keys``, first key most significant: ONE STABLE SORT PER KEY, from
+    the last key to the first (a radix sort by digits; the library's ``torch.sort(stable=True)`` on int64).  Between two sorts the next
+    key is brought into the current order and the order composed with ``atx_obs_take_rows``."""
+    order = None
+    for key in reversed(list(keys)):
+        if order is None:
+            order = torch.sort(key, stable=True).indices
+        else:  # rows already ordered by the later keys: a stable sort by this one keeps that order among its equals
+            (moved,) = _take([key], order, check=False)
+            (order,) = _take([order], torch.sort(moved, stable=True).indices, check=False)
+    return order.contiguous()
+
+
+def sort_order(columns: Sequence[Any], dev: torch.device | None = None, *, datetimes: Sequence[bool] | None = None) -> torch.Tensor:
+    """The int64 device permutation that ``df.sort_values(by=columns, kind="stable")`` applies (R: filters/tabular/sort_by.py:51):
+    rows ascending by the key tuple, the first column most significant, missing values (NaN, NaT) of a key last, rows of equal tuples
+    in table order.  ``columns``: the key columns themselves (see ``order_keys``); ``datetimes[k]`` marks an int64 column as
+    nanoseconds with NaT.  One stable sort per key, from the last to the first (``_sort_keys``) — a folded single key, as
+    ``superob_groups`` builds it, would give the same permutation but needs the ranges of every key first."""
+    return _sort_keys(_row_keys(columns, dev, datetimes))
+
+
+def first_rows(columns: Sequence[Any], dev: torch.device | None = None, *, datetimes: Sequence[bool] | None = None) -> torch.Tensor:
+    """The ascending int64 device row numbers that ``df.drop_duplicates(subset)`` keeps (R: filters/tabular/drop_duplicates.py:61): the
+    first row, in table order, of every set of rows equal in ``columns`` by pandas' equality (``order_keys``).  The rows are sorted
+    stably by the key tuple (``_sort_keys``), ``atx_obs_mark_first`` marks every row whose tuple differs from its predecessor's in
+    that order — 16 keys per launch, further launches accumulating — and the marked rows are listed ascending."""
+    keys = _row_keys(columns, dev, datetimes)
+    n = keys[0].numel()
+    if n == 0:
+        return torch.zeros(0, dtype=torch.int64, device=keys[0].device)
+    order = _sort_keys(keys)
+    keep = torch.empty(n, dtype=torch.uint8, device=order.device)
+    for j in range(0, len(keys), native.MAX_ROWSET_COLUMNS):
+        native.obs_mark_first(keys[j:j + native.MAX_ROWSET_COLUMNS], order, keep, accumulate=j > 0)
+    return torch.nonzero(keep).reshape(-1)
+
+
+def take_rows(columns: Mapping[str, Any], rows: Any, dev: torch.device | None = None) -> dict[str, torch.Tensor]:
+    """``{name: column[rows]}`` as device tensors — one launch of ``atx_obs_take_rows`` per 16 columns, the row list read once per row
+    for all of them.  Dtypes are kept (anything of 1, 2, 4 or 8 bytes per element); datetime64 columns come back as int64
+    nanoseconds.  numpy columns are uploaded, device tensors used in place; ``rows``: int64 positions, array or tensor, in any order and
+    with repeats.  A position outside the table raises ``IndexError`` with the count (synchronises; the kernel reads nothing through it)."""
+    if dev is None:
+        held = [c for c in (*columns.values(), rows) if isinstance(c, torch.Tensor) and c.is_cuda]
+        dev = held[0].device if held else _stack.device()
+    rows = _device(rows if isinstance(rows, torch.Tensor) else np.asarray(rows, dtype=np.int64), dev).reshape(-1)
+    if rows.dtype != torch.int64:
+        raise ValueError(f"row positions must be int64, got {rows.dtype}")
+    cols = {}
+    for name, col in columns.items():
+        if not isinstance(col, torch.Tensor):
+            a = _host_array(col).reshape(-1)
+            if a.dtype.kind in "Mm":
+                a = np.ascontiguousarray(a.astype(f"{'datetime64' if a.dtype.kind == 'M' else 'timedelta64'}[ns]")).view(np.int64)
+            elif a.dtype.kind not in "iufbc":
+                raise ValueError(f"column {name!r} of dtype {a.dtype} cannot live on the device")
+            col = torch.from_numpy(np.ascontiguousarray(a))
+        if col.element_size() not in (1, 2, 4, 8):
+            raise ValueError(f"column {name!r}: elements of {col.element_size()} bytes (1, 2, 4 or 8 are taken)")
+        cols[name] = col.reshape(-1).to(dev).contiguous()
+    if len({c.numel() for c in cols.values()}) > 1:
+        raise ValueError(f"columns differ in length: { {name: c.numel() for name, c in cols.items()} }")
+    return dict(zip(cols, _take(list(cols.values()), rows)))

@@ -68,7 +68,9 @@
 extern "C" {
 #endif
 
-#define ATX_VERSION 420 /* 0.4.2 — additions only, so the number stays: atx_obs_column_ops (a program of library functions over
+#define ATX_VERSION 420 /* 0.4.2 — additions only, so the number stays: atx_obs_order_key / atx_obs_mark_first / atx_obs_take_rows (row
+                           * sets: pandas' order and equality as int64 keys, first occurrences, a gather of rows) with the
+                           * atx_key_dtype enum; atx_obs_column_ops (a program of library functions over
                            * columns) with its ATX_COLOP_* codes; atx_obs_fill_heights (missing station altitudes from an
                            * orography); atx_healpix_ang2pix (HEALPix pixel indices per row) with its atx_healpix_scheme enum; atx_obs_forcings / atx_obs_view_angles / atx_obs_planck_bt (per-row
                            * observation operators); atx_obs_group_mean / atx_obs_group_argmin (superob: per-group
@@ -570,6 +572,59 @@ enum {
 };
 ATX_API int atx_obs_column_ops(int32_t n_ops, const int32_t* op, const int32_t* src, const double* const* in, double* const* out, int64_t n,
                                void* stream);
+
+/* ---- row sets: pandas' order and equality as int64 keys, first occurrences, a gather of rows ---- */
+
+/* key[i] = the int64 ORDER KEY of column[i], defined by two properties: key(a) < key(b) exactly when pandas' sort_values puts a before b,
+ * and key(a) == key(b) exactly when pandas' drop_duplicates treats a and b as the same value.  That rule is not IEEE's: -0.0 and 0.0
+ * are one key; every NaN, whatever its sign or payload, is one key and the LAST (INT64_MAX), and so is NaT; +-inf order as numbers
+ * (+inf stays below the NaN key); integers compare as integers (2^53 and 2^53 + 1 differ).  dtype is an atx_key_dtype:
+ *   F64, F32        the sign-magnitude to two's-complement map of the float64 bit pattern (float32 widened first, which is exact)
+ *   I64 .. I8, U8   the value;   BOOL: 0 / 1 (any non-zero byte is true)
+ *   DATETIME        int64 nanoseconds, NaT = INT64_MIN -> INT64_MAX (the one date that shares the key is INT64_MAX nanoseconds itself,
+ *                   pandas' Timestamp.max, 2262-04-11T23:47:16.854775807)
+ * Integer and compare work only: no rounding anywhere.  The same key serves the sort and the duplicate test.
+ *   column  device, n elements of the dtype       key  device int64 [n]
+ * n < 0, a dtype code outside the enum, a null pointer with n > 0: ATX_EINVAL.
+ *   R: filters/tabular/sort_by.py:44-51 (df.sort_values(by=columns, kind="stable")); filters/tabular/drop_duplicates.py:49-61 */
+#define ATX_MAX_ROWSET_COLUMNS 16
+typedef enum {
+    ATX_KEY_F64 = 0,
+    ATX_KEY_F32 = 1,
+    ATX_KEY_I64 = 2,
+    ATX_KEY_I32 = 3,
+    ATX_KEY_I16 = 4,
+    ATX_KEY_I8 = 5,
+    ATX_KEY_U8 = 6,
+    ATX_KEY_BOOL = 7,
+    ATX_KEY_DATETIME = 8
+} atx_key_dtype;
+ATX_API int atx_obs_order_key(const void* column, int64_t n, int dtype /* atx_key_dtype */, int64_t* key, void* stream);
+
+/* keep[order[i]] = (i == 0) or there is a k < n_keys with keys[k][order[i]] != keys[k][order[i - 1]], for i < n.  With `order` the
+ * STABLE sort of the rows by the key tuple, the rows marked are the first row of every set of rows equal in the keys, in table
+ * order: pandas' df.drop_duplicates(subset), keep="first".  accumulate = 0 writes 0 or 1 to every keep[order[i]]; accumulate = 1
+ * only ever SETS bytes (keep |= ...), for a tuple of more than ATX_MAX_ROWSET_COLUMNS keys taken 16 per launch.  An entry of
+ * order outside [0, n) is not read through and marks nothing.
+ *   keys    HOST array of n_keys DEVICE pointers to int64 [n] (copied into the kernel's arguments; may be freed on return)
+ *   order   device int64 [n], a permutation of 0 .. n - 1        keep  device uint8 [n]
+ * n < 0, n_keys outside 1 .. ATX_MAX_ROWSET_COLUMNS, accumulate other than 0 / 1, a null table, a null pointer with n > 0: ATX_EINVAL.
+ *   R: filters/tabular/drop_duplicates.py:49-61 (obs_df.drop_duplicates(subset=subset)) */
+ATX_API int atx_obs_mark_first(int32_t n_keys, const int64_t* const* keys, const int64_t* order, int64_t n, int accumulate, uint8_t* keep,
+                               void* stream);
+
+/* out[c][i] = in[c][rows[i]] for c < n_cols, i < n_out: the rows of a table of n_in rows at the positions `rows`, every column in one
+ * pass — rows[i] is read once per row for all columns of the call.  width[c] is the element size of column c in bytes, 1, 2, 4 or 8,
+ * mixed freely; elements are copied bit for bit.  A row index outside [0, n_in) is never read through: that output row is left
+ * untouched in every column, and *n_bad (device, set by this call whenever n_out > 0) counts such rows.
+ *   in, out   HOST arrays of n_cols DEVICE pointers (copied into the kernel's arguments); no output may overlap an input or rows
+ *   width     HOST int32 [n_cols]        rows  device int64 [n_out]
+ * n_out < 0, n_in < 0, n_cols outside 1 .. ATX_MAX_ROWSET_COLUMNS, a width other than the four, a null table or n_bad, a null column or
+ * rows with rows to take: ATX_EINVAL, nothing launched.
+ *   R: filters/tabular/sort_by.py:51 (the frame sort_values returns), filters/tabular/drop_duplicates.py:61 (the frame
+ *   drop_duplicates returns): every column of the table at the chosen rows */
+ATX_API int atx_obs_take_rows(int32_t n_cols, const void* const* in, void* const* out, const int32_t* width, const int64_t* rows,
+                              int64_t n_out, int64_t n_in, int64_t* n_bad, void* stream);
 
 /* ---- masks ------------------------------------------------------------------ */
 
