@@ -526,14 +526,19 @@ def obs_group_mean(values, order, offsets, mean, count) -> None:
     """``mean[c, g]`` / ``count[c, g]``: pandas' group mean (one Kahan sum in row order, NaN skipped) of column ``c`` of ``values``
     (float64 ``[n_cols, n_obs]``, rows may be pitched) over the rows ``order[offsets[g]:offsets[g + 1]]`` — ``atx_obs_group_mean``.
     ``order``: int32 row indices in group order (a stable sort by group); ``offsets``: int64 ``[n_groups + 1]``; ``mean`` float64 and
-    ``count`` int64: contiguous ``[n_cols, n_groups]``."""
+    ``count`` int64: ``[n_cols, n_groups]``, rows may be pitched (``out_pitch`` is ``mean.stride(0)``, the same for ``count``)."""
     n_cols, n_obs = values.shape
     n_sel, n_groups = _group_order_args(order, offsets)
     assert values.dtype == mean.dtype == torch.float64 and count.dtype == torch.int64 and (values.stride(1) == 1 or n_obs <= 1)
-    assert mean.is_contiguous() and count.is_contiguous() and tuple(mean.shape) == tuple(count.shape) == (n_cols, n_groups)
+    assert tuple(mean.shape) == tuple(count.shape) == (n_cols, n_groups)
+    assert n_groups <= 1 or (mean.stride(1) == 1 and count.stride(1) == 1)
     val_pitch = values.stride(0) if n_cols > 1 else max(n_obs, 1)
+    out_pitch = max(n_groups, 1)
+    if n_cols > 1:
+        out_pitch = mean.stride(0)
+        assert count.stride(0) == out_pitch, f"mean rows are {out_pitch} elements apart, count rows {count.stride(0)}"
     _call("atx_obs_group_mean", _ptr(values), n_obs, n_cols, val_pitch, _ptr(order), n_sel, _ptr(offsets), n_groups, _ptr(mean), _ptr(count),
-          max(n_groups, 1), _stream())
+          out_pitch, _stream())
 
 
 def obs_group_argmin(distance, order, offsets, nearest) -> None:
@@ -725,34 +730,51 @@ def mask_to_index(mask, n: int | None = None) -> torch.Tensor:
 
 
 class KnnIndex:
-    """A device k-NN index over source points (``atx_knn_build`` / ``atx_knn_query``)."""
+    """A device k-NN index over source points (``atx_knn_build`` / ``atx_knn_query``).  ``workspace``: the caller's uint8 buffer
+    (256-byte aligned, at least ``atx_knn_workspace_bytes(n_src)`` bytes, of which exactly that many are used) instead of one of
+    the index's own."""
 
-    def __init__(self, src_xyz: torch.Tensor) -> None:
+    def __init__(self, src_xyz: torch.Tensor, workspace: torch.Tensor | None = None) -> None:
         assert src_xyz.dtype == torch.float64 and src_xyz.dim() == 2 and src_xyz.shape[1] == 3 and src_xyz.is_contiguous()
         self.n_src = src_xyz.shape[0]
         nbytes = load().atx_knn_workspace_bytes(self.n_src)
         if nbytes == 0:
             raise ValueError(f"cannot index {self.n_src} source points")
-        self.workspace = torch.empty(nbytes + 256, dtype=torch.uint8, device=src_xyz.device)
-        shift = (-self.workspace.data_ptr()) % 256
+        if workspace is None:
+            self.workspace = torch.empty(nbytes + 256, dtype=torch.uint8, device=src_xyz.device)
+            shift = (-self.workspace.data_ptr()) % 256
+        else:
+            assert workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == src_xyz.device
+            assert workspace.numel() >= nbytes and workspace.data_ptr() % 256 == 0
+            self.workspace, shift = workspace, 0
         self._ws = self.workspace[shift: shift + nbytes]
         _call("atx_knn_build", _ptr(src_xyz), self.n_src, _ptr(self._ws), nbytes, _stream())
 
-    def query(self, tgt_xyz: torch.Tensor, k: int) -> tuple[torch.Tensor, torch.Tensor]:
-        """``(indices int32 [n, k], squared distances float64 [n, k])``, nearest first."""
+    def query(self, tgt_xyz: torch.Tensor, k: int, out: tuple[torch.Tensor, torch.Tensor] | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+        """``(indices int32 [n, k], squared distances float64 [n, k])``, nearest first; into ``out`` when given."""
         assert tgt_xyz.dtype == torch.float64 and tgt_xyz.dim() == 2 and tgt_xyz.shape[1] == 3 and tgt_xyz.is_contiguous()
         n = tgt_xyz.shape[0]
-        idx = torch.empty((n, k), dtype=torch.int32, device=tgt_xyz.device)
-        d2 = torch.empty((n, k), dtype=torch.float64, device=tgt_xyz.device)
+        if out is None:
+            idx = torch.empty((n, k), dtype=torch.int32, device=tgt_xyz.device)
+            d2 = torch.empty((n, k), dtype=torch.float64, device=tgt_xyz.device)
+        else:
+            idx, d2 = out
+            assert idx.dtype == torch.int32 and d2.dtype == torch.float64 and tuple(idx.shape) == tuple(d2.shape) == (n, k)
+            assert idx.is_contiguous() and d2.is_contiguous() and idx.device == d2.device == tgt_xyz.device
         _call("atx_knn_query", _ptr(self._ws), self.n_src, _ptr(tgt_xyz), n, k, _ptr(idx), _ptr(d2), _stream())
         return idx, d2
 
 
-def cutout_inside(global_xyz: torch.Tensor, lam_xyz: torch.Tensor, neighbours: torch.Tensor) -> torch.Tensor:
-    """uint8 [n]: the ray through each global point hits a triangle of its nearest LAM points (``atx_cutout_inside``)."""
+def cutout_inside(global_xyz: torch.Tensor, lam_xyz: torch.Tensor, neighbours: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """uint8 [n]: the ray through each global point hits a triangle of its nearest LAM points (``atx_cutout_inside``); into ``out``
+    (uint8 ``[n]``) when given."""
     assert global_xyz.dtype == lam_xyz.dtype == torch.float64 and neighbours.dtype == torch.int32
     n, k = neighbours.shape
-    inside = torch.empty(max(n, 1), dtype=torch.uint8, device=global_xyz.device)
+    if out is None:
+        inside = torch.empty(max(n, 1), dtype=torch.uint8, device=global_xyz.device)
+    else:
+        assert out.dtype == torch.uint8 and out.numel() == n and out.is_contiguous() and out.device == global_xyz.device
+        inside = out
     _call("atx_cutout_inside", _ptr(global_xyz), n, _ptr(lam_xyz), lam_xyz.shape[0], _ptr(neighbours), k, _ptr(inside), _stream())
     return inside[:n]
 
