@@ -23,7 +23,8 @@
 // Both tables start as all-ones bytes (UINT64_MAX / 0xffffffff = -1), one memset each.  A cell index is compared against
 // [0, n_cells) BEFORE it becomes an address; rows outside are dropped, as the reference drops them.
 //
-// atx_obs_fill_stack then writes level t * n_cols + c of a float64 stack: values[c][winner[t][p]], NaN where the winner is -1.
+// atx_obs_fill_stack then writes level t * n_cols + c of a float64 stack: values[c][winner[t][p]], NaN where the winner is -1
+// or any other value outside [0, n_obs) — in both layouts, whatever table the caller hands in.
 // The reads are a gather of 8-byte words; the stores are 16-byte and non-temporal, as in the other streaming kernels:
 //   ATX_FIELDS   lane = two neighbouring points of target t (grid.y = t): their winners are read once and the n_cols levels of
 //                that target are written from them.
@@ -105,18 +106,18 @@ obs_fill_fields_kernel(const int32_t* __restrict__ winner, const double* __restr
                        int64_t val_pitch, int64_t n_cells, int n_time, int64_t pitch) {
     const int64_t p0 = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * VEC;
     if (p0 >= pitch) return;
+    bool real[VEC];  // a point of the grid; padding is told by its position, never by a value of the caller's table
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) real[e] = p0 + e < n_cells;
     for (int t = blockIdx.y; t < n_time; t += gridDim.y) {
         int32_t w[VEC];
 #pragma unroll
-        for (int e = 0; e < VEC; ++e) {
-            const int64_t p = p0 + e;
-            w[e] = p < n_cells ? winner[(int64_t)t * n_cells + p] : -2;
-        }
+        for (int e = 0; e < VEC; ++e) w[e] = real[e] ? winner[(int64_t)t * n_cells + p0 + e] : -1;
         for (int c = 0; c < n_cols; ++c) {
             Pack<double, VEC> o;
 #pragma unroll
             for (int e = 0; e < VEC; ++e) {
-                if (w[e] == -2) o.v[e] = 0.0;
+                if (!real[e]) o.v[e] = 0.0;
                 else o.v[e] = (w[e] >= 0 && (int64_t)w[e] < n_obs) ? values[(int64_t)c * val_pitch + w[e]] : quiet_nan<double>();
             }
             obs_store<VEC>(out + ((int64_t)t * n_cols + c) * pitch + p0, o);
