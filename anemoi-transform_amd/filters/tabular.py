@@ -27,7 +27,10 @@ order: ``obs.sort_order`` -> ``atx_obs_order_key`` and the library's stable radi
 group of equal key tuples: ``obs.first_rows`` -> ``atx_obs_mark_first``) — both end in ONE gather of every column
 (``obs.take_rows`` -> ``atx_obs_take_rows``) — and ``drop`` (columns leave; host bookkeeping, nothing is copied).
 
-A table is a pandas DataFrame (when pandas can be imported) or a plain mapping ``name -> 1-D array / device tensor``.
+A table is a pandas DataFrame or a plain mapping ``name -> 1-D array / device tensor``.  Every ``forward`` wraps it in
+``tables.Table``, which is where the table rule lives: which columns there are, where the launch runs, which columns are datetimes
+and what goes back to the caller — a DataFrame for a DataFrame, a new dict of device tensors if any column was a tensor, else of
+numpy arrays, never the caller's object (``with_columns``, ``replaced``, ``without``, ``take``).
 
 Deviations from the reference, each said once when it first matters (``core.say_once``):
   * rows are taken by POSITION.  The reference goes through index labels (``df.loc[idxmin]``): a table whose index has duplicate
@@ -61,7 +64,6 @@ from __future__ import annotations
 
 import datetime
 import logging
-from collections.abc import Mapping
 from typing import Any
 
 import numpy as np
@@ -71,32 +73,9 @@ from .. import healpix, obs
 from ..core import Filter, filter_registry, say_once
 from ..fields import MISSING, Field, FieldList, new_field_from_stack
 from ..grids import lookup
+from ..tables import NAT, Table, column_kind, dtype_kind, float_column, host_array, on_device, to_ns
 
 LOG = logging.getLogger(__name__)
-
-
-def _is_dataframe(table: Any) -> bool:
-    try:
-        import pandas as pd
-    except ImportError:
-        return False
-    return isinstance(table, pd.DataFrame)
-
-
-def _column_names(table: Any) -> list[str]:
-    if _is_dataframe(table):
-        return list(table.columns)
-    if isinstance(table, Mapping):
-        return list(table.keys())
-    raise TypeError(f"a table is a pandas DataFrame or a mapping name -> column, got {type(table).__name__}")
-
-
-def _require(table: Any, names: list[str]) -> None:
-    # R: filters/tabular/support/utils.py:18-21
-    available = _column_names(table)
-    missing = set(names) - set(available)
-    if missing:
-        raise ValueError(f"DataFrame is missing columns: {missing}. Available columns: {available}")
 
 
 def _healpix(grid: str) -> bool:
@@ -143,7 +122,7 @@ class _GridTemplate(Field):
 
 def _to_datetime(ns: int) -> datetime.datetime | None:
     """``pd.Timestamp(ns).to_pydatetime()``: microseconds kept, the nanoseconds below them dropped; NaT -> None."""
-    if ns == obs.NAT:
+    if ns == NAT:
         return None
     return datetime.datetime(1970, 1, 1) + datetime.timedelta(microseconds=int(ns) // 1000)
 
@@ -195,19 +174,19 @@ class IrregularToGrid(Filter):
         return _named_grid(grid)
 
     def forward(self, table: Any) -> FieldList:
-        _require(table, ["date", "spatial_index", self.window_date_column] + list(self.columns))
-        if _is_dataframe(table) and not table.index.is_unique:
+        t = Table(table)
+        t.require(["date", "spatial_index", self.window_date_column] + list(self.columns))
+        if t.frame and not table.index.is_unique:
             say_once(LOG, (type(self), "position"), "irregular_to_grid: the table's index has duplicate labels; rows are taken by "
                      "position here, the reference would repeat the rows of a duplicated label")
-        cells = table["spatial_index"]
-        kind = cells.dtype.is_floating_point if isinstance(cells, torch.Tensor) else getattr(np.asarray(cells).dtype, "kind", "") == "f"
-        if kind:
+        cells = t["spatial_index"]
+        if column_kind(cells) == "f":
             say_once(LOG, (type(self), "float-index"), "irregular_to_grid: spatial_index is a float column; whole numbers are "
                      "read as indices and missing entries dropped", level=logging.INFO)
         latitudes, longitudes = self._define_grid(self.grid)
-        window_ns = obs.to_ns(table[self.window_date_column])
+        window_ns = to_ns(t[self.window_date_column])
         targets = obs.unique_in_order(window_ns)
-        stack = obs.grid_observations(table["date"], cells, [table[c] for c in self.columns], targets, n_cells=len(latitudes),
+        stack = obs.grid_observations(t["date"], cells, [t[c] for c in self.columns], targets, n_cells=len(latitudes),
                                       window=self.window, freq=self.freq_ns, weight=self.nan_score_weight)
         template = _GridTemplate(latitudes, longitudes)
         fields = []
@@ -237,16 +216,12 @@ class AssignToGrid(Filter):
         return f"AssignToGrid(grid={self.grid!r})"
 
     def forward(self, table: Any) -> Any:
-        _require(table, ["latitude", "longitude"])
+        t = Table(table)
+        t.require(["latitude", "longitude"])
         grid_lat, grid_lon = _named_grid(self.grid)
-        lat, lon = table["latitude"], table["longitude"]
-        if isinstance(lat, torch.Tensor):
-            lat, lon = lat.cpu().numpy(), lon.cpu().numpy()
-        distances, indices = obs.nearest_grid_index(grid_lat, grid_lon, lat, lon)
+        distances, indices = obs.nearest_grid_index(grid_lat, grid_lon, t["latitude"], t["longitude"])  # host arrays: the search's own crossing
         added = {f"grid_index_{self.grid}": indices, "distance": distances}
-        if _is_dataframe(table):
-            return table.assign(**added)
-        return {**table, **added}
+        return table.assign(**added) if t.frame else {**table, **added}
 
 
 class SuperOb(Filter):
@@ -301,205 +276,81 @@ class SuperOb(Filter):
         return _named_grid(grid)
 
     def forward(self, table: Any) -> Any:
-        names = _column_names(table)
-        n_rows = len(table) if _is_dataframe(table) else (len(table[names[0]]) if names else 0)
-        if self.grid == "native" or n_rows == 0:
+        t = Table(table)
+        if self.grid == "native" or t.n_rows == 0:
             return table
         grid_lat, grid_lon = self._define_grid(self.grid)
-        _require(table, ["date", "latitude", "longitude"] + self.columns_to_groupby + self.columns_to_take_nearest)
-        if _is_dataframe(table) and not table.index.is_unique:
+        t.require(["date", "latitude", "longitude"] + self.columns_to_groupby + self.columns_to_take_nearest)
+        if t.frame and not table.index.is_unique:
             say_once(LOG, (type(self), "position"), "superob: the table's index has duplicate labels; rows are taken by position "
                      "here, the reference would repeat the rows of a duplicated label")
-        return _superob(self, _Table(table), grid_lat, grid_lon)
+        return _superob(self, t, grid_lat, grid_lon)
 
 
-class _Table:
-    """The columns of a DataFrame or mapping by name, with what ``SuperOb`` needs of them: positional row selection that keeps
-    the column's kind, and a float64 device view for the columns that are averaged."""
-
-    def __init__(self, table: Any) -> None:
-        self.frame = _is_dataframe(table)
-        self.columns = {c: table[c] for c in _column_names(table)}
-        self.resident = any(isinstance(v, torch.Tensor) for v in self.columns.values())
-        self.device = next((v.device for v in self.columns.values() if isinstance(v, torch.Tensor) and v.is_cuda), None)
-
-    def __len__(self) -> int:
-        return len(next(iter(self.columns.values())))
-
-    def take(self, rows: np.ndarray | torch.Tensor) -> "_Table":
-        """The rows at the positions ``rows`` (host array or device tensor, whichever the column is)."""
-        host, dev = (rows.cpu().numpy(), rows) if isinstance(rows, torch.Tensor) else (rows, None)
-        out = {}
-        for name, col in self.columns.items():
-            if isinstance(col, torch.Tensor):
-                index = torch.from_numpy(host) if dev is None else dev
-                out[name] = col.reshape(-1)[index.to(col.device)]
-            elif hasattr(col, "iloc"):
-                out[name] = col.iloc[host]
-            else:
-                out[name] = np.asarray(col)[host]
-        taken = _Table.__new__(_Table)
-        taken.frame, taken.columns, taken.resident, taken.device = self.frame, out, self.resident, self.device
-        return taken
-
-    def is_datetime(self, name: str) -> bool:
-        col = self.columns[name]
-        if isinstance(col, torch.Tensor):
-            return name == "date"  # obs.to_ns: an int64 tensor in the date column IS nanoseconds
-        return getattr(obs._host_array(col).dtype, "kind", "") == "M"
-
-    def missing(self, name: str, dev: torch.device) -> torch.Tensor:
-        """Where the column has no value (NaN / NaT), on the device."""
-        col = self.columns[name]
-        if self.is_datetime(name):
-            return obs._device(obs.to_ns(col), dev) == obs.NAT
-        if isinstance(col, torch.Tensor):
-            return torch.isnan(col.reshape(-1)).to(dev) if col.dtype.is_floating_point else torch.zeros(col.numel(), dtype=torch.bool, device=dev)
-        a = obs._host_array(col)
-        if a.dtype.kind == "f":
-            return obs._device(np.isnan(a), dev)
-        if a.dtype.kind in "iub":
-            return torch.zeros(a.size, dtype=torch.bool, device=dev)
-        return obs._device(np.array([v is None or v != v for v in a.tolist()], dtype=bool), dev)
-
-    def as_float64(self, name: str, out: torch.Tensor) -> None:
-        """The column as float64 into the device row ``out``: integers and bools converted, datetimes as ``(double)`` of their int64
-        nanoseconds with NaT as NaN — what pandas hands to its group mean.  Anything else cannot be averaged: ``TypeError``."""
-        col = self.columns[name]
-        if self.is_datetime(name):
-            ns = obs._device(obs.to_ns(col), out.device)
-            out.copy_(ns)
-            out.masked_fill_(ns == obs.NAT, float("nan"))
-            return
-        if not isinstance(col, torch.Tensor):
-            a = obs._host_array(col)
-            if a.dtype.kind not in "iubf":
-                raise TypeError(f"superob: column {name!r} of dtype {a.dtype} cannot be averaged; name it in columns_to_groupby or "
-                                "columns_to_take_nearest, or drop it first")
-            col = torch.from_numpy(np.ascontiguousarray(a.reshape(-1)))
-        elif col.dtype.is_complex:
-            raise TypeError(f"superob: column {name!r} of dtype {col.dtype} cannot be averaged")
-        out.copy_(col.reshape(-1))
-
-
-def _superob(f: SuperOb, table: _Table, grid_lat: np.ndarray, grid_lon: np.ndarray) -> Any:
-    from .. import stack as _stack
-
-    dev = table.device or _stack.device()
+def _superob(f: SuperOb, t: Table, grid_lat: np.ndarray, grid_lon: np.ndarray) -> Any:
+    dev = t.device
     # R: superob.py:72 — rows without date / latitude / longitude leave (here: a copy of the rest, the caller's table stays)
-    gone = table.missing("date", dev) | table.missing("latitude", dev) | table.missing("longitude", dev)
+    gone = t.missing("date", dev) | t.missing("latitude", dev) | t.missing("longitude", dev)
     if bool(gone.any()):
-        table = table.take(torch.nonzero(~gone).reshape(-1))
-    n = len(table)
+        t = Table(t.take(torch.nonzero(~gone).reshape(-1)), like=t)
+    n = t.n_rows
     if n == 0:
-        return _superob_result(table, {c: v for c, v in table.columns.items()}, None)
+        return t.table
     # R: support/superob.py:43-69
-    lat, lon = (c.cpu().numpy() if isinstance(c, torch.Tensor) else obs._host_array(c) for c in (table.columns["latitude"], table.columns["longitude"]))
-    distance, spatial = obs.nearest_grid_index(grid_lat, grid_lon, lat, lon)
-    distance, spatial = obs._device(np.asarray(distance, dtype=np.float64), dev), obs._device(np.asarray(spatial, dtype=np.int64), dev)
-    date = obs._device(obs.to_ns(table.columns["date"]), dev)
+    distance, spatial = obs.nearest_grid_index(grid_lat, grid_lon, t["latitude"], t["longitude"])
+    distance, spatial = on_device(np.asarray(distance, dtype=np.float64), dev), on_device(np.asarray(spatial, dtype=np.int64), dev)
+    date = on_device(to_ns(t["date"]), dev)
     slot = (date - date.min()) // (f.timeslot_length * 10**9)
     added = {"grid_index": spatial + len(grid_lat) * slot, "spatial_index": spatial, "distance": distance}
-    columns = dict(table.columns)
-    columns.update(added)  # DataFrame.assign: an existing column keeps its place, a new one goes to the end
-    table.columns = columns
+    names = list(dict.fromkeys(t.names + list(added)))  # DataFrame.assign: an existing column keeps its place, a new one goes to the end
     key_names = ["grid_index"] + f.columns_to_groupby
-    averaged = [c for c in columns if c not in set(key_names) | set(f.columns_to_take_nearest)]
+    averaged = [c for c in names if c not in set(key_names) | set(f.columns_to_take_nearest)]
+    asked = {c: added[c] for c in f.columns_to_groupby + f.columns_to_take_nearest if c in added}
+    if asked:  # the table came with a column of that name (superob's own output does): the new one replaces it before rows are taken
+        t = Table(t.with_columns(asked), like=t)
     # R: superob.py:86-88
     keys, valid = [], None
     for name in key_names:
-        codes, ok = obs.key_codes(columns[name])
+        codes, ok = obs.key_codes(added[name] if name in added else t[name])
+        if ok is None and name not in added and t.is_datetime(name):  # int64 nanoseconds on the device: NaT is a missing key there too
+            ok = codes != NAT
         keys.append(codes)
         if ok is not None:
-            ok = obs._device(ok, dev)
+            ok = on_device(ok, dev)
             valid = ok if valid is None else valid & ok
     groups = obs.superob_groups(keys, valid, dev)
     values = torch.empty((len(averaged), n), dtype=torch.float64, device=dev)
     for j, name in enumerate(averaged):
-        table.as_float64(name, values[j])
+        if name in added:
+            values[j].copy_(added[name])
+        else:
+            t.as_float64(name, values[j])
     mean, _ = obs.group_means(values, groups)
     nearest = obs.group_nearest(distance, groups)
     # R: superob.py:94-96 — groups in order of first appearance, then a stable sort by date (NaT last)
-    out_names = f.columns_to_groupby + [c for c in averaged if c != "distance"] + f.columns_to_take_nearest
     mean_of = {name: mean[j] for j, name in enumerate(averaged)}
 
     def as_ns(m: torch.Tensor) -> torch.Tensor:
         # pandas: the float64 quotient truncated back to int64, NaT where nothing was summed
-        return torch.where(torch.isnan(m), torch.zeros_like(m), m).to(torch.int64).masked_fill_(torch.isnan(m), obs.NAT)
+        return torch.where(torch.isnan(m), torch.zeros_like(m), m).to(torch.int64).masked_fill_(torch.isnan(m), NAT)
 
     when = as_ns(mean_of["date"]) if "date" in mean_of else date[groups.first if "date" in key_names else nearest]
     when = when[groups.appearance]
-    by_date = torch.argsort(torch.where(when == obs.NAT, torch.full_like(when, torch.iinfo(torch.int64).max), when), stable=True)
+    by_date = torch.argsort(torch.where(when == NAT, torch.full_like(when, torch.iinfo(torch.int64).max), when), stable=True)
     final = groups.appearance[by_date]
-    result = {}
-    for name in out_names:
-        if name in mean_of:
-            m = mean_of[name][final]
-            result[name] = as_ns(m) if table.is_datetime(name) else m
-        else:
-            result[name] = (groups.first if name in key_names else nearest)[final]  # a row index: the value is taken below
-    return _superob_result(table, result, by_date, set(mean_of))
-
-
-def _superob_result(table: _Table, result: dict[str, Any], labels: torch.Tensor | None, computed: set[str] = frozenset()) -> Any:
-    """The output table in the kind of the input.  ``result[name]`` is a device column of values for ``computed`` names and a
-    device column of ROW POSITIONS of ``table`` for the others; ``labels``: the index a DataFrame gets (pandas keeps the group
-    numbers through ``sort_values``).  ``labels is None``: ``result`` already holds the (empty) columns."""
-    if labels is None:
-        if table.frame:
-            import pandas as pd
-
-            return pd.DataFrame(result)
-        return dict(result)
-    host_rows: dict[int, np.ndarray] = {}
-
-    def rows_on_host(rows: torch.Tensor) -> np.ndarray:
-        return host_rows.setdefault(id(rows), rows.cpu().numpy())
-
-    out = {}
-    for name, col in result.items():
-        source = table.columns.get(name)
-        if name in computed:
-            if table.frame or not table.resident:
-                col = col.cpu().numpy()
-                col = col.view("datetime64[ns]") if table.is_datetime(name) else col
-        elif isinstance(source, torch.Tensor):
-            col = source.reshape(-1)[col.to(source.device)]
-            col = col if table.resident and not table.frame else col.cpu().numpy()
-        elif hasattr(source, "iloc"):
-            col = source.iloc[rows_on_host(col)]
-            col = col.reset_index(drop=True) if table.frame else col.to_numpy()
-        else:
-            col = np.asarray(source)[rows_on_host(col)]
-        if table.resident and not table.frame and isinstance(col, np.ndarray) and col.dtype.kind in "iubfM":
-            col = obs._device(obs.to_ns(col) if col.dtype.kind == "M" else col, table.device or result[name].device)
-        out[name] = col
-    if table.frame:
-        import pandas as pd
-
-        frame = pd.DataFrame(out)
-        frame.index = labels.cpu().numpy()
-        return frame
+    # columns_to_groupby, the averaged columns in table order, columns_to_take_nearest: two row sets, one gather each
+    dates = [name for name in averaged if name not in added and t.is_datetime(name)]
+    means = {name: (as_ns(m[final]) if name in dates else m[final]) for name, m in mean_of.items() if name != "distance"}
+    out = Table(t.take(groups.first[final], f.columns_to_groupby), like=t).with_columns(means, datetimes=dates)
+    near = t.take(nearest[final], f.columns_to_take_nearest)
+    if not t.frame:
+        return {**out, **near}
+    out = out.reset_index(drop=True).join(near.reset_index(drop=True))
+    out.index = by_date.cpu().numpy()  # pandas keeps the group numbers through sort_values
     return out
 
 
 # ---- per-row derived columns ---------------------------------------------------------------------------------------------------------
-def _table_device(table: Any) -> tuple[bool, torch.device]:
-    """``(resident, device)``: whether any column of the table is a device tensor, and the device the launch runs on."""
-    from .. import stack as _stack
-
-    tensors = [v for v in (table[c] for c in _column_names(table)) if isinstance(v, torch.Tensor)]
-    return bool(tensors), next((v.device for v in tensors if v.is_cuda), None) or _stack.device()
-
-
-def _with_columns(table: Any, added: dict[str, torch.Tensor], resident: bool) -> Any:
-    """The table with the device rows ``added``, in the kind of the input and never the caller's object: ``DataFrame.assign`` for a
-    DataFrame; for a mapping a new dict, of device tensors if any input column was one, else with the new columns as numpy arrays."""
-    if _is_dataframe(table):
-        return table.assign(**{name: col.cpu().numpy() for name, col in added.items()})
-    return {**table, **{name: (col if resident else col.cpu().numpy()) for name, col in added.items()}}
-
-
 class AddForcings(Filter):
     """Adds solar and calendar forcing columns to the table (R: filters/tabular/add_forcings.py:19-127,
     support/compute_forcings.py:14-87).
@@ -523,9 +374,9 @@ class AddForcings(Filter):
         return f"AddForcings({list(self.columns)})"
 
     def forward(self, table: Any) -> Any:
-        _require(table, ["date", "latitude", "longitude"])
-        resident, dev = _table_device(table)
-        return _with_columns(table, obs.forcings(table["date"], table["latitude"], table["longitude"], list(self.columns), dev=dev), resident)
+        t = Table(table)
+        t.require(["date", "latitude", "longitude"])
+        return t.with_columns(obs.forcings(t["date"], t["latitude"], t["longitude"], list(self.columns), dev=t.device))
 
 
 class AddAzimuth(Filter):
@@ -549,12 +400,12 @@ class AddAzimuth(Filter):
         return f"AddAzimuth({self.azimuth!r})"
 
     def forward(self, table: Any) -> Any:
-        _require(table, [self.spacecraft_latitude, self.spacecraft_longitude])
-        _require(table, ["latitude", "longitude"])
-        resident, dev = _table_device(table)
-        angles = obs.view_angles(table["latitude"], table["longitude"], table[self.spacecraft_latitude], table[self.spacecraft_longitude],
-                                 azimuth=True, zenith=False, dev=dev)
-        return _with_columns(table, {self.azimuth: angles["azimuth"]}, resident)
+        t = Table(table)
+        t.require([self.spacecraft_latitude, self.spacecraft_longitude])
+        t.require(["latitude", "longitude"])
+        angles = obs.view_angles(t["latitude"], t["longitude"], t[self.spacecraft_latitude], t[self.spacecraft_longitude],
+                                 azimuth=True, zenith=False, dev=t.device)
+        return t.with_columns({self.azimuth: angles["azimuth"]})
 
 
 class AddMSGAngles(Filter):
@@ -583,14 +434,14 @@ class AddMSGAngles(Filter):
         return f"AddMSGAngles({'+'.join(self.angle)})"
 
     def forward(self, table: Any) -> Any:
-        if self.satellite_id not in _column_names(table):
+        t = Table(table)
+        if self.satellite_id not in t.names:
             raise ValueError(f"DataFrame must contain a column '{self.satellite_id}' for MSG angles calculation.")
-        _require(table, ["latitude", "longitude", "date"])
-        resident, dev = _table_device(table)
-        sat_lat, sat_lon = obs.meteosat_position(table[self.satellite_id], table["date"], dev=dev)
-        angles = obs.view_angles(table["latitude"], table["longitude"], sat_lat, sat_lon, azimuth="azimuth" in self.angle,
-                                 zenith="zenith" in self.angle, dev=dev)
-        return _with_columns(table, {getattr(self, name): angles[name] for name in self.angle}, resident)
+        t.require(["latitude", "longitude", "date"])
+        sat_lat, sat_lon = obs.meteosat_position(t[self.satellite_id], t["date"], dev=t.device)
+        angles = obs.view_angles(t["latitude"], t["longitude"], sat_lat, sat_lon, azimuth="azimuth" in self.angle,
+                                 zenith="zenith" in self.angle, dev=t.device)
+        return t.with_columns({getattr(self, name): angles[name] for name in self.angle})
 
 
 class RadianceToBrightnessTemperature(Filter):
@@ -617,8 +468,8 @@ class RadianceToBrightnessTemperature(Filter):
     def forward(self, table: Any) -> Any:
         import re
 
-        names = _column_names(table)
-        cols = [c for c in names if isinstance(c, str) and c.startswith(self.input_prefix)]
+        t = Table(table)
+        cols = [c for c in t.names if isinstance(c, str) and c.startswith(self.input_prefix)]
         if not cols:
             raise ValueError(f"No columns starting with '{self.input_prefix}' found in DataFrame.")
         found = [re.search(r"_(\d+)$", c) for c in cols]
@@ -628,17 +479,9 @@ class RadianceToBrightnessTemperature(Filter):
         chans = np.array([int(m.group(1)) for m in found], dtype=np.int64)
         order = np.argsort(chans, kind="stable")
         cols, chans = [cols[i] for i in order], chans[order]
-        resident, dev = _table_device(table)
-        radiance = torch.stack([obs.float_column(table[c], dev) for c in cols])
+        radiance = torch.stack([float_column(t[c], t.device) for c in cols])
         tb = obs.brightness_temperature(radiance, obs.cris_wavenumbers(chans, self.mode), out=radiance)
-        renamed = {c: f"{self.output_prefix}{ch}" for c, ch in zip(cols, chans)}
-        if _is_dataframe(table):
-            out = table.copy()
-            for j, c in enumerate(cols):
-                out[c] = tb[j].cpu().numpy()
-            return out.rename(columns=renamed)
-        row = {c: j for j, c in enumerate(cols)}
-        return {renamed.get(c, c): ((tb[row[c]] if resident else tb[row[c]].cpu().numpy()) if c in row else table[c]) for c in names}
+        return t.replaced(dict(zip(cols, tb)), renamed={c: f"{self.output_prefix}{ch}" for c, ch in zip(cols, chans)})
 
 
 class AddHealpix(Filter):
@@ -666,11 +509,11 @@ class AddHealpix(Filter):
         return f"AddHealpix(nside={self.nside})"
 
     def forward(self, table: Any) -> Any:
-        _require(table, ["latitude", "longitude"])
+        t = Table(table)
+        t.require(["latitude", "longitude"])
         healpix.check_nside(self.nside, nest=True)
-        resident, dev = _table_device(table)
-        index = healpix.ang2pix(self.nside, table["longitude"], table["latitude"], nest=True, dev=dev)
-        return _with_columns(table, {f"healpix_idx_{self.nside}": index}, resident)
+        index = healpix.ang2pix(self.nside, t["longitude"], t["latitude"], nest=True, dev=t.device)
+        return t.with_columns({f"healpix_idx_{self.nside}": index})
 
 
 class FillHeights(Filter):
@@ -735,12 +578,11 @@ class FillHeights(Filter):
         return self._grid
 
     def forward(self, table: Any) -> Any:
-        _require(table, [self.station_altitude])
-        _require(table, ["latitude", "longitude"])
+        t = Table(table)
+        t.require([self.station_altitude])
+        t.require(["latitude", "longitude"])
         grid = self.grid()  # the file's checks come before anything touches the device
-        resident = any(isinstance(table[c], torch.Tensor) for c in _column_names(table))
-        filled = obs.fill_heights(grid, table["latitude"], table["longitude"], table[self.station_altitude])
-        return _with_columns(table, {self.station_altitude: filled}, resident)
+        return t.with_columns({self.station_altitude: obs.fill_heights(grid, t["latitude"], t["longitude"], t[self.station_altitude])})
 
 
 class GeopotentialToHeightTabular(Filter):
@@ -762,19 +604,17 @@ class GeopotentialToHeightTabular(Filter):
         return f"GeopotentialToHeightTabular({self.geopotential!r} -> {self.height!r})"
 
     def forward(self, table: Any) -> Any:
-        _require(table, [self.geopotential])
-        z = table[self.geopotential]
-        if isinstance(z, torch.Tensor):
-            if z.dtype.is_complex or z.dtype == torch.bool:
-                raise ValueError(f"a numeric column is needed, got {z.dtype}")
-            # the divisor as a tensor on z's device: torch turns division by a Python number into a multiplication by its
-            # reciprocal on the device, which is two roundings and not numpy's quotient
-            height = torch.true_divide(z.to(torch.float64), torch.full((), self.G, dtype=torch.float64, device=z.device))
-        elif _is_dataframe(table):
+        t = Table(table)
+        t.require([self.geopotential])
+        z = t[self.geopotential]
+        if t.frame:
             return table.assign(**{self.height: z.astype(np.float64) / self.G})
-        else:
-            height = np.asarray(obs._host_array(z), dtype=np.float64) / self.G
-        return {**table, self.height: height}
+        if not t.resident:
+            return {**table, self.height: np.asarray(host_array(z), dtype=np.float64) / self.G}
+        # the divisor as a tensor on z's device: torch turns division by a Python number into a multiplication by its
+        # reciprocal on the device, which is two roundings and not numpy's quotient
+        z = float_column(z, t.device)
+        return t.with_columns({self.height: torch.true_divide(z, torch.full((), self.G, dtype=torch.float64, device=z.device))})
 
 
 def column_ops_parity_note() -> None:
@@ -825,50 +665,17 @@ class ApplyColumnTransformations(Filter):
         return "ApplyColumnTransformations(" + ", ".join(f"{t}={f}({s})" for t, s, f in self.transformations) + ")"
 
     def forward(self, table: Any) -> Any:
-        names = _column_names(table)
+        t = Table(table)
         # obs.column_ops refuses a missing or non-numeric source on the host and only then looks for the device
         added = obs.column_ops(table, self.transformations)
-        narrow = [s for s, dtype in obs.column_dtypes(table, self.transformations).items() if obs._dtype_kind(dtype) == "f" and dtype.itemsize < 8]
+        narrow = [s for s, dtype in obs.column_dtypes(table, self.transformations).items() if dtype_kind(dtype) == "f" and dtype.itemsize < 8]
         if narrow:
             say_once(LOG, (type(self), "float64"), "apply_column_transformations: float32 and float16 columns (here %s) are read as float64 and "
                      "the result is float64 (numpy would stay in float32)", narrow, level=logging.INFO)
-        return _with_columns(table, added, any(isinstance(table[c], torch.Tensor) for c in names))
+        return t.with_columns(added)
 
 
 # ---- row sets: sort_by, drop_duplicates, drop ------------------------------------------------------------------------------------------
-def _table_rows(table: Any) -> int:
-    names = _column_names(table)
-    return len(table) if _is_dataframe(table) else (len(table[names[0]]) if names else 0)
-
-
-def _key_columns(table: Any, names: list[str]) -> tuple[list[Any], list[bool]]:
-    """The key columns ``names`` of the table and, per column, whether it is int64 nanoseconds: a device tensor named ``date``
-    (``obs.to_ns``: an int64 tensor in the date column IS nanoseconds; a datetime64 array says so itself)."""
-    columns = [table[name] for name in names]
-    return columns, [name == "date" and isinstance(c, torch.Tensor) and c.dtype == torch.int64 for name, c in zip(names, columns)]
-
-
-def _take_table(table: Any, rows: torch.Tensor) -> Any:
-    """The rows of the table at the device positions ``rows``, in the kind of the input and never the caller's object: ``iloc`` for a
-    DataFrame (index labels and dtypes are pandas' own); for a mapping a new dict — device tensors through ``obs.take_rows`` if any
-    column was a device tensor (a non-numeric host column cannot live there and stays a host array), else numpy arrays."""
-    if _is_dataframe(table):
-        return table.iloc[rows.cpu().numpy()]
-    names = _column_names(table)
-    resident, dev = _table_device(table)
-    host = None
-    taken: dict[str, Any] = {}
-    if resident:
-        numeric = {name: table[name] for name in names
-                   if isinstance(table[name], torch.Tensor) or getattr(obs._host_array(table[name]).dtype, "kind", "O") in "iufbcMm"}
-        taken = obs.take_rows(numeric, rows, dev=dev)
-    for name in names:
-        if name not in taken:
-            host = rows.cpu().numpy() if host is None else host
-            taken[name] = np.asarray(obs._host_array(table[name]))[host]
-    return {name: taken[name] for name in names}
-
-
 class SortBy(Filter):
     """Sorts the rows of a table by the columns in ``columns`` (R: filters/tabular/sort_by.py:21-63: ``df.sort_values(by=columns,
     kind="stable")``): ascending by the key tuple, the first column most significant, missing values (NaN, NaT) of a key last, rows of
@@ -889,12 +696,12 @@ class SortBy(Filter):
         return f"SortBy({self.columns})"
 
     def forward(self, table: Any) -> Any:
-        _require(table, self.columns)
-        if _table_rows(table) == 0 or not self.columns:
-            return table.copy() if _is_dataframe(table) else dict(table)
-        columns, datetimes = _key_columns(table, self.columns)
-        _, dev = _table_device(table)
-        return _take_table(table, obs.sort_order(columns, dev, datetimes=datetimes))
+        t = Table(table)
+        t.require(self.columns)
+        if t.n_rows == 0 or not self.columns:
+            return table.copy() if t.frame else dict(table)
+        keys = [t[name] for name in self.columns]
+        return t.take(obs.sort_order(keys, t.device, datetimes=[t.is_datetime(name) for name in self.columns]))
 
 
 class DropDuplicates(Filter):
@@ -917,21 +724,20 @@ class DropDuplicates(Filter):
         return f"DropDuplicates({self.columns if self.columns else (self.column_prefix + '*' if self.column_prefix else 'all columns')})"
 
     def forward(self, table: Any) -> Any:
-        names = _column_names(table)
+        t = Table(table)
         if self.columns:
             subset = list(self.columns)
-            _require(table, subset)
+            t.require(subset)
         elif self.column_prefix:
-            subset = [c for c in names if isinstance(c, str) and c.startswith(self.column_prefix)]
+            subset = [c for c in t.names if isinstance(c, str) and c.startswith(self.column_prefix)]
             if not subset:
                 raise ValueError(f"No columns starting with '{self.column_prefix}' found in DataFrame.")
         else:
-            subset = names
-        if _table_rows(table) == 0 or not subset:
-            return table.copy() if _is_dataframe(table) else dict(table)
-        columns, datetimes = _key_columns(table, subset)
-        _, dev = _table_device(table)
-        return _take_table(table, obs.first_rows(columns, dev, datetimes=datetimes))
+            subset = t.names
+        if t.n_rows == 0 or not subset:
+            return table.copy() if t.frame else dict(table)
+        keys = [t[name] for name in subset]
+        return t.take(obs.first_rows(keys, t.device, datetimes=[t.is_datetime(name) for name in subset]))
 
 
 class Drop(Filter):
@@ -949,11 +755,9 @@ class Drop(Filter):
         return f"Drop({self.columns})"
 
     def forward(self, table: Any) -> Any:
-        _require(table, self.columns)
-        if _is_dataframe(table):
-            return table.drop(labels=self.columns, axis=1)
-        gone = set(self.columns)
-        return {name: table[name] for name in _column_names(table) if name not in gone}
+        t = Table(table)
+        t.require(self.columns)
+        return t.without(self.columns)
 
 
 filter_registry.register("sort_by", SortBy)

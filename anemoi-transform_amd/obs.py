@@ -9,7 +9,9 @@ table goes to the device once (a few columns of ``n_obs`` values), ``atx_obs_bes
 What this module restates on the host is the bookkeeping around those two launches: the window strings the reference hands to
 ``anemoi.utils.window.Window`` (``parse_window``), ``pd.Timedelta(time_freq)`` (``parse_frequency``), datetimes as int64
 nanoseconds (``to_ns``), ``spatial_index`` as int64 cells (``to_cells``) and the targets in order of first appearance
-(``unique_in_order``).  Arrays may be numpy arrays (uploaded) or device tensors (used in place).
+(``unique_in_order``).  Arrays may be numpy arrays (uploaded) or device tensors (used in place).  The column readers
+(``to_ns``, ``float_column``, ``host_array``, ``datetime_ns``), the device a launch runs on (``launch_device``) and ``take_rows`` live in
+``tables`` and are imported here under the names this module has always offered them by.
 
 The second half serves ``superob`` (R: filters/tabular/superob.py), which thins a raw table before it is gridded: ``key_codes`` and
 ``superob_groups`` turn key columns into rows in group order (torch on the device: one stable sort), ``group_means`` is pandas'
@@ -48,8 +50,8 @@ import torch
 from . import native
 from . import stack as _stack
 from .stack import COLUMNS, Stack
-
-NAT = np.iinfo(np.int64).min  # numpy's / pandas' NaT as int64
+from .tables import NAT, datetime_ns, float_column, host_array, launch_device, take_rows, to_ns  # noqa: F401
+from .tables import dtype_kind as _dtype_kind, gather as _take, on_device as _device  # the names this module, its tests and tools know them by
 
 _UNIT_NS = {"s": 10**9, "m": 60 * 10**9, "h": 3600 * 10**9, "d": 86400 * 10**9}
 _OFFSET = re.compile(r"^([+-]?)(\d+)([smhd])$")
@@ -108,30 +110,6 @@ def parse_frequency(freq: Any) -> int:
     return ns
 
 
-def _host_array(column: Any) -> np.ndarray:
-    if hasattr(column, "dt") and getattr(column.dt, "tz", None) is not None:  # a tz-aware pandas Series: all times are UTC
-        column = column.dt.tz_convert(None)
-    if hasattr(column, "to_numpy"):
-        return column.to_numpy()
-    return np.asarray(column)
-
-
-def to_ns(column: Any) -> np.ndarray | torch.Tensor:
-    """A column of datetimes as int64 nanoseconds since the epoch, NaT = ``INT64_MIN``.  datetime64 arrays of any unit, pandas
-    Series, lists of datetimes or ISO strings; an int64 array or tensor is taken to BE nanoseconds already."""
-    if isinstance(column, torch.Tensor):
-        if column.dtype != torch.int64:
-            raise ValueError(f"a date tensor must hold int64 nanoseconds, got {column.dtype}")
-        return column.reshape(-1)
-    a = _host_array(column)
-    if a.dtype.kind == "i":
-        return np.ascontiguousarray(a.reshape(-1), dtype=np.int64)
-    try:
-        return np.ascontiguousarray(a.astype("datetime64[ns]").reshape(-1)).view(np.int64)
-    except (ValueError, TypeError) as e:
-        raise ValueError(f"cannot read a date column of dtype {a.dtype} as datetimes: {e}") from None
-
-
 def to_cells(column: Any) -> np.ndarray | torch.Tensor:
     """``spatial_index`` as int64.  An integer column is taken as it is; a float column must hold whole numbers, its missing
     (non-finite) entries become -1, which no grid has: ``groupby`` drops them in the reference."""
@@ -145,7 +123,7 @@ def to_cells(column: Any) -> np.ndarray | torch.Tensor:
         if bool((ok & (c != torch.floor(c))).any()):
             raise ValueError("spatial_index holds values that are not whole numbers")
         return torch.where(ok, c, torch.full_like(c, -1.0)).to(torch.int64)
-    a = _host_array(column).reshape(-1)
+    a = host_array(column).reshape(-1)
     if a.dtype.kind in "iu":
         return np.ascontiguousarray(a, dtype=np.int64)
     try:
@@ -168,10 +146,10 @@ def to_values(columns: Any) -> np.ndarray | torch.Tensor:
     columns = list(columns)
     if any(isinstance(c, torch.Tensor) for c in columns):
         dev = next(c.device for c in columns if isinstance(c, torch.Tensor))
-        rows = [c if isinstance(c, torch.Tensor) else torch.from_numpy(np.asarray(_host_array(c), dtype=np.float64)) for c in columns]
+        rows = [c if isinstance(c, torch.Tensor) else torch.from_numpy(np.asarray(host_array(c), dtype=np.float64)) for c in columns]
         return torch.stack([r.reshape(-1).to(device=dev, dtype=torch.float64) for r in rows])
     try:
-        rows = [np.asarray(_host_array(c), dtype=np.float64).reshape(-1) for c in columns]
+        rows = [np.asarray(host_array(c), dtype=np.float64).reshape(-1) for c in columns]
     except (ValueError, TypeError) as e:
         raise ValueError(f"value columns must be numeric (they are read as float64): {e}") from None
     if len({r.size for r in rows}) > 1:
@@ -190,11 +168,6 @@ def unique_in_order(ns: np.ndarray | torch.Tensor) -> np.ndarray:
         return uniq[torch.argsort(first)].cpu().numpy()
     uniq, first = np.unique(ns, return_index=True)
     return uniq[np.argsort(first, kind="stable")]
-
-
-def _device(x: np.ndarray | torch.Tensor, dev: torch.device) -> torch.Tensor:
-    t = torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x
-    return t.to(dev).contiguous()
 
 
 def _prepare(date_ns, cell, values, target_ns, window, freq, weight, dev):
@@ -261,7 +234,7 @@ def nearest_grid_index(grid_lat: np.ndarray, grid_lon: np.ndarray, lat: Any, lon
     from .interp import device_knn
 
     def plane(a: Any, b: Any) -> np.ndarray:
-        a, b = (np.asarray(_host_array(x), dtype=np.float64).reshape(-1) for x in (a, b))
+        a, b = (np.asarray(host_array(x), dtype=np.float64).reshape(-1) for x in (a, b))
         return np.column_stack([a / 512.0, b / 512.0, np.zeros_like(a)])
 
     grid, points = plane(grid_lat, grid_lon), plane(lat, lon)
@@ -305,7 +278,7 @@ def key_codes(column: Any) -> tuple[np.ndarray | torch.Tensor, np.ndarray | torc
         codes = torch.zeros(c.numel(), dtype=torch.int64, device=c.device)
         codes[ok] = torch.unique(c[ok], return_inverse=True)[1]
         return codes, ok
-    a = _host_array(column).reshape(-1)
+    a = host_array(column).reshape(-1)
     if a.dtype.kind in "iub":
         return np.ascontiguousarray(a, dtype=np.int64), None
     if a.dtype.kind == "M":
@@ -400,18 +373,6 @@ def group_nearest(distance: torch.Tensor, groups: Groups) -> torch.Tensor:
 FORCINGS = native.FORCINGS  # the nine names in the order of R: add_forcings.py:51-61, which is the order of the kernel's mask bits
 
 
-def float_column(column: Any, dev: torch.device) -> torch.Tensor:
-    """A numeric column as a contiguous float64 device row (a device tensor is used in place when it already is one)."""
-    if isinstance(column, torch.Tensor):
-        if column.dtype.is_complex or column.dtype == torch.bool:
-            raise ValueError(f"a numeric column is needed, got {column.dtype}")
-        return column.reshape(-1).to(device=dev, dtype=torch.float64).contiguous()
-    a = _host_array(column)
-    if a.dtype.kind not in "iuf":
-        raise ValueError(f"a numeric column is needed, got dtype {a.dtype}")
-    return _device(np.ascontiguousarray(a.reshape(-1), dtype=np.float64), dev)
-
-
 def forcings(date: Any, latitude: Any, longitude: Any, columns: Sequence[str], dev: torch.device | None = None) -> dict[str, torch.Tensor]:
     """``{name: float64 device row}`` for the forcing names in ``columns`` (a subset of ``FORCINGS``), in the order given
     (R: add_forcings.py:68-127, support/compute_forcings.py:14-87) — ONE launch of ``atx_obs_forcings``; julian day, hours since
@@ -464,7 +425,7 @@ def meteosat_position(satellite_id: Any, date: Any, dev: torch.device | None = N
     store 41.5 / 45.5 / -3.4 as 41 / 45 / -3, and the reference's literals depend on it.  The date comparisons are strict; NaT and
     unknown ids give 0."""
     dev = _stack.device() if dev is None else dev
-    ids = satellite_id if isinstance(satellite_id, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(_host_array(satellite_id)))
+    ids = satellite_id if isinstance(satellite_id, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(host_array(satellite_id)))
     ids = ids.reshape(-1).to(dev)
     ns = _device(to_ns(date), dev)
     if ids.numel() != ns.numel():
@@ -513,7 +474,7 @@ FILL_SENTINEL = 9999.0  # R: fill_heights.py:80 — a station altitude of exactl
 
 
 def _check_axis(name: str, axis: Any) -> np.ndarray:
-    a = np.asarray(_host_array(axis))
+    a = np.asarray(host_array(axis))
     if a.ndim != 1 or a.size == 0:
         raise ValueError(f"orography {name} axis must be 1-D and non-empty, got shape {a.shape}")
     if a.dtype.kind not in "iuf":
@@ -550,7 +511,7 @@ class HeightGrid:
             dev = heights.device if heights.is_cuda else (_stack.device() if dev is None else dev)
             self.heights = heights.to(dev)
         else:
-            h = np.asarray(_host_array(heights))
+            h = np.asarray(host_array(heights))
             if h.dtype.kind not in "iuf":
                 raise ValueError(f"orography heights must be numeric, got dtype {h.dtype}")
             h = np.ascontiguousarray(h, dtype=h.dtype if h.dtype in (np.float32, np.float64) else np.float64)
@@ -642,17 +603,6 @@ class IntegerAbs(NamedTuple):
     source: str
 
 
-def _dtype_kind(dtype: Any) -> str:
-    """numpy's kind letter of a numpy or torch dtype: b, i, u, f, c — anything else is not numeric."""
-    if isinstance(dtype, torch.dtype):
-        if dtype == torch.bool:
-            return "b"
-        if dtype.is_complex:
-            return "c"
-        return "f" if dtype.is_floating_point else ("u" if str(dtype).startswith("torch.uint") else "i")  # uint8, uint16, uint32, uint64
-    return np.dtype(dtype).kind
-
-
 def compile_column_program(spec: Sequence[tuple[str, str, str]], dtypes: Mapping[str, Any]) -> list[KernelStep | IntegerAbs]:
     """The ordered transformations ``[(target, source, function), ...]`` over a table whose columns have the (numpy or torch)
     ``dtypes``, as the steps that compute them: pure host logic.
@@ -698,7 +648,7 @@ def compile_column_program(spec: Sequence[tuple[str, str, str]], dtypes: Mapping
 def column_dtypes(columns: Mapping[str, Any], spec: Sequence[tuple[str, str, str]]) -> dict[str, Any]:
     """The dtypes of the columns of the table that ``spec`` names as sources (``compile_column_program``'s second argument)."""
     names = {source for _, source, _ in spec} & set(columns.keys())
-    return {name: (columns[name].dtype if isinstance(columns[name], torch.Tensor) else _host_array(columns[name]).dtype) for name in names}
+    return {name: (columns[name].dtype if isinstance(columns[name], torch.Tensor) else host_array(columns[name]).dtype) for name in names}
 
 
 def column_ops(columns: Mapping[str, Any], spec: Sequence[tuple[str, str, str]], dev: torch.device | None = None) -> dict[str, torch.Tensor]:
@@ -712,9 +662,7 @@ def column_ops(columns: Mapping[str, Any], spec: Sequence[tuple[str, str, str]],
     never written: every target, one equal to its source included, is a fresh row."""
     spec = [tuple(item) for item in spec]
     steps = compile_column_program(spec, column_dtypes(columns, spec))  # the host's errors come before anything touches the device
-    if dev is None:  # where the table's device tensors are, else this process's device
-        held = (columns[name] for name in columns.keys())
-        dev = next((c.device for c in held if isinstance(c, torch.Tensor) and c.is_cuda), None) or _stack.device()
+    dev = launch_device((columns[name] for name in columns.keys()), dev)
     current: dict[str, Any] = {}  # the targets written so far
     as_float: dict[str, torch.Tensor] = {}  # float64 device rows of the columns read so far
 
@@ -727,7 +675,7 @@ def column_ops(columns: Mapping[str, Any], spec: Sequence[tuple[str, str, str]],
         if isinstance(step, IntegerAbs):
             col = current[step.source] if step.source in current else columns[step.source]
             if not isinstance(col, torch.Tensor):
-                col = torch.from_numpy(np.ascontiguousarray(_host_array(col)).reshape(-1))
+                col = torch.from_numpy(np.ascontiguousarray(host_array(col)).reshape(-1))
             col = col.reshape(-1).to(dev)
             # an unsigned column is its own absolute value (torch has no abs for most unsigned types)
             written = {step.target: col.clone() if _dtype_kind(col.dtype) == "u" else torch.abs(col)}
@@ -755,7 +703,7 @@ def _host_ranks(column: Any) -> np.ndarray:
     if hasattr(column, "cat"):
         codes = np.asarray(column.cat.codes, dtype=np.int64)
         return np.where(codes < 0, len(column.cat.categories), codes)
-    a = _host_array(column).reshape(-1)
+    a = host_array(column).reshape(-1)
     try:
         try:
             import pandas as pd
@@ -796,15 +744,15 @@ def order_keys(column: Any, dev: torch.device | None = None, *, datetime: bool =
             c = c.to(torch.int64)
         elif c.dtype not in native.KEY_DTYPES:
             raise ValueError(f"a {c.dtype} column has no int64 order key")
-        dev = c.device if c.is_cuda else (_stack.device() if dev is None else dev)
+        dev = launch_device([c], None if c.is_cuda else dev)  # a device tensor is used where it is
         c = c.to(dev).contiguous()
     else:
-        dev = _stack.device() if dev is None else dev
-        a = None if hasattr(column, "cat") else _host_array(column).reshape(-1)
+        dev = launch_device((), dev)
+        a = None if hasattr(column, "cat") else host_array(column).reshape(-1)
         if a is None or a.dtype.kind not in "iufbMm":
             a = _host_ranks(column)
         elif a.dtype.kind in "Mm":
-            a = np.ascontiguousarray(a.astype(f"{'datetime64' if a.dtype.kind == 'M' else 'timedelta64'}[ns]")).view(np.int64)
+            a = datetime_ns(a)
             code = native.KEY_DATETIME
         elif a.dtype.kind == "u" and a.dtype.itemsize == 8:
             raise ValueError("a uint64 column has no int64 order key")
@@ -828,28 +776,12 @@ def _row_keys(columns: Sequence[Any], dev: torch.device | None, datetimes: Seque
     columns = list(columns)
     if not columns:
         raise ValueError("at least one key column")
-    if dev is None:
-        dev = next((c.device for c in columns if isinstance(c, torch.Tensor) and c.is_cuda), None) or _stack.device()
+    dev = launch_device(columns, dev)
     flags = [False] * len(columns) if datetimes is None else list(datetimes)
     keys = [order_keys(c, dev, datetime=bool(f)) for c, f in zip(columns, flags)]
     if len({k.numel() for k in keys}) > 1:
         raise ValueError(f"key columns differ in length: {[k.numel() for k in keys]}")
     return keys
-
-
-def _take(columns: Sequence[torch.Tensor], rows: torch.Tensor, check: bool = True) -> list[torch.Tensor]:
-    """``[c[rows] for c in columns]`` for contiguous device rows of equal length: one launch of ``atx_obs_take_rows`` per 16 columns."""
-    columns = list(columns)
-    step = native.MAX_ROWSET_COLUMNS
-    outs = [torch.empty(rows.numel(), dtype=c.dtype, device=rows.device) for c in columns]
-    n_bad = torch.zeros(max((len(columns) + step - 1) // step, 1), dtype=torch.int64, device=rows.device)
-    for j in range(0, len(columns), step):
-        native.obs_take_rows(columns[j:j + step], outs[j:j + step], rows, n_bad[j // step:j // step + 1])
-    if check and columns and rows.numel():
-        bad = int(n_bad[0])  # every launch of the call sees the same rows
-        if bad:
-            raise IndexError(f"take_rows: {bad} of {rows.numel()} row indices lie outside the table's {columns[0].numel()} rows")
-    return outs
 
 
 def _sort_keys(keys: Sequence[torch.Tensor]) -> torch.Tensor:
@@ -889,31 +821,3 @@ def first_rows(columns: Sequence[Any], dev: torch.device | None = None, *, datet
     for j in range(0, len(keys), native.MAX_ROWSET_COLUMNS):
         native.obs_mark_first(keys[j:j + native.MAX_ROWSET_COLUMNS], order, keep, accumulate=j > 0)
     return torch.nonzero(keep).reshape(-1)
-
-
-def take_rows(columns: Mapping[str, Any], rows: Any, dev: torch.device | None = None) -> dict[str, torch.Tensor]:
-    """``{name: column[rows]}`` as device tensors — one launch of ``atx_obs_take_rows`` per 16 columns, the row list read once per row
-    for all of them.  Dtypes are kept (anything of 1, 2, 4 or 8 bytes per element); datetime64 columns come back as int64
-    nanoseconds.  numpy columns are uploaded, device tensors used in place; ``rows``: int64 positions, array or tensor, in any order and
-    with repeats.  A position outside the table raises ``IndexError`` with the count (synchronises; the kernel reads nothing through it)."""
-    if dev is None:
-        held = [c for c in (*columns.values(), rows) if isinstance(c, torch.Tensor) and c.is_cuda]
-        dev = held[0].device if held else _stack.device()
-    rows = _device(rows if isinstance(rows, torch.Tensor) else np.asarray(rows, dtype=np.int64), dev).reshape(-1)
-    if rows.dtype != torch.int64:
-        raise ValueError(f"row positions must be int64, got {rows.dtype}")
-    cols = {}
-    for name, col in columns.items():
-        if not isinstance(col, torch.Tensor):
-            a = _host_array(col).reshape(-1)
-            if a.dtype.kind in "Mm":
-                a = np.ascontiguousarray(a.astype(f"{'datetime64' if a.dtype.kind == 'M' else 'timedelta64'}[ns]")).view(np.int64)
-            elif a.dtype.kind not in "iufbc":
-                raise ValueError(f"column {name!r} of dtype {a.dtype} cannot live on the device")
-            col = torch.from_numpy(np.ascontiguousarray(a))
-        if col.element_size() not in (1, 2, 4, 8):
-            raise ValueError(f"column {name!r}: elements of {col.element_size()} bytes (1, 2, 4 or 8 are taken)")
-        cols[name] = col.reshape(-1).to(dev).contiguous()
-    if len({c.numel() for c in cols.values()}) > 1:
-        raise ValueError(f"columns differ in length: { {name: c.numel() for name, c in cols.items()} }")
-    return dict(zip(cols, _take(list(cols.values()), rows)))

@@ -278,3 +278,29 @@ def test_a_chain_of_device_tensors_stays_on_the_device_and_equals_pandas(dev):
         want = frame[name].to_numpy()
         want = want.view(np.int64) if want.dtype.kind == "M" else want
         assert R.same_bits(got[name].cpu().numpy(), want), name
+
+
+@pytest.mark.parametrize("n", [1, 257])
+def test_table_take_gathers_what_can_live_on_the_device_and_indexes_the_rest_on_the_host(dev, monkeypatch, n):
+    """``Table.take`` on a resident mapping of 18 numeric columns and one of strings: the numeric ones come back as device tensors from
+    two launches, the strings as a numpy array, all of it numpy's indexing — for rows with repeats and for descending rows."""
+    from anemoi_transform_amd.tables import Table
+
+    rng = np.random.default_rng(400 + n)
+    host = {f"c{c}": col for c, col in enumerate(_columns(n, 18, rng))}
+    host = {**dict(list(host.items())[:5]), "name": np.array(R.NAME_POOL, dtype=object)[rng.integers(0, len(R.NAME_POOL), n)], **dict(list(host.items())[5:])}
+    resident = _as_resident(host, dev)
+    calls = []
+    real = native.obs_take_rows
+    monkeypatch.setattr(native, "obs_take_rows", lambda cols, outs, rows, n_bad: (calls.append(len(cols)), real(cols, outs, rows, n_bad))[1])
+    for rows in (rng.integers(0, n, n + 7).astype(np.int64), np.arange(n, dtype=np.int64)[::-1].copy()):
+        del calls[:]
+        got = Table(resident).take(_up(rows, dev))
+        assert calls == [16, 2] and got is not resident and list(got) == list(host) and list(resident) == list(host)
+        assert isinstance(got["name"], np.ndarray) and R.same_bits(got["name"], host["name"][rows])
+        for name, col in host.items():
+            if name != "name":
+                assert got[name].is_cuda and got[name].dtype == resident[name].dtype and R.same_bits(got[name].cpu().numpy(), col[rows]), (n, name)
+    del calls[:]
+    part = Table(resident).take(_up(rows, dev), names=["name", "c17", "c0"])
+    assert calls == [2] and list(part) == ["name", "c17", "c0"] and R.same_bits(part["c17"].cpu().numpy(), host["c17"][rows])

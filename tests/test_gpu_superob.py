@@ -240,3 +240,108 @@ def test_two_million_rows():
         rows_out = np.array(rows_out)
         assert (rows_out >= 0).all()
         np.testing.assert_array_equal(_bits(got[name][rows_out]), _bits(want), err_msg=name)
+
+
+# ---- rows are taken as sort_by takes them: one gather per row set ------------------------------------------------------------------------
+NEAREST_DTYPES = (np.float64, np.float32, np.int32, np.int16, np.uint8, np.bool_)
+WIDE_NEAREST = [f"near_{j}" for j in range(17)]
+WIDE_CONFIG = dict(grid="5/5", timeslot_length=3600, columns_to_take_nearest=WIDE_NEAREST, columns_to_groupby=["network", "kind"])
+
+
+def _wide_table(n: int, missing: bool) -> dict:
+    """23 columns: date (averaged), latitude, longitude, two group keys, one value and 17 columns taken from the nearest row, of which
+    ``near_0`` is the row's own number — where every taken value came from."""
+    rng = np.random.default_rng(1000 + n)
+    n_sites = max(2, n // 6)
+    site = rng.integers(0, n_sites, n)
+    table = {"date": np.datetime64("2025-01-01T00:00:00", "ns") + rng.integers(0, 3 * 3600, n) * np.timedelta64(10**9, "ns"),
+             "latitude": rng.uniform(-80, 80, n_sites)[site] + rng.uniform(-0.3, 0.3, n),
+             "longitude": rng.uniform(-170, 170, n_sites)[site] + rng.uniform(-0.3, 0.3, n),
+             "network": rng.integers(0, 3, n), "kind": rng.integers(0, 2, n).astype(np.int32), "value": rng.normal(280.0, 30.0, n),
+             "near_0": np.arange(n, dtype=np.float64)}
+    for j in range(1, 17):
+        dtype = NEAREST_DTYPES[j % len(NEAREST_DTYPES)]
+        table[f"near_{j}"] = rng.random(n) < 0.5 if dtype is np.bool_ else rng.integers(0, 120, n).astype(dtype)
+    if missing:
+        table["latitude"][n // 2] = np.nan
+    assert len(table) == 23 and {table[c].dtype.type for c in WIDE_NEAREST} == set(NEAREST_DTYPES)
+    return table
+
+
+def _equal_to_the_device_result(host: dict, device: dict) -> None:
+    assert list(host) == list(device)
+    for name in host:
+        h, d = np.asarray(host[name]), device[name].cpu().numpy()
+        if h.dtype.kind == "M":  # datetimes are int64 nanoseconds on the device
+            assert h.dtype == np.dtype("datetime64[ns]") and d.dtype == np.int64, name
+            h = h.view(np.int64)
+        assert h.dtype == d.dtype and np.array_equal(h, d, equal_nan=h.dtype.kind == "f"), name
+
+
+@pytest.mark.parametrize("missing", [False, True], ids=["complete", "a_row_without_latitude"])
+@pytest.mark.parametrize("n", [1, 255, 256, 257, 513])
+def test_rows_are_gathered_per_row_set_and_host_tables_launch_no_gather(monkeypatch, n, missing):
+    """A device table is gathered by ``atx_obs_take_rows``, one launch per 16 columns and row set: the 17 nearest-row columns in two,
+    the two group keys in one, and — only where a row lacks its latitude — the 23 columns of the first-stage drop in two.  A host
+    mapping and a DataFrame launch none, and hold the device's values."""
+    from anemoi_transform_amd import native
+
+    pd = pytest.importorskip("pandas")
+    table = _wide_table(n, missing)
+    want = _restated(table, WIDE_CONFIG)
+    n_out = len(want["date"])
+    assert n_out == 0 if (n == 1 and missing) else 0 < n_out <= n - missing
+    resident = _on_device(table)
+    calls = []
+    real = native.obs_take_rows
+    monkeypatch.setattr(native, "obs_take_rows", lambda cols, outs, rows, n_bad: (calls.append((len(cols), rows.numel())), real(cols, outs, rows, n_bad))[1])
+    f = create_filter_by_name("superob", **WIDE_CONFIG)
+    got = f(resident)
+    drop = [(16, n - 1), (7, n - 1)] if missing else []
+    assert calls == drop + ([(2, n_out), (16, n_out), (1, n_out)] if n_out else [])
+    assert all(isinstance(v, torch.Tensor) and v.is_cuda and v.numel() == n_out for v in got.values())
+    if n_out:
+        assert list(got) == list(want) == ["network", "kind", "date", "latitude", "longitude", "value", "spatial_index"] + WIDE_NEAREST
+        rows = torch.from_numpy(want["near_0"].astype(np.int64)).cuda()  # the nearest row of every group, in the output's order
+        for name in ["network", "kind"] + WIDE_NEAREST:
+            assert got[name].dtype == resident[name].dtype and torch.equal(got[name], resident[name][rows]), name
+        for name in want:
+            np.testing.assert_array_equal(_bits(got[name].cpu().numpy()), _bits(want[name]), err_msg=name)
+    else:
+        assert list(got) == list(table)
+    del calls[:]
+    _equal_to_the_device_result(f(table), got)
+    frame = f(pd.DataFrame(table))
+    _equal_to_the_device_result({c: frame[c].to_numpy() for c in frame.columns}, got)
+    assert calls == []
+
+
+def test_a_chain_from_raw_rows_to_the_stack_stays_on_the_device():
+    """``superob | add_forcings | sort_by | drop_duplicates | irregular_to_grid`` on device tensors: every table on the way is device
+    tensors, the fields are levels of one stack in HBM, and they equal the same chain fed the host mapping."""
+    rng = np.random.default_rng(43)
+    table, _ = R.random_table(7004, n=1500)
+    table = {k: table[k] for k in ("date", "latitude", "longitude", "wide", "near")}
+    table["window_date"] = np.datetime64("2025-01-01T00:00:00", "ns") + rng.integers(1, 4, 1500) * np.timedelta64(3600 * 10**9, "ns")
+    chain = [create_filter_by_name("superob", grid="5/5", timeslot_length=1800, columns_to_take_nearest=["date"], columns_to_groupby=["window_date"]),
+             create_filter_by_name("add_forcings", columns=["cos_sza", "sin_julian_day"]),
+             create_filter_by_name("sort_by", columns=["spatial_index", "date"]),
+             create_filter_by_name("drop_duplicates", columns=["spatial_index", "window_date"])]
+    to_grid = create_filter_by_name("irregular_to_grid", window_date_column="window_date", columns=["wide", "cos_sza"], time_freq="1h", grid="5/5",
+                                    window="(-3h, +3h]")
+    resident, host = _on_device(table), dict(table)
+    sizes = []
+    for f in chain:
+        resident, host = f(resident), f(host)
+        assert all(isinstance(v, torch.Tensor) and v.is_cuda for v in resident.values()), repr(f)
+        assert all(isinstance(v, np.ndarray) for v in host.values()), repr(f)
+        _equal_to_the_device_result(host, resident)
+        sizes.append(len(host["date"]))
+    assert 100 < sizes[3] < sizes[2] == sizes[0] < 1500  # superob and drop_duplicates both thinned the table
+    fields, want = to_grid(resident), to_grid(host)
+    assert len(fields) == len(want) == 3 * 2
+    stacks = {id(f.stack_ref()[0]): f.stack_ref()[0] for f in fields}
+    assert len(stacks) == 1 and next(iter(stacks.values())).data.is_cuda  # one stack, in HBM
+    for got, expected in zip(fields, want):
+        a = got.to_numpy(flatten=True)
+        assert np.isfinite(a).sum() > 20 and np.array_equal(a, expected.to_numpy(flatten=True), equal_nan=True)
