@@ -17,17 +17,12 @@
 // refuses an unroll pragma here, so there is none) and addresses `r[]` through the VGPR index register: 114 VGPRs, no scratch.
 // That is this compiler's choice, not something the source can force: tools/kernel_resources.py reads it from the code object and
 // tests/test_host_api.py::test_no_streaming_kernel_uses_scratch_memory fails the build that decides otherwise.
+//
+// The entry point carries a second family of codes, ATX_COLOP_SCALAR and above: the compares, selects and row predicates of the tabular
+// QC filters (atx_obs_row_program.hip).  A program is of one family; the check below decides which kernel runs.
 #include "atx_obs_rows.hpp"
 
 namespace atx {
-
-struct ColumnProgram {
-    const double* in[ATX_MAX_COLUMN_OPS];
-    double* out[ATX_MAX_COLUMN_OPS];
-    int32_t op[ATX_MAX_COLUMN_OPS];  // dwords: a scalar load can fetch them at a run-time index, a byte needs a vector load
-    int32_t src[ATX_MAX_COLUMN_OPS];
-    int32_t n_ops;
-};
 
 __device__ __forceinline__ double column_op(int op, double x) {
     switch (op) {
@@ -81,11 +76,20 @@ extern "C" int atx_obs_column_ops(int32_t n_ops, const int32_t* op, const int32_
     ATX_REQUIRE(op && src && in && out, ATX_EINVAL, "atx_obs_column_ops: null program array");
     ColumnProgram p = {};
     p.n_ops = n_ops;
+    const bool rows = op[0] >= ATX_COLOP_SCALAR;  // the family of the program: library functions, or the row operations of the QC filters
     for (int t = 0; t < n_ops; ++t) {
-        ATX_REQUIRE(op[t] >= ATX_COLOP_LOG && op[t] <= ATX_COLOP_COS_DEG, ATX_EINVAL, "atx_obs_column_ops: operation %d has the unknown code %d", t,
-                    (int)op[t]);
+        ATX_REQUIRE((op[t] >= ATX_COLOP_LOG && op[t] <= ATX_COLOP_COS_DEG) || (op[t] >= ATX_COLOP_SCALAR && op[t] <= ATX_COLOP_FILL_NAN), ATX_EINVAL,
+                    "atx_obs_column_ops: operation %d has the unknown code %d", t, (int)op[t]);
+        ATX_REQUIRE((op[t] >= ATX_COLOP_SCALAR) == rows, ATX_EINVAL,
+                    "atx_obs_column_ops: operation %d (code %d) mixes the two families: a program is all codes 0 .. %d or all codes %d .. %d", t,
+                    (int)op[t], (int)ATX_COLOP_COS_DEG, (int)ATX_COLOP_SCALAR, (int)ATX_COLOP_FILL_NAN);
         ATX_REQUIRE(src[t] < t, ATX_EINVAL, "atx_obs_column_ops: operation %d takes the result of operation %d, which is not an earlier one", t,
                     (int)src[t]);
+        ATX_REQUIRE(op[t] != ATX_COLOP_SCALAR || src[t] < 0, ATX_EINVAL,
+                    "atx_obs_column_ops: operation %d is a SCALAR and reads in[%d][0]: its src must be -1, got %d", t, t, (int)src[t]);
+        ATX_REQUIRE(op[t] < ATX_COLOP_CMP_GT || t > 0, ATX_EINVAL,
+                    "atx_obs_column_ops: operation %d (code %d) is binary: its second operand is the result of the operation before it, and there is none",
+                    t, (int)op[t]);
         ATX_REQUIRE(src[t] >= 0 || in[t] || n == 0, ATX_EINVAL, "atx_obs_column_ops: operation %d reads a null column", t);
         p.op[t] = op[t];
         p.src[t] = src[t] < 0 ? -1 : src[t];
@@ -93,6 +97,7 @@ extern "C" int atx_obs_column_ops(int32_t n_ops, const int32_t* op, const int32_
         p.out[t] = out[t];
     }
     if (n == 0) return ATX_OK;
+    if (rows) return launch_obs_row_program(p, n, static_cast<hipStream_t>(stream));
     hipLaunchKernelGGL(obs_column_ops_kernel, dim3(row_grid(n)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), p, n);
     ATX_LAUNCH_CHECK("obs_column_ops");
     return ATX_OK;

@@ -15,25 +15,31 @@ Registered names:
                   fill_orography, geopotential_to_height_tabular, apply_column_transformations
                                                              (per-row columns, filters/tabular.py)
                   sort_by, drop_duplicates, drop             (row sets on the device / column bookkeeping, filters/tabular.py)
+                  mask_tabular, mask_outside_range, mask_infs, mask_dewpoint_temperature, exclude_dates,
+                  remove_extreme_values, clip_tabular, impute_nans_tabular, drop_nans_tabular
+                                                             (QC: masking, clipping, filling, dropping rows; filters/tabular.py)
                   rename_fields, clear_step, repeat_members, earthkitfieldlambda, empty,
                   icon_refinement_level   (re-labelling / re-listing, filters/metadata.py)
   dispatchers     mask (alias apply_mask), remove_nans (alias drop_nans),
                   geopotential_to_height (alias orog_to_z), height_to_geopotential (alias z_to_orog),
                   clip (alias clipper), impute_nans (alias replace_nans), rename
 
-The dispatchers pick the field filter from the configuration keys exactly as the
-reference does; configurations that select the *tabular* (pandas) half of a
-dispatcher raise ``NotImplementedError`` — except ``geopotential_to_height``,
-whose tabular half is built: given a DataFrame or a plain mapping of columns it
-calls ``geopotential_to_height_tabular`` with its ``geopotential`` and ``height``
-keys (``height`` defaults to ``"orog"`` there, as in the reference).
+The dispatchers pick the field or the tabular filter from the configuration keys exactly
+as the reference does; given a DataFrame — or a plain mapping of columns — ``mask``,
+``clip``, ``impute_nans`` and ``remove_nans`` call ``mask_tabular``, ``clip_tabular``,
+``impute_nans_tabular`` and ``drop_nans_tabular``, and ``geopotential_to_height`` calls
+``geopotential_to_height_tabular`` with its ``geopotential`` and ``height`` keys
+(``height`` defaults to ``"orog"`` there, as in the reference).  A configuration that
+belongs to the other half raises the reference's "Ambiguous config" ``ValueError``.
+``rename`` alone still raises ``NotImplementedError`` for its tabular half.
 Observations enter the field path through ``irregular_to_grid`` (with
 ``assign_to_grid`` before it): a table goes to the device once and comes out as
 one HBM stack of gridded fields.  ``sort_by`` and ``drop_duplicates`` reorder and
 thin a table by pandas' order and equality on the device, ``drop`` removes columns,
-so a chain that needs them stays a mapping of device tensors.  The rest of the
-reference's tabular family is row-dropping, renaming and masking bookkeeping in
-pandas with no field output and stays out.
+and the nine QC filters mask, clip, fill and drop rows with one program of compares
+and selects per row, so a chain that needs them stays a mapping of device tensors.
+``filter_query``, ``mask_values_custom``, ``encode_statids`` and the tabular ``rename``
+stay out.
 """
 
 from __future__ import annotations
@@ -54,38 +60,46 @@ from . import tabular as _tabular_filters  # noqa: E402
 from . import winds as _winds  # noqa: E402
 from .masks import MaskVariable, RemoveNaNs as RemoveNaNsFields
 from .pointwise import Clipper, ImputeNaNs as ImputeNaNsFields, Orography
-from .tabular import GeopotentialToHeightTabular
+from .tabular import ClipTabular, DropNaNsTabular, GeopotentialToHeightTabular, ImputeNaNsTabular, MaskValues
 
 
-def _tabular(name: str) -> NotImplementedError:
-    return NotImplementedError(
-        f"'{name}': this configuration selects the tabular (pandas DataFrame) filter of the reference, "
-        "which is outside the gridded-field hot path this package implements"
-    )
+class _TableFallback:
+    """A table is a DataFrame or a plain mapping name -> column (filters/tabular.py): the mapping takes the tabular half too."""
+
+    def forward_fallback(self, data: Any) -> Any:
+        if isinstance(data, Mapping):
+            return self.forward_tabular(data)
+        return super().forward_fallback(data)
 
 
-class Mask(DispatchingFilter):
+class Mask(_TableFallback, DispatchingFilter):
     """R: filters/mask.py:19-35."""
 
     def __init__(self, **config: Any) -> None:
         if "path" in config or "mask_param" in config:
             self.filter = MaskVariable(**config)
         else:
-            raise _tabular("mask")
+            self.filter = MaskValues(**config)
 
     def forward_fields(self, data: Any) -> Any:
         return self.filter.forward(data)
 
+    def forward_tabular(self, data: Any) -> Any:
+        return self.filter.forward(data)
 
-class RemoveNaNs(DispatchingFilter):
+
+class RemoveNaNs(_TableFallback, DispatchingFilter):
     """R: filters/remove_nans.py:19-47."""
 
     def __init__(self, **config: Any) -> None:
-        if len(config) == 0:
+        if len(config) == 0:  # valid for both
+            self.tabular_filter = DropNaNsTabular()
             self.field_filter = RemoveNaNsFields()
         elif ("columns" in config) or ("column_prefix" in config) or ("how" in config):
+            self.tabular_filter = DropNaNsTabular(**config)
             self.field_filter = None
         else:
+            self.tabular_filter = None
             self.field_filter = RemoveNaNsFields(**config)
 
     def forward_fields(self, data: Any) -> Any:
@@ -93,8 +107,13 @@ class RemoveNaNs(DispatchingFilter):
             raise ValueError("Ambigious config for RemoveNaNs filter.")
         return self.field_filter.forward(data)
 
+    def forward_tabular(self, data: Any) -> Any:
+        if self.tabular_filter is None:
+            raise ValueError("Ambigious config for RemoveNaNs filter.")
+        return self.tabular_filter.forward(data)
 
-class GeopotentialToHeight(DispatchingFilter):
+
+class GeopotentialToHeight(_TableFallback, DispatchingFilter):
     """R: filters/geopotential_to_height.py:19-47."""
 
     def __init__(self, **config: Any) -> None:
@@ -115,44 +134,49 @@ class GeopotentialToHeight(DispatchingFilter):
     def forward_tabular(self, data: Any) -> Any:
         return self.tabular_filter.forward(data)
 
-    def forward_fallback(self, data: Any) -> Any:
-        # a table is a DataFrame or a plain mapping name -> column (filters/tabular.py)
-        if isinstance(data, Mapping):
-            return self.forward_tabular(data)
-        return super().forward_fallback(data)
-
     def patch_data_request(self, data_request: dict) -> dict:
         return self.field_filter.patch_data_request(data_request)
 
 
-class Clip(DispatchingFilter):
+class Clip(_TableFallback, DispatchingFilter):
     """R: filters/clip.py:19-35."""
 
     def __init__(self, **config: Any) -> None:
         if "param" in config and isinstance(config["param"], str):
             self.filter = Clipper(**config)
         else:
-            raise _tabular("clip")
+            self.filter = ClipTabular(**config)
 
     def forward_fields(self, data: Any) -> Any:
         return self.filter.forward(data)
 
+    def forward_tabular(self, data: Any) -> Any:
+        return self.filter.forward(data)
 
-class ImputeNaNs(DispatchingFilter):
+
+class ImputeNaNs(_TableFallback, DispatchingFilter):
     """R: filters/impute_nans.py:19-49."""
 
     def __init__(self, **config: Any) -> None:
         if len(config) == 0:
-            self.field_filter = ImputeNaNsFields()  # raises like the reference: required inputs are missing
+            self.tabular_filter = ImputeNaNsTabular()  # raises like the reference: required inputs are missing
+            self.field_filter = ImputeNaNsFields()
         elif ("columns" in config) or ("column_prefix" in config):
+            self.tabular_filter = ImputeNaNsTabular(**config)
             self.field_filter = None
         else:
+            self.tabular_filter = None
             self.field_filter = ImputeNaNsFields(**config)
 
     def forward_fields(self, data: Any) -> Any:
         if self.field_filter is None:
             raise ValueError("Ambiguous config for ImputeNaNs field filter.")
         return self.field_filter.forward(data)
+
+    def forward_tabular(self, data: Any) -> Any:
+        if self.tabular_filter is None:
+            raise ValueError("Ambiguous config for ImputeNans tabular filter.")
+        return self.tabular_filter.forward(data)
 
 
 filter_registry.register("mask", Mask, aliases=["apply_mask"])

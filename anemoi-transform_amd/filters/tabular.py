@@ -27,6 +27,13 @@ order: ``obs.sort_order`` -> ``atx_obs_order_key`` and the library's stable radi
 group of equal key tuples: ``obs.first_rows`` -> ``atx_obs_mark_first``) — both end in ONE gather of every column
 (``obs.take_rows`` -> ``atx_obs_take_rows``) — and ``drop`` (columns leave; host bookkeeping, nothing is copied).
 
+The QC filters mask, clip, fill and drop rows where recipes do it between those steps: ``mask_tabular``, ``mask_outside_range``,
+``mask_infs``, ``mask_dewpoint_temperature``, ``exclude_dates``, ``remove_extreme_values``, ``clip_tabular``, ``impute_nans_tabular`` and
+``drop_nans_tabular``.  Each compiles its configuration and the column dtypes into a program of compares and selects per row
+(``obs.compile_*`` -> ``obs.row_program`` / ``obs.keep_rows`` -> ``atx_obs_column_ops``' second family of codes, up to 16 slots a launch); the
+row-dropping ones end in one gather of every column (``Table.take``).  What comes back is pandas' to the bit and to the dtype: a float32
+column is compared in float32 and stays float32, an integer column turns float64 only where a row was masked.
+
 A table is a pandas DataFrame or a plain mapping ``name -> 1-D array / device tensor``.  Every ``forward`` wraps it in
 ``tables.Table``, which is where the table rule lives: which columns there are, where the launch runs, which columns are datetimes
 and what goes back to the caller — a DataFrame for a DataFrame, a new dict of device tensors if any column was a tensor, else of
@@ -56,7 +63,11 @@ Deviations from the reference, each said once when it first matters (``core.say_
   * ``sort_by``: a key column that cannot be ordered raises ``ValueError`` (the reference logs the error and returns the frame
     UNSORTED); an int64 device tensor named ``date`` is nanoseconds with NaT, as everywhere in this module.
   * ``sort_by`` / ``drop_duplicates``: a uint64 key column raises ``ValueError`` (it has no int64 key); the caller's table is not modified.
-The other tabular filters of the reference (the remaining row-dropping, renaming and masking bookkeeping in pandas) are not built:
+  * the QC filters: the caller's table is not modified; columns are read as float64 (exact for float32 and for integers below 2^53,
+    beyond which nothing is specially handled); a bool column raises ``ValueError``; ``mask_outside_range`` with ``[None, None]`` leaves
+    the column as it is (the reference raises) and raises ``ValueError`` for a missing column (the reference: ``KeyError``);
+    ``impute_nans_tabular`` cannot fill a datetime or string column of a mapping (``ValueError``; a DataFrame's goes through pandas).
+The other tabular filters of the reference (``filter_query``, ``mask_values_custom``, ``encode_statids``, the tabular ``rename``) are not built:
 DESIGN.md §7.
 """
 
@@ -760,6 +771,393 @@ class Drop(Filter):
         return t.without(self.columns)
 
 
+# ---- QC: masking, clipping, filling and dropping rows on the row-program kernel ----------------------------------------------------------
+def _qc_note(kind: type) -> None:
+    say_once(LOG, (kind, "table"), "%s: the caller's table is not modified (the reference writes into its argument); columns are read as "
+             "float64 — exact for float32 and for integers below 2^53, beyond which nothing is specially handled", kind.__name__,
+             level=logging.INFO)
+
+
+def _dtypes(t: Table, names: Any) -> dict[str, Any]:
+    return {name: (t[name].dtype if isinstance(t[name], torch.Tensor) else host_array(t[name]).dtype) for name in names}
+
+
+def _torch_dtype(dtype: Any) -> torch.dtype:
+    return dtype if isinstance(dtype, torch.dtype) else torch.from_numpy(np.empty(0, dtype=dtype)).dtype
+
+
+def _narrowed(rows: dict[str, torch.Tensor], dtypes: dict[str, Any], integers: str) -> dict[str, torch.Tensor]:
+    """The float64 result rows in the dtypes pandas hands back.  A float column keeps its dtype (the cast back is exact: every value is
+    one of the column's own, a NaN, or a scalar rounded to the column's precision first).  An integer column, ``integers="nan"``: its
+    own dtype and the caller's values — it is left out — when no row was masked, float64 otherwise; ``integers="whole"`` (clip): its own
+    dtype when every clipped value is a whole number, float64 otherwise.  One reduction on the device decides either."""
+    out = {}
+    for name, row in rows.items():
+        dtype = dtypes[name]
+        if dtype_kind(dtype) == "f":
+            out[name] = row if _torch_dtype(dtype) == torch.float64 else row.to(_torch_dtype(dtype))
+        elif integers == "nan":
+            if bool(torch.isnan(row).any()):
+                out[name] = row
+        elif bool((row == torch.floor(row)).all()):
+            out[name] = row.to(_torch_dtype(dtype))
+        else:
+            out[name] = row
+    return out
+
+
+def _selected(t: Table, columns: list[str] | None, column_prefix: str | None) -> list[str] | None:
+    """R: the ``columns`` / ``column_prefix`` selection every such filter repeats; None with neither."""
+    if columns:
+        t.require(columns)
+        return list(columns)
+    if column_prefix:
+        found = [c for c in t.names if isinstance(c, str) and c.startswith(column_prefix)]
+        if not found:
+            raise ValueError(f"No columns starting with '{column_prefix}' found in DataFrame.")
+        return found
+    return None
+
+
+class _MaskFilter(Filter):
+    """What the masking filters share: compile, run, narrow, hand back through ``Table``."""
+
+    integers = "nan"
+
+    def _program(self, t: Table, dtypes: dict[str, Any]) -> obs.RowProgram:
+        raise NotImplementedError
+
+    def _columns(self, t: Table) -> list[str]:
+        raise NotImplementedError
+
+    def _rows(self, t: Table) -> dict[str, torch.Tensor]:
+        return {}
+
+    def forward(self, table: Any) -> Any:
+        t = Table(table)
+        dtypes = _dtypes(t, self._columns(t))
+        program = self._program(t, dtypes)  # the host's errors come before anything touches the device
+        if t.n_rows == 0 or not program.launches:
+            return table.copy() if t.frame else dict(table)
+        rows = obs.row_program(table, program, dev=t.device, rows=self._rows(t))
+        return t.replaced(_narrowed(rows, dtypes, self.integers))
+
+
+class MaskValues(_MaskFilter):
+    """NaN where ``column OPERATOR value`` (R: filters/tabular/mask.py:36-87).  ``**config`` maps a column to ``{"value": v, "operator":
+    op}``; ``op`` is one of ``> < == != >= <=`` or ``gt lt eq ne ge le`` and defaults to ``==``.  The constructor's ``ValueError``s are the
+    reference's.  One launch per four columns (``obs.compile_mask_values`` -> ``obs.row_program`` -> ``atx_obs_column_ops``).  A float32 column
+    is compared in float32, as numpy compares it (the value is rounded first), and stays float32; an integer column comes back
+    unchanged when nothing was masked and float64 otherwise (pandas' rule).
+
+    Deviations: the caller's table is not modified; integers beyond 2^53 are not specially handled; a bool column raises ``ValueError``."""
+
+    def __init__(self, **config: Any) -> None:
+        if not config:
+            raise ValueError("No columns to mask were specified.")
+        self.config = {}
+        for col, condition in config.items():
+            if not isinstance(condition, dict):
+                raise ValueError(f"Mask condition for column {col} must be a dictionary, ")
+            if "value" not in condition:
+                raise ValueError(f"Mask condition for column {col} must contain a 'value' key.")
+            operator = condition.get("operator", "==")
+            if operator not in obs.MASK_OPERATORS:
+                raise ValueError(f"Invalid operator '{operator}' for column {col}. "
+                                 f"Valid operators are: {', '.join(obs.MASK_OPERATORS.keys())}.")
+            self.config[col] = (operator, condition["value"])
+        _qc_note(type(self))
+
+    def __repr__(self) -> str:
+        return "MaskValues(" + ", ".join(f"{c} {o} {v}" for c, (o, v) in self.config.items()) + ")"
+
+    def _columns(self, t: Table) -> list[str]:
+        t.require(list(self.config))
+        return list(self.config)
+
+    def _program(self, t: Table, dtypes: dict[str, Any]) -> obs.RowProgram:
+        return obs.compile_mask_values(self.config, dtypes)
+
+
+def _check_ranges(config: dict, what: str, noun: str) -> None:
+    """R: mask_outside_range.py:40-50 and clip.py:44-52, word for word."""
+    for column, bounds in config.items():
+        if not isinstance(bounds, (list, tuple)) or len(bounds) != 2:
+            raise ValueError(f"Invalid {what} range for column {column}: {bounds}")
+        if not all(isinstance(v, (int, float)) or v is None for v in bounds):
+            raise ValueError(f"{noun} range values for column {column} must be numeric or None: {bounds}")
+
+
+class MaskOutsideRange(_MaskFilter):
+    """NaN where ``column < low`` or ``column > high`` (R: filters/tabular/mask_outside_range.py:19-60).  ``**config`` maps a column to
+    ``[low, high]``; None is no bound.  Numerics and dtypes as ``mask_tabular``.  A missing column raises ``ValueError`` (the reference: a
+    ``KeyError`` from pandas)."""
+
+    def __init__(self, **config: Any) -> None:
+        if not config:
+            raise ValueError("No columns to mask were specified.")
+        _check_ranges(config, "mask", "Mask")
+        self.config = config
+        _qc_note(type(self))
+
+    def __repr__(self) -> str:
+        return f"MaskOutsideRange({self.config})"
+
+    def _columns(self, t: Table) -> list[str]:
+        t.require(list(self.config))
+        return list(self.config)
+
+    def _program(self, t: Table, dtypes: dict[str, Any]) -> obs.RowProgram:
+        return obs.compile_mask_outside_range({c: tuple(r) for c, r in self.config.items()}, dtypes)
+
+
+class MaskInfs(_MaskFilter):
+    """NaN where a column is infinite (R: filters/tabular/mask_infs.py:21-64): ``|x| > DBL_MAX``.  ``columns`` or ``column_prefix``, exactly
+    one of them (``ValueError`` otherwise, at construction)."""
+
+    def __init__(self, *, columns: list[str] | None = None, column_prefix: str | None = None) -> None:
+        if bool(columns) == bool(column_prefix):
+            raise ValueError("Either columns or column_prefix must be specified, but not both.")
+        self.columns = [columns] if isinstance(columns, str) else columns
+        self.column_prefix = column_prefix
+        _qc_note(type(self))
+
+    def __repr__(self) -> str:
+        return f"MaskInfs({self.columns if self.columns else self.column_prefix + '*'})"
+
+    def _columns(self, t: Table) -> list[str]:
+        return _selected(t, self.columns, self.column_prefix)
+
+    def _program(self, t: Table, dtypes: dict[str, Any]) -> obs.RowProgram:
+        return obs.compile_mask_beyond(list(dtypes), None, dtypes)
+
+
+class MaskDewpointTemperature(_MaskFilter):
+    """NaN in the dewpoint column — and, with ``mask_specific_humidity``, in the humidity column — where ``temperature < dewpoint``
+    (R: filters/tabular/mask_dewpoint_temperature.py:20-73).  One condition, on the dewpoint as it came: a NaN dewpoint masks nothing."""
+
+    def __init__(self, *, temperature: str = "2t", dewpoint_temperature: str = "2d", specific_humidity: str = "2q",
+                 mask_specific_humidity: bool = False) -> None:
+        self.temperature = temperature
+        self.dewpoint_temperature = dewpoint_temperature
+        self.specific_humidity = specific_humidity
+        self.mask_specific_humidity = mask_specific_humidity
+        _qc_note(type(self))
+
+    def __repr__(self) -> str:
+        return f"MaskDewpointTemperature({self.temperature!r} < {self.dewpoint_temperature!r})"
+
+    def _columns(self, t: Table) -> list[str]:
+        names = [self.temperature, self.dewpoint_temperature] + ([self.specific_humidity] if self.mask_specific_humidity else [])
+        t.require(names)
+        return names
+
+    def _program(self, t: Table, dtypes: dict[str, Any]) -> obs.RowProgram:
+        return obs.compile_mask_dewpoint(self.temperature, self.dewpoint_temperature,
+                                         self.specific_humidity if self.mask_specific_humidity else None, dtypes)
+
+
+def _epoch_day(value: Any) -> int:
+    """``pd.to_datetime(str(value), format="%Y%m%d")`` as whole days since the epoch (R: exclude_dates.py:69-70)."""
+    try:
+        return (datetime.datetime.strptime(str(value), "%Y%m%d").date() - datetime.date(1970, 1, 1)).days
+    except ValueError as e:
+        raise ValueError(f"time data \"{value}\" doesn't match format \"%Y%m%d\": {e}") from None
+
+
+class ExcludeDates(_MaskFilter):
+    """NaN in a column where the row's ``date`` lies in one of the column's date ranges, both ends inclusive
+    (R: filters/tabular/exclude_dates.py:21-91).  ``**config`` maps a column to a list of ``[start, end]`` (``YYYYMMDD`` as int or
+    str); a single pair is one range.  The bounds are whole UTC days, so the condition is ``start_day <= day < end_day + 1`` with
+    ``day = floor(date_ns / 86 400e9)``, computed once per call on the device (``obs.utc_days``; NaT is NaN and in no range); the ranges
+    are compares in the program, OR-ed.  The constructor's ``ValueError``s are the reference's."""
+
+    def __init__(self, **config: Any) -> None:
+        if not config:
+            raise ValueError("No columns to exclude dates from were specified.")
+        self.excluded_dates: dict[str, list[tuple[int, int]]] = {}
+        for column, ranges in config.items():
+            if not (ranges and isinstance(ranges, (list, tuple))):
+                raise ValueError(f"Invalid date ranges {ranges} for column '{column}'. Expected a list/tuple.")
+            if len(ranges) == 2 and all(isinstance(r, (int, str)) for r in ranges):
+                ranges = [ranges]  # a single pair
+            for date_range in ranges:
+                try:
+                    start, end = date_range
+                except (ValueError, TypeError) as e:
+                    raise ValueError(f"Invalid date range {date_range} for column '{column}'. "
+                                     "Expected a tuple like (start_date, end_date).") from e
+                self.excluded_dates.setdefault(column, []).append((_epoch_day(start), _epoch_day(end)))
+        _qc_note(type(self))
+
+    def __repr__(self) -> str:
+        return f"ExcludeDates({ {c: len(r) for c, r in self.excluded_dates.items()} })"
+
+    def _columns(self, t: Table) -> list[str]:
+        t.require(list(self.excluded_dates) + ["date"])
+        return list(self.excluded_dates)
+
+    def _program(self, t: Table, dtypes: dict[str, Any]) -> obs.RowProgram:
+        if not (t.is_datetime("date") or column_kind(t["date"]) in "iO"):
+            raise ValueError(f"the date column holds {column_kind(t['date'])!r} values, not datetimes")
+        return obs.compile_exclude_dates(self.excluded_dates, dtypes)
+
+    def _rows(self, t: Table) -> dict[str, torch.Tensor]:
+        return {obs.DAY_ROW: obs.utc_days(t["date"], t.device)}
+
+
+class RemoveExtremeValues(_MaskFilter):
+    """Masks, or drops the rows with, values beyond ``±threshold`` (R: filters/tabular/remove_extreme_values.py:21-92).  The columns are
+    ``columns`` or those starting with ``column_prefix`` (exactly one of the two), plus ``latitude`` and ``longitude``.  ``method="mask"``:
+    NaN where ``|x| > threshold``.  ``method="drop"`` (the default): the rows where no column exceeds the threshold are kept (a NaN does
+    not exceed it) — ``obs.keep_rows`` and one gather of every column (``Table.take``; ``iloc`` for a DataFrame, so index labels travel)."""
+
+    def __init__(self, *, columns: list[str] | None = None, column_prefix: str | None = None, threshold: float = 1e10,
+                 method: str = "drop") -> None:
+        if method not in ("mask", "drop"):
+            raise ValueError(f"Invalid method '{method}'. Must be either 'mask' or 'drop'.")
+        if bool(columns) == bool(column_prefix):
+            raise ValueError("Either columns or column_prefix must be specified, but not both.")
+        self.method = method
+        self.columns = [columns] if isinstance(columns, str) else columns
+        self.column_prefix = column_prefix
+        self.threshold = threshold
+        _qc_note(type(self))
+
+    def __repr__(self) -> str:
+        return f"RemoveExtremeValues({self.method}, threshold={self.threshold})"
+
+    def _columns(self, t: Table) -> list[str]:
+        names = _selected(t, self.columns, self.column_prefix) + ["latitude", "longitude"]
+        t.require(names)
+        return list(dict.fromkeys(names))
+
+    def _program(self, t: Table, dtypes: dict[str, Any]) -> obs.RowProgram:
+        return obs.compile_mask_beyond(list(dtypes), self.threshold, dtypes)
+
+    def forward(self, table: Any) -> Any:
+        if self.method == "mask":
+            return super().forward(table)
+        t = Table(table)
+        dtypes = _dtypes(t, self._columns(t))
+        program = obs.compile_keep_not_beyond(list(dtypes), self.threshold, dtypes)
+        if t.n_rows == 0:
+            return table.copy() if t.frame else dict(table)
+        return t.take(obs.keep_rows(table, program, dev=t.device))
+
+
+class ClipTabular(_MaskFilter):
+    """``column.clip(low, high)`` (R: filters/tabular/clip.py:20-60).  ``**config`` maps a column to ``[low, high]``; None is no bound.
+    ``CLIP_LOW`` then ``CLIP_HIGH`` in one launch: a NaN stays, ``-0.0`` stays against a bound of 0.  pandas' own rules are kept: a NaN
+    bound is no bound, bounds the wrong way round are swapped, a float32 column is clipped to the bound rounded to float32 and stays
+    float32, and an integer column stays integer when every clipped value is a whole number — always so with integer bounds — and is
+    float64 otherwise."""
+
+    integers = "whole"
+
+    def __init__(self, **config: Any) -> None:
+        if not config:
+            raise ValueError("No columns to clip were specified.")
+        _check_ranges(config, "clip", "Clip")
+        self.config = config
+        _qc_note(type(self))
+
+    def __repr__(self) -> str:
+        return f"ClipTabular({self.config})"
+
+    def _columns(self, t: Table) -> list[str]:
+        t.require(list(self.config))
+        return list(self.config)
+
+    def _program(self, t: Table, dtypes: dict[str, Any]) -> obs.RowProgram:
+        return obs.compile_clip({c: tuple(r) for c, r in self.config.items()}, dtypes)
+
+
+class ImputeNaNsTabular(Filter):
+    """``table.fillna(value)`` (R: filters/tabular/impute_nans.py:20-81).  ``value`` is a scalar or a dict per column.  ``columns`` /
+    ``column_prefix`` (not both: ``ValueError``) are validated against the table and then — as in the reference, whose ``forward`` calls
+    ``fillna`` on the WHOLE frame — select nothing: every column is filled.  Floating-point columns are filled on the device
+    (``FILL_NAN``; a float32 column gets the value rounded to float32 and stays float32); integer columns have nothing to fill.  A
+    datetime or non-numeric column goes through pandas' own ``fillna`` in a DataFrame; in a mapping it raises ``ValueError`` if it has
+    a missing entry, and stays as it is otherwise."""
+
+    def __init__(self, *, value: Any, columns: list[str] | None = None, column_prefix: str | None = None) -> None:
+        if bool(columns) and bool(column_prefix):
+            raise ValueError("Either columns or column_prefix may be specified, but not both.")
+        self.value = value
+        self.columns = [columns] if isinstance(columns, str) else columns
+        self.column_prefix = column_prefix
+        _qc_note(type(self))
+
+    def __repr__(self) -> str:
+        return f"ImputeNaNsTabular(value={self.value!r})"
+
+    def forward(self, table: Any) -> Any:
+        t = Table(table)
+        if _selected(t, self.columns, self.column_prefix) is not None:
+            say_once(LOG, (type(self), "subset"), "impute_nans_tabular: columns / column_prefix are checked against the table and then "
+                     "ignored, as in the reference: its forward() calls fillna(value) on the whole frame", level=logging.INFO)
+        per_column = isinstance(self.value, dict)
+        asked = [name for name in t.names if not per_column or name in self.value]
+        floats = [name for name in asked if not t.is_datetime(name) and column_kind(t[name]) == "f"]
+        others = [name for name in asked if name not in floats and (t.is_datetime(name) or column_kind(t[name]) not in "iub")]
+        if not t.frame:
+            for name in others:
+                if bool(t.missing(name, torch.device("cpu") if not isinstance(t[name], torch.Tensor) else t[name].device).any()):
+                    raise ValueError(f"impute_nans_tabular: column {name!r} is not numeric and has missing entries; only a DataFrame's "
+                                     "own fillna can fill it")
+        dtypes = _dtypes(t, floats)
+        program = obs.compile_fill_nans({name: (self.value[name] if per_column else self.value) for name in floats}, dtypes)
+        filled = {}
+        if t.n_rows and program.launches:
+            filled = _narrowed(obs.row_program(table, program, dev=t.device), dtypes, "nan")
+        out = t.replaced(filled) if (filled or not t.frame) else table.copy()
+        if t.frame and others:
+            out[others] = table[others].fillna({name: self.value[name] for name in others} if per_column else self.value)
+        return out
+
+
+class DropNaNsTabular(Filter):
+    """``table.dropna(how=how, subset=...)`` (R: filters/tabular/drop_nans.py:21-73).  ``how``: ``"any"`` (default) or ``"all"``; the subset
+    is ``columns``, or the columns starting with ``column_prefix`` (not both), or every column.  Floating-point columns are tested in the
+    program (``IS_NAN``); any other column enters as the 0 / 1 row of ``Table.missing`` — NaT and None count, an integer column has
+    none.  The kept rows are taken in one gather of every column (``obs.keep_rows`` -> ``Table.take``; ``iloc`` for a DataFrame)."""
+
+    def __init__(self, *, how: str = "any", columns: list[str] | None = None, column_prefix: str | None = None) -> None:
+        if how not in ("any", "all"):
+            raise ValueError(f"DropNaNs - 'how' must be either 'any' or 'all', not '{how}'.")
+        if bool(columns) and bool(column_prefix):
+            raise ValueError("Either columns or column_prefix may be specified, but not both.")
+        self.how = how
+        self.columns = [columns] if isinstance(columns, str) else columns
+        self.column_prefix = column_prefix
+        _qc_note(type(self))
+
+    def __repr__(self) -> str:
+        return f"DropNaNsTabular(how={self.how!r})"
+
+    def forward(self, table: Any) -> Any:
+        t = Table(table)
+        subset = _selected(t, self.columns, self.column_prefix)
+        subset = t.names if subset is None else subset
+        if t.n_rows == 0 or not subset:
+            return table.copy() if t.frame else dict(table)
+        kinds = {name: ("M" if t.is_datetime(name) else column_kind(t[name])) for name in subset}
+        dtypes = {name: (np.dtype(np.float64) if kinds[name] == "f" else np.dtype(np.int64)) for name in subset}
+        program = obs.compile_keep_not_missing(subset, self.how, dtypes)
+        rows = {f"%missing:{name}": t.missing(name, t.device).to(torch.float64) for name in subset if kinds[name] != "f"}
+        return t.take(obs.keep_rows(table, program, dev=t.device, rows=rows))
+
+
+filter_registry.register("mask_tabular", MaskValues)
+filter_registry.register("mask_outside_range", MaskOutsideRange)
+filter_registry.register("mask_infs", MaskInfs)
+filter_registry.register("mask_dewpoint_temperature", MaskDewpointTemperature)
+filter_registry.register("exclude_dates", ExcludeDates)
+filter_registry.register("remove_extreme_values", RemoveExtremeValues)
+filter_registry.register("clip_tabular", ClipTabular)
+filter_registry.register("impute_nans_tabular", ImputeNaNsTabular)
+filter_registry.register("drop_nans_tabular", DropNaNsTabular)
 filter_registry.register("sort_by", SortBy)
 filter_registry.register("drop_duplicates", DropDuplicates)
 filter_registry.register("drop", Drop)

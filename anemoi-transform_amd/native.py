@@ -637,14 +637,23 @@ def obs_fill_heights(latitude, longitude, altitude, lat_axis, lat_perm, lon_axis
 MAX_COLUMN_OPS = 16
 # the ATX_COLOP_* codes by the reference's function names (R: filters/tabular/apply_column_transformations.py:31-42, in its order)
 COLUMN_OPS = {"log": 0, "log1p": 1, "safe_log": 2, "sqrt": 3, "exp": 4, "abs": 5, "sin": 6, "sin_deg": 7, "cos": 8, "cos_deg": 9}
+# the second family of ATX_COLOP_* codes: the row operations of the tabular QC filters (include/atx.h; csrc/atx_obs_row_program.hip).  A
+# program is all COLUMN_OPS or all ROW_OPS.  The binary ones (cmp_gt and above) take the result of the operation before them as y.
+ROW_OPS = {"scalar": 16, "copy": 17, "is_nan": 18, "not": 19, "cmp_gt": 20, "cmp_lt": 21, "cmp_eq": 22, "cmp_ne": 23, "cmp_ge": 24,
+           "cmp_le": 25, "abs_gt": 26, "and": 27, "or": 28, "nan_where": 29, "clip_low": 30, "clip_high": 31, "fill_nan": 32}
 
 
 def obs_column_ops(ops, n: int) -> None:
     """One launch of ``atx_obs_column_ops`` over ``n`` rows.  ``ops``: 1 .. ``MAX_COLUMN_OPS`` tuples ``(code, src, column, out)`` —
     ``code`` an ATX_COLOP_* value; ``src`` -1 to read ``column`` (a float64 device row of ``n``), or the index of the earlier
     operation whose result is taken (``column`` is then ignored and may be ``None``); ``out`` a float64 device row of ``n`` or ``None``
-    for an intermediate.  ``out`` may be ``column``.  Does not synchronise."""
-    for _, src, column, out in ops:
+    for an intermediate.  ``out`` may be ``column``.  The ``column`` of a ``ROW_OPS["scalar"]`` operation is a float64 device tensor of
+    which element 0 alone is read.  Does not synchronise."""
+    for code, src, column, out in ops:
+        if int(code) == ROW_OPS["scalar"] and column is not None:
+            assert column.dtype == torch.float64 and column.is_contiguous() and column.numel() >= 1, "a scalar is a float64 device tensor of one element"
+            _rows(None, out, n=n)
+            continue
         _rows(column if src < 0 else None, out, n=n)
     k = len(ops)
     codes = (c_int32 * k)(*[int(o[0]) for o in ops])

@@ -35,6 +35,12 @@ The sixth is the row sets of ``sort_by`` and ``drop_duplicates`` (R: filters/tab
 turns a column into int64 keys that order and compare as pandas does (``atx_obs_order_key``), ``sort_order`` is the stable multi-key
 permutation (the library's stable radix sort, one pass per key), ``first_rows`` the first row of every group of equal key tuples
 (``atx_obs_mark_first``), and ``take_rows`` gathers every column of a table by one row list (``atx_obs_take_rows``).
+
+The seventh is the tabular QC filters (R: filters/tabular/mask.py, mask_outside_range.py, mask_infs.py, mask_dewpoint_temperature.py,
+exclude_dates.py, remove_extreme_values.py, clip.py, impute_nans.py, drop_nans.py): one small compiler per filter (``compile_mask_values``
+.. ``compile_keep_not_missing``) turns its configuration and the column dtypes into a ``RowProgram`` — launches of at most 16 slots of the
+row operations ``native.ROW_OPS``, pure host logic — ``row_program`` runs it (``atx_obs_column_ops``, the row-program kernel) and
+``keep_rows`` lists the rows a row-dropping filter keeps.
 """
 
 from __future__ import annotations
@@ -821,3 +827,282 @@ def first_rows(columns: Sequence[Any], dev: torch.device | None = None, *, datet
     for j in range(0, len(keys), native.MAX_ROWSET_COLUMNS):
         native.obs_mark_first(keys[j:j + native.MAX_ROWSET_COLUMNS], order, keep, accumulate=j > 0)
     return torch.nonzero(keep).reshape(-1)
+
+
+# ---- row programs: the tabular QC filters (R: filters/tabular/mask.py, mask_outside_range.py, mask_infs.py, --------------------------
+# ---- mask_dewpoint_temperature.py, exclude_dates.py, remove_extreme_values.py, clip.py, impute_nans.py, drop_nans.py) ---------------
+DBL_MAX = float(np.finfo(np.float64).max)
+DAY_NS = 86400 * 10**9
+DAY_ROW = "%day"    # the whole UTC day of every row's date, float64 with NaT as NaN (``utc_days``)
+KEEP_ROW = "%keep"  # the 0 / 1 row a keep-row program ends in
+# R: mask.py:20-33, the 12 spellings
+MASK_OPERATORS = {">": "cmp_gt", "<": "cmp_lt", "==": "cmp_eq", "!=": "cmp_ne", ">=": "cmp_ge", "<=": "cmp_le",
+                  "gt": "cmp_gt", "lt": "cmp_lt", "eq": "cmp_eq", "ne": "cmp_ne", "ge": "cmp_ge", "le": "cmp_le"}
+ROW_BINARY = frozenset(name for name, code in native.ROW_OPS.items() if code >= native.ROW_OPS["cmp_gt"])
+
+
+class RowSlot(NamedTuple):
+    """One operation of a launch of the row-program kernel.  ``op``: a ``native.ROW_OPS`` name.  x is the result of slot ``src`` of the
+    same launch, or with ``src`` -1 the row ``read`` from memory, or for ``"scalar"`` the entry ``scalar`` of the program's scalars.  y, for
+    a binary operation, is the result of the slot before.  ``store``: the row the result is written to, or None."""
+    op: str
+    src: int
+    read: str | None
+    scalar: int | None
+    store: str | None
+
+
+class RowLaunch(NamedTuple):
+    """One launch of ``atx_obs_column_ops`` with codes of the second family: 1 .. 16 slots."""
+    slots: tuple[RowSlot, ...]
+
+
+class RowProgram(NamedTuple):
+    """What a QC filter computes for one table: ``scalars`` (uploaded once per call), the ``launches`` in order, and the names of the rows
+    that leave it (``results``).  A name starting with ``%`` is no column of the table: ``%day``, ``%missing:<column>`` are rows the
+    caller provides, every other one an intermediate that crosses a launch boundary through a float64 device row."""
+    scalars: tuple[float, ...]
+    launches: tuple[RowLaunch, ...]
+    results: tuple[str, ...]
+
+
+class _RowBuilder:
+    """Packs UNITS of slots into launches.  A unit is a list of ``(op, x, store)`` that stays together, because its binary operations
+    take the slot before them: ``x`` is a row name (read from memory, or taken from the slot of this launch that last stored or copied
+    that row), an int (a slot of the unit, counted from its start) or a 1-tuple (the number of a scalar)."""
+
+    def __init__(self) -> None:
+        self.scalars: list[float] = []
+        self.launches: list[list[RowSlot]] = []
+        self.run: list[RowSlot] = []
+        self.where: dict[str, int] = {}  # row name -> the slot of the open launch that holds its current value
+
+    def scalar(self, value: float) -> tuple[int]:
+        self.scalars.append(float(value))
+        return (len(self.scalars) - 1,)
+
+    def close(self) -> None:
+        if self.run:
+            self.launches.append(self.run)
+            self.run, self.where = [], {}
+
+    def emit(self, unit: Sequence[tuple[str, Any, str | None]]) -> None:
+        assert 0 < len(unit) <= native.MAX_COLUMN_OPS and unit[0][0] not in ROW_BINARY
+        if len(self.run) + len(unit) > native.MAX_COLUMN_OPS:
+            self.close()
+        base = len(self.run)
+        for op, x, store in unit:
+            t = len(self.run)
+            if isinstance(x, tuple):
+                slot = RowSlot(op, -1, None, x[0], store)
+            elif isinstance(x, int):
+                slot = RowSlot(op, base + x, None, None, store)
+            else:
+                held = self.where.get(x, -1)
+                slot = RowSlot(op, held, x if held < 0 else None, None, store)
+                if op == "copy" and held < 0:
+                    self.where[x] = t  # loaded once: later reads of this launch take the register
+            self.run.append(slot)
+            if store is not None:
+                self.where[store] = t
+
+    def finish(self, results: Sequence[str]) -> RowProgram:
+        self.close()
+        launches = []
+        for k, run in enumerate(self.launches):
+            last = {slot.store: t for t, slot in enumerate(run) if slot.store is not None}
+            later = {slot.read for other in self.launches[k + 1:] for slot in other if slot.read is not None}
+            # a row is written by the last slot of the launch that stores it, and an intermediate only where a later launch reads it
+            launches.append(RowLaunch(tuple(
+                slot._replace(store=slot.store if slot.store is not None and last[slot.store] == t
+                              and (not slot.store.startswith("%") or slot.store in later or slot.store in results) else None)
+                for t, slot in enumerate(run))))
+        return RowProgram(tuple(self.scalars), tuple(launches), tuple(results))
+
+
+def round_scalar(value: Any, dtype: Any) -> float:
+    """The configured number as the column's compare sees it: numpy compares a float32 (float16) column with a Python number in the
+    column's precision, so the number is rounded to it first — after that the float64 compare IS the narrow one.  float64 and integer
+    columns take ``float(value)`` (an integer beyond 2^53 is rounded: not specially handled)."""
+    if _dtype_kind(dtype) == "f":
+        if isinstance(dtype, torch.dtype):
+            return float(torch.tensor(float(value), dtype=torch.float64).to(dtype)) if dtype != torch.float64 else float(value)
+        if np.dtype(dtype).itemsize < 8:
+            with np.errstate(over="ignore"):
+                return float(np.dtype(dtype).type(value))
+    return float(value)
+
+
+def _numeric(dtypes: Mapping[str, Any], name: str) -> Any:
+    if _dtype_kind(dtypes[name]) not in "iuf":
+        raise ValueError(f"column {name!r}: a numeric column is needed, got dtype {dtypes[name]}")
+    return dtypes[name]
+
+
+def compile_mask_values(conditions: Mapping[str, tuple[str, Any]], dtypes: Mapping[str, Any]) -> RowProgram:
+    """``column -> (operator, value)``: NaN where ``column OPERATOR value`` (R: mask.py: ``col.mask(op(col, value))``)."""
+    b = _RowBuilder()
+    for col, (operator, value) in conditions.items():
+        k = b.scalar(round_scalar(value, _numeric(dtypes, col)))
+        b.emit([("copy", col, None), ("scalar", k, None), (MASK_OPERATORS[operator], 0, None), ("nan_where", 0, col)])
+    return b.finish(list(conditions))
+
+
+def compile_mask_outside_range(ranges: Mapping[str, tuple[Any, Any]], dtypes: Mapping[str, Any]) -> RowProgram:
+    """``column -> (low, high)``: NaN where ``column < low`` or ``column > high``; None is no bound (R: mask_outside_range.py)."""
+    b = _RowBuilder()
+    results = []
+    for col, (low, high) in ranges.items():
+        dtype = _numeric(dtypes, col)
+        if low is None and high is None:
+            continue  # Series.mask(False): the column as it is
+        unit: list[tuple[str, Any, str | None]] = [("copy", col, None)]
+        if low is not None:
+            unit += [("scalar", b.scalar(round_scalar(low, dtype)), None), ("cmp_lt", 0, None)]
+        if high is not None:
+            unit += [("scalar", b.scalar(round_scalar(high, dtype)), None), ("cmp_gt", 0, None)]
+        if low is not None and high is not None:
+            unit.append(("or", 2, None))
+        b.emit(unit + [("nan_where", 0, col)])
+        results.append(col)
+    return b.finish(results)
+
+
+def compile_mask_beyond(columns: Sequence[str], threshold: float | None, dtypes: Mapping[str, Any]) -> RowProgram:
+    """NaN where ``|column| > threshold`` (R: remove_extreme_values.py, method ``mask``: the threshold is compared in the column's
+    precision); ``threshold=None`` is ``mask_infs``: ``|column| > DBL_MAX``, not rounded — a float32 infinity is a float64 infinity."""
+    b = _RowBuilder()
+    for col in dict.fromkeys(columns):
+        k = b.scalar(DBL_MAX if threshold is None else round_scalar(threshold, _numeric(dtypes, col)))
+        _numeric(dtypes, col)
+        b.emit([("copy", col, None), ("scalar", k, None), ("abs_gt", 0, None), ("nan_where", 0, col)])
+    return b.finish(list(dict.fromkeys(columns)))
+
+
+def compile_mask_dewpoint(temperature: str, dewpoint: str, humidity: str | None, dtypes: Mapping[str, Any]) -> RowProgram:
+    """ONE condition, ``temperature < dewpoint`` on the original dewpoint, masks the dewpoint and — if named — the humidity
+    (R: mask_dewpoint_temperature.py): a NaN dewpoint masks nothing."""
+    for name in (temperature, dewpoint) + ((humidity,) if humidity else ()):
+        _numeric(dtypes, name)
+    b = _RowBuilder()
+    unit: list[tuple[str, Any, str | None]] = [("copy", dewpoint, None), ("cmp_lt", temperature, None), ("nan_where", 0, dewpoint)]
+    if humidity:
+        unit += [("copy", 1, None), ("nan_where", humidity, humidity)]
+    b.emit(unit)
+    return b.finish([dewpoint] + ([humidity] if humidity else []))
+
+
+def compile_exclude_dates(excluded: Mapping[str, Sequence[tuple[int, int]]], dtypes: Mapping[str, Any]) -> RowProgram:
+    """``column -> [(start_day, end_day), ...]`` in whole days since the epoch, both inclusive: NaN where
+    ``start_day <= day < end_day + 1`` for any range, ``day`` the row ``%day`` (R: exclude_dates.py; a NaT day is NaN and in no range)."""
+    b = _RowBuilder()
+    for col, ranges in excluded.items():
+        _numeric(dtypes, col)
+        cond = f"%in:{col}"
+        for k, (start, end) in enumerate(ranges):
+            unit: list[tuple[str, Any, str | None]] = [("copy", DAY_ROW, None)] if k == 0 else []
+            first = len(unit)
+            unit += [("scalar", b.scalar(float(start)), None), ("cmp_ge", DAY_ROW, None), ("scalar", b.scalar(float(end) + 1.0), None),
+                     ("cmp_lt", DAY_ROW, None), ("and", first + 1, None if k else cond)]
+            if k:
+                unit.append(("or", cond, cond))
+            if k == len(ranges) - 1:
+                unit.append(("nan_where", col, col))
+            b.emit(unit)
+    return b.finish(list(excluded))
+
+
+def compile_clip(ranges: Mapping[str, tuple[Any, Any]], dtypes: Mapping[str, Any]) -> RowProgram:
+    """``column -> (low, high)``: ``Series.clip(low, high)`` (R: clip.py) — a NaN bound is no bound, two bounds the wrong way round are
+    swapped (both pandas' own), a NaN value stays, ``-0.0`` stays against a bound of 0."""
+    b = _RowBuilder()
+    results = []
+    for col, (low, high) in ranges.items():
+        dtype = _numeric(dtypes, col)
+        low, high = (None if v is None or v != v else v for v in (low, high))
+        if low is not None and high is not None and low > high:
+            low, high = high, low
+        unit: list[tuple[str, Any, str | None]] = []
+        if low is not None:
+            unit += [("scalar", b.scalar(round_scalar(low, dtype)), None), ("clip_low", col, None)]
+        if high is not None:
+            unit += [("scalar", b.scalar(round_scalar(high, dtype)), None), ("clip_high", 1 if unit else col, None)]
+        if unit:
+            b.emit(unit[:-1] + [(unit[-1][0], unit[-1][1], col)])
+            results.append(col)
+    return b.finish(results)
+
+
+def compile_fill_nans(values: Mapping[str, Any], dtypes: Mapping[str, Any]) -> RowProgram:
+    """``column -> value``: ``fillna`` of the floating-point columns (R: impute_nans.py)."""
+    b = _RowBuilder()
+    for col, value in values.items():
+        b.emit([("scalar", b.scalar(round_scalar(value, dtypes[col])), None), ("fill_nan", col, col)])
+    return b.finish(list(values))
+
+
+def compile_keep_not_beyond(columns: Sequence[str], threshold: float, dtypes: Mapping[str, Any]) -> RowProgram:
+    """``%keep`` = no column has ``|x| > threshold`` (R: remove_extreme_values.py, method ``drop``); a NaN does not exceed it."""
+    b = _RowBuilder()
+    bad = "%beyond"
+    for k, col in enumerate(dict.fromkeys(columns)):
+        unit: list[tuple[str, Any, str | None]] = [("scalar", b.scalar(round_scalar(threshold, _numeric(dtypes, col))), None),
+                                                    ("abs_gt", col, None if k else bad)]
+        b.emit(unit + ([("or", bad, bad)] if k else []))
+    b.emit([("not", bad, KEEP_ROW)])
+    return b.finish([KEEP_ROW])
+
+
+def compile_keep_not_missing(columns: Sequence[str], how: str, dtypes: Mapping[str, Any]) -> RowProgram:
+    """``%keep`` = not (any / all of the columns are missing) (R: drop_nans.py: ``dropna(how, subset)``).  A floating-point column is
+    tested by ``is_nan``; any other enters as the 0 / 1 row ``%missing:<column>`` the caller provides (NaT, None; zeros for integers)."""
+    b = _RowBuilder()
+    gone = "%gone"
+    for k, col in enumerate(dict.fromkeys(columns)):
+        test = ("is_nan", col) if _dtype_kind(dtypes[col]) == "f" else ("copy", f"%missing:{col}")
+        b.emit([(*test, None if k else gone)] + ([("or" if how == "any" else "and", gone, gone)] if k else []))
+    b.emit([("not", gone, KEEP_ROW)])
+    return b.finish([KEEP_ROW])
+
+
+def utc_days(date: Any, dev: torch.device) -> torch.Tensor:
+    """``floor(date_ns / 86 400e9)`` as a float64 device row, NaN for NaT: one floor division on the device; the cast is exact."""
+    ns = _device(to_ns(date), dev)
+    return torch.div(ns, DAY_NS, rounding_mode="floor").to(torch.float64).masked_fill_(ns == NAT, float("nan"))
+
+
+def row_program(columns: Mapping[str, Any], program: RowProgram, dev: torch.device | None = None,
+                rows: Mapping[str, torch.Tensor] | None = None) -> dict[str, torch.Tensor]:
+    """``{name: float64 device row}`` of the program's results over the table ``columns`` (a mapping or DataFrame of numpy arrays, pandas
+    Series or device tensors) — one launch of ``atx_obs_column_ops`` per ``RowLaunch``.  ``rows``: the ``%`` rows the program reads.  Columns
+    are read through ``float_column`` (a float64 device tensor is used in place, anything narrower or integer converts exactly below
+    2^53); every result is a fresh row, so the caller's columns are never written.  The scalars go up once, as one float64 tensor."""
+    dev = launch_device([*(columns[name] for name in columns.keys()), *(rows or {}).values()], dev)
+    scalars = _device(np.asarray(program.scalars, dtype=np.float64), dev) if program.scalars else None
+    current: dict[str, torch.Tensor] = {}
+    as_float: dict[str, torch.Tensor] = dict(rows or {})
+
+    def row(name: str) -> torch.Tensor:
+        if name in current:
+            return current[name]
+        if name not in as_float:
+            as_float[name] = float_column(columns[name], dev)
+        return as_float[name]
+
+    for launch in program.launches:
+        inputs = [row(slot.read) if slot.read is not None else None for slot in launch.slots]
+        lengths = {c.numel() for c in inputs if c is not None}
+        if len(lengths) != 1:
+            raise ValueError(f"columns differ in length: { {slot.read: c.numel() for slot, c in zip(launch.slots, inputs) if c is not None} }")
+        n = lengths.pop()
+        outs = [torch.empty(n, dtype=torch.float64, device=dev) if slot.store is not None else None for slot in launch.slots]
+        native.obs_column_ops([(native.ROW_OPS[slot.op], slot.src, scalars[slot.scalar:slot.scalar + 1] if slot.op == "scalar" else c, o)
+                               for slot, c, o in zip(launch.slots, inputs, outs)], n)
+        current.update({slot.store: o for slot, o in zip(launch.slots, outs) if o is not None})
+    return {name: current[name] for name in program.results}
+
+
+def keep_rows(columns: Mapping[str, Any], program: RowProgram, dev: torch.device | None = None,
+              rows: Mapping[str, torch.Tensor] | None = None) -> torch.Tensor:
+    """The ascending int64 device positions of the rows a keep-row program keeps (its ``%keep`` row is not 0)."""
+    return torch.nonzero(row_program(columns, program, dev, rows)[KEEP_ROW]).reshape(-1)

@@ -68,7 +68,8 @@
 extern "C" {
 #endif
 
-#define ATX_VERSION 420 /* 0.4.2 — additions only, so the number stays: atx_obs_order_key / atx_obs_mark_first / atx_obs_take_rows (row
+#define ATX_VERSION 420 /* 0.4.2 — additions only, so the number stays: a second family of atx_obs_column_ops codes, ATX_COLOP_SCALAR ..
+                           * ATX_COLOP_FILL_NAN (the compares, selects and row predicates of the tabular QC filters; no new entry point); atx_obs_order_key / atx_obs_mark_first / atx_obs_take_rows (row
                            * sets: pandas' order and equality as int64 keys, first occurrences, a gather of rows) with the
                            * atx_key_dtype enum; atx_obs_column_ops (a program of library functions over
                            * columns) with its ATX_COLOP_* codes; atx_obs_fill_heights (missing station altitudes from an
@@ -555,8 +556,28 @@ ATX_API int atx_obs_fill_heights(const double* latitude, const double* longitude
  * The caller guarantees that no operation reads from memory a column that an EARLIER operation of the same call writes: that
  * dependency goes through src.  A column that a LATER operation writes may be read.
  * n_ops outside 1 .. ATX_MAX_COLUMN_OPS, an unknown code, src[t] >= t, in[t] == NULL where src[t] < 0 (n > 0), a null program array,
- * n < 0: ATX_EINVAL, nothing launched.
- *   R: filters/tabular/apply_column_transformations.py:18-42 (the ten functions), :55-61 (apply), :132-138 (in order, chained) */
+ * n < 0: ATX_EINVAL, nothing launched.  n == 0: validated, nothing launched.
+ *   R: filters/tabular/apply_column_transformations.py:18-42 (the ten functions), :55-61 (apply), :132-138 (in order, chained)
+ *
+ * A SECOND FAMILY of codes, ATX_COLOP_SCALAR (16) and above, carries the tabular QC filters (R: filters/tabular/mask.py,
+ * mask_outside_range.py, mask_infs.py, mask_dewpoint_temperature.py, exclude_dates.py, remove_extreme_values.py, clip.py, impute_nans.py,
+ * drop_nans.py): compares, selects and one fabs per row, all exact.  A program is EITHER all codes 0 .. 9 OR all codes >= 16 (a mixed one
+ * is ATX_EINVAL); codes 10 .. 15 and above 32 are unknown.  The slot fields mean what they mean above; x is in[t][r] or the result of
+ * operation src[t].  New: a binary operation takes a second operand y = the result of operation t - 1 (whatever that is), so a binary
+ * operation at t = 0 is ATX_EINVAL.  Conditions are the doubles 0.0 / 1.0.
+ *   SCALAR      in[t][0] for every row           in[t] is a DEVICE double read at element 0 only; src[t] must be < 0 (else ATX_EINVAL)
+ *   COPY        x                                the bits kept, NaN payloads included
+ *   IS_NAN      x != x ? 1 : 0
+ *   NOT         x == 0 ? 1 : 0
+ *   CMP_GT, CMP_LT, CMP_EQ, CMP_NE, CMP_GE, CMP_LE   (x cmp y) ? 1 : 0     ATX_COLOP_CMP_GT + atx_cmp; IEEE's and numpy's compares:
+ *                                                false whenever x or y is a NaN, except NE, which is then true
+ *   ABS_GT      fabs(x) > y ? 1 : 0
+ *   AND, OR     (x != 0) and / or (y != 0) ? 1 : 0    a NaN is not 0
+ *   NAN_WHERE   y != 0 ? the canonical quiet NaN 0x7ff8000000000000 : x      pandas' Series.mask(y)
+ *   CLIP_LOW    x < y ? y : x                    selects, not fmax / fmin: a NaN x stays, and so does -0.0 against a bound of 0.0
+ *   CLIP_HIGH   x > y ? y : x
+ *   FILL_NAN    x != x ? y : x                   pandas' Series.fillna(y)
+ * Every select hands on the bits of the operand it picks. */
 #define ATX_MAX_COLUMN_OPS 16
 enum {
     ATX_COLOP_LOG = 0,
@@ -568,7 +589,25 @@ enum {
     ATX_COLOP_SIN = 6,
     ATX_COLOP_SIN_DEG = 7,
     ATX_COLOP_COS = 8,
-    ATX_COLOP_COS_DEG = 9
+    ATX_COLOP_COS_DEG = 9,
+    /* 10 .. 15: unknown */
+    ATX_COLOP_SCALAR = 16,
+    ATX_COLOP_COPY = 17,
+    ATX_COLOP_IS_NAN = 18,
+    ATX_COLOP_NOT = 19,
+    ATX_COLOP_CMP_GT = 20, /* 20 + atx_cmp: GT, LT, EQ, NE, GE, LE */
+    ATX_COLOP_CMP_LT = 21,
+    ATX_COLOP_CMP_EQ = 22,
+    ATX_COLOP_CMP_NE = 23,
+    ATX_COLOP_CMP_GE = 24,
+    ATX_COLOP_CMP_LE = 25,
+    ATX_COLOP_ABS_GT = 26,
+    ATX_COLOP_AND = 27,
+    ATX_COLOP_OR = 28,
+    ATX_COLOP_NAN_WHERE = 29,
+    ATX_COLOP_CLIP_LOW = 30,
+    ATX_COLOP_CLIP_HIGH = 31,
+    ATX_COLOP_FILL_NAN = 32
 };
 ATX_API int atx_obs_column_ops(int32_t n_ops, const int32_t* op, const int32_t* src, const double* const* in, double* const* out, int64_t n,
                                void* stream);
