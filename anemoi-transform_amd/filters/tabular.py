@@ -34,6 +34,10 @@ The QC filters mask, clip, fill and drop rows where recipes do it between those 
 row-dropping ones end in one gather of every column (``Table.take``).  What comes back is pandas' to the bit and to the dtype: a float32
 column is compared in float32 and stays float32, an integer column turns float64 only where a row was masked.
 
+``filter_query`` and ``mask_values_custom`` take pandas' query language (``query``: the parser, numpy's typing, the postfix compiler): the
+expression is one launch of the row-expression kernel (``obs.compile_query`` -> ``obs.query_rows`` / ``obs.eval_rows`` -> ``native.obs_row_expr``,
+``native.obs_keep_positions``), a row filter writes a bit per row and ends in the same gather.
+
 A table is a pandas DataFrame or a plain mapping ``name -> 1-D array / device tensor``.  Every ``forward`` wraps it in
 ``tables.Table``, which is where the table rule lives: which columns there are, where the launch runs, which columns are datetimes
 and what goes back to the caller — a DataFrame for a DataFrame, a new dict of device tensors if any column was a tensor, else of
@@ -67,8 +71,10 @@ Deviations from the reference, each said once when it first matters (``core.say_
     beyond which nothing is specially handled); a bool column raises ``ValueError``; ``mask_outside_range`` with ``[None, None]`` leaves
     the column as it is (the reference raises) and raises ``ValueError`` for a missing column (the reference: ``KeyError``);
     ``impute_nans_tabular`` cannot fill a datetime or string column of a mapping (``ValueError``; a DataFrame's goes through pandas).
-The other tabular filters of the reference (``filter_query``, ``mask_values_custom``, ``encode_statids``, the tabular ``rename``) are not built:
-DESIGN.md §7.
+  * ``filter_query`` / ``mask_values_custom``: what pandas takes beyond the language of ``query`` (``@local``, ``//``, ``%``, ``**``, other
+    functions, arithmetic or compares on booleans, datetimes) raises the reference's ``ValueError``; integers ride in float64 and never
+    wrap; the caller's table is not modified.
+The other tabular filters of the reference (``encode_statids``, the tabular ``rename``) are not built: DESIGN.md §7.
 """
 
 from __future__ import annotations
@@ -80,7 +86,7 @@ from typing import Any
 import numpy as np
 import torch
 
-from .. import healpix, obs
+from .. import healpix, obs, query
 from ..core import Filter, filter_registry, say_once
 from ..fields import MISSING, Field, FieldList, new_field_from_stack
 from ..grids import lookup
@@ -1149,6 +1155,92 @@ class DropNaNsTabular(Filter):
         return t.take(obs.keep_rows(table, program, dev=t.device, rows=rows))
 
 
+# ---- the query language: filter_query and mask_values_custom on the row-expression kernel ------------------------------------------------
+def _query_dtypes(t: Table) -> dict[str, Any]:
+    """Every column's dtype as the query compiler reads it: datetimes say so (an int64 tensor named ``date`` is one)."""
+    return {name: (np.dtype("datetime64[ns]") if t.is_datetime(name) else dtype) for name, dtype in _dtypes(t, t.names).items()}
+
+
+class FilterQuery(Filter):
+    """``table.query(query)`` (R: filters/tabular/filter_query.py:19-92): the rows where the expression holds, in the table's order.  The
+    language is pandas' (``query``: names, numbers, ``+ - * /``, ``abs``, compares and chains, ``in`` / ``not in`` lists, ``and or not``, ``&``
+    / ``|``, backticks; a string column against string literals); the typing is numpy's, so a float32 column compares and computes in
+    float32.  The expression is ONE launch that writes a bit per row (``obs.compile_query`` -> ``obs.query_rows`` -> ``native.obs_row_expr``,
+    ``native.obs_keep_positions``); the kept rows are taken in one gather of every column (``Table.take``; ``iloc`` for a DataFrame).  Every
+    error is the reference's ``ValueError("Invalid query expression: ...")``.
+
+    Deviations: what pandas accepts beyond the language above (``@local``, ``//``, ``%``, ``**``, other functions, arithmetic on booleans,
+    datetimes) raises that ``ValueError``; integers ride in float64 (exact below 2^53, never wrapped)."""
+
+    def __init__(self, *, query: str) -> None:
+        if not query:
+            raise ValueError("Query expression cannot be empty")
+        self.query = query
+        _qc_note(type(self))
+
+    def __repr__(self) -> str:
+        return f"FilterQuery({self.query!r})"
+
+    def forward(self, table: Any) -> Any:
+        t = Table(table)
+        try:
+            program = obs.compile_query(self.query, _query_dtypes(t))
+        except ValueError as e:
+            raise ValueError(f"Invalid query expression: {self.query}. Error: {e}") from None
+        return t.take(obs.query_rows(table, program, dev=t.device))
+
+
+class MaskValuesCustom(_MaskFilter):
+    """NaN in a column where a query-style condition over any columns holds (R: filters/tabular/mask_values_custom.py:20-67).  ``**config``
+    maps a column to its condition, in the language of ``filter_query``.  Conditions apply IN ORDER: a later one sees an earlier one's
+    masked column.  They are one launch when they fit one program (``query.compile_masks`` -> ``obs.eval_rows`` -> ``native.obs_row_expr``:
+    sequential ``NAN_WHERE``s, the masked columns on the stack), one launch per condition otherwise.  Dtypes as ``mask_tabular``: a float
+    column keeps its dtype, an integer column comes back float64 if a row was masked and unchanged otherwise.  A missing target column
+    raises ``ValueError`` (``Table.require``), anything wrong with a condition the reference's ``ValueError("Invalid condition for column
+    ...")``."""
+
+    def __init__(self, **config: Any) -> None:
+        if not config:
+            raise ValueError("No columns to mask were specified.")
+        self.config = dict(config)
+        _qc_note(type(self))
+
+    def __repr__(self) -> str:
+        return f"MaskValuesCustom({self.config})"
+
+    def _compile(self, conditions: list, dtypes: dict[str, Any]) -> obs.ExprProgram:
+        try:
+            return query.compile_masks(conditions, dtypes)
+        except query.SplitNeeded:
+            raise
+        except ValueError as e:
+            raise ValueError(f"Invalid condition for column '{conditions[-1][0]}': {conditions[-1][1]}. Error: {e}") from None
+
+    def forward(self, table: Any) -> Any:
+        t = Table(table)
+        t.require(list(self.config))
+        conditions = [(col, text) for col, text in self.config.items()]
+        dtypes = _query_dtypes(t)
+        for one in conditions:  # every condition's own errors first, by its own name, before anything touches the device
+            self._compile([one], dtypes)
+        try:
+            programs = [self._compile(conditions, dtypes)]
+        except ValueError:  # too large for one launch, or conditions that cannot share one: one launch each
+            programs = None
+        if t.n_rows == 0:
+            return table.copy() if t.frame else dict(table)
+        if programs is not None:
+            return t.replaced(_narrowed(obs.eval_rows(table, programs[0], dev=t.device), dtypes, "nan"))
+        current, done = dict(table) if not t.frame else {name: table[name] for name in t.names}, {}
+        for col, text in conditions:
+            rows = _narrowed(obs.eval_rows(current, self._compile([(col, text)], dtypes), dev=t.device), {col: dtypes[col]}, "nan")
+            for name, row in rows.items():  # an integer column that lost a row is float64 from here on
+                current[name], done[name], dtypes[name] = row, row, row.dtype
+        return t.replaced(done)
+
+
+filter_registry.register("filter_query", FilterQuery)
+filter_registry.register("mask_values_custom", MaskValuesCustom)
 filter_registry.register("mask_tabular", MaskValues)
 filter_registry.register("mask_outside_range", MaskOutsideRange)
 filter_registry.register("mask_infs", MaskInfs)

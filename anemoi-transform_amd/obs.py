@@ -41,6 +41,10 @@ exclude_dates.py, remove_extreme_values.py, clip.py, impute_nans.py, drop_nans.p
 .. ``compile_keep_not_missing``) turns its configuration and the column dtypes into a ``RowProgram`` — launches of at most 16 slots of the
 row operations ``native.ROW_OPS``, pure host logic — ``row_program`` runs it (``atx_obs_column_ops``, the row-program kernel) and
 ``keep_rows`` lists the rows a row-dropping filter keeps.
+
+The eighth is ``filter_query`` and ``mask_values_custom`` (R: filters/tabular/filter_query.py, mask_values_custom.py): ``compile_query``
+turns pandas' query text into an ``ExprProgram`` (``query``: parser, numpy's typing, Sethi-Ullman postfix order), ``query_rows`` runs it and
+lists the rows it keeps (``native.obs_row_expr``: one bit per row; ``native.obs_keep_positions``: the third family of ``atx_obs_column_ops`` codes), ``eval_rows`` returns its value rows.
 """
 
 from __future__ import annotations
@@ -54,6 +58,7 @@ import numpy as np
 import torch
 
 from . import native
+from . import query as _query
 from . import stack as _stack
 from .stack import COLUMNS, Stack
 from .tables import NAT, datetime_ns, float_column, host_array, launch_device, take_rows, to_ns  # noqa: F401
@@ -1106,3 +1111,76 @@ def keep_rows(columns: Mapping[str, Any], program: RowProgram, dev: torch.device
               rows: Mapping[str, torch.Tensor] | None = None) -> torch.Tensor:
     """The ascending int64 device positions of the rows a keep-row program keeps (its ``%keep`` row is not 0)."""
     return torch.nonzero(row_program(columns, program, dev, rows)[KEEP_ROW]).reshape(-1)
+
+
+# ---- row expressions: filter_query and mask_values_custom (R: filters/tabular/filter_query.py, mask_values_custom.py) --------------------
+ExprProgram = _query.ExprProgram
+
+
+def compile_query(text: str, dtypes: Mapping[str, Any]) -> ExprProgram:
+    """The keep-row program of ``DataFrame.query(text)`` for columns of the dtypes ``dtypes`` (``query.compile_query``: the language, numpy's
+    typing and the limits are stated there).  Pure host logic; raises ``ValueError``."""
+    return _query.compile_query(text, dtypes)
+
+
+def _expr_inputs(columns: Mapping[str, Any], program: ExprProgram, dev: torch.device, rows: Mapping[str, torch.Tensor] | None) -> list[torch.Tensor]:
+    """The program's input rows: a ``%`` row the caller provides, a string leaf evaluated on the host (0 / 1), a bool column as 0 / 1, any
+    other column through ``float_column`` (a float64 device tensor is used in place)."""
+    inputs = []
+    for name in program.inputs:
+        if rows and name in rows:
+            inputs.append(rows[name])
+        elif name.startswith(_query.HOST_ROW):
+            leaf = program.host[int(name[len(_query.HOST_ROW):])]
+            inputs.append(_device(_query.host_leaf(leaf, host_array(columns[leaf.column])).astype(np.float64), dev))
+        elif _dtype_kind(columns[name].dtype if isinstance(columns[name], torch.Tensor) else host_array(columns[name]).dtype) == "b":
+            column = columns[name] if isinstance(columns[name], torch.Tensor) else torch.from_numpy(np.ascontiguousarray(host_array(columns[name])))
+            inputs.append(column.reshape(-1).to(device=dev, dtype=torch.float64).contiguous())
+        else:
+            inputs.append(float_column(columns[name], dev))
+    if len({c.numel() for c in inputs}) > 1:
+        raise ValueError(f"columns differ in length: { {name: c.numel() for name, c in zip(program.inputs, inputs)} }")
+    return inputs
+
+
+def _expr_code(program: ExprProgram) -> list[tuple[int, int, int]]:
+    return [(native.EXPR_OPS[op], a, b) for op, a, b in program.code]
+
+
+def _n_rows(columns: Mapping[str, Any], inputs: Sequence[torch.Tensor]) -> int:
+    if inputs:
+        return inputs[0].numel()
+    return len(columns) if hasattr(columns, "columns") else next((len(columns[name]) for name in columns.keys()), 0)
+
+
+def query_rows(columns: Mapping[str, Any], program: ExprProgram, dev: torch.device | None = None,
+               rows: Mapping[str, torch.Tensor] | None = None) -> torch.Tensor:
+    """The ascending int64 device positions of the rows a keep program keeps: ONE launch of ``native.obs_row_expr`` writes a bit per row and a
+    count per chunk of ``native.EXPR_CHUNK_ROWS`` rows, ``torch.cumsum`` scans the counts (its last element, read once on the host,
+    sizes the result — the one synchronisation), and ``native.obs_keep_positions`` expands the bits."""
+    assert program.keep and not program.results
+    dev = launch_device([*(columns[name] for name in columns.keys()), *(rows or {}).values()], dev)
+    inputs = _expr_inputs(columns, program, dev, rows)
+    n = _n_rows(columns, inputs)
+    if n == 0:
+        return torch.empty(0, dtype=torch.int64, device=dev)
+    words = torch.empty((n + 63) // 64, dtype=torch.int64, device=dev)
+    counts = torch.empty((n + native.EXPR_CHUNK_ROWS - 1) // native.EXPR_CHUNK_ROWS, dtype=torch.int64, device=dev)
+    native.obs_row_expr(_expr_code(program), inputs, program.consts, [], n, keep_words=words, chunk_counts=counts)
+    ends = torch.cumsum(counts, 0)
+    positions = torch.empty(int(ends[-1]), dtype=torch.int64, device=dev)
+    native.obs_keep_positions(words, ends - counts, n, positions)
+    return positions
+
+
+def eval_rows(columns: Mapping[str, Any], program: ExprProgram, dev: torch.device | None = None,
+              rows: Mapping[str, torch.Tensor] | None = None) -> dict[str, torch.Tensor]:
+    """``{name: float64 device row}`` of a program's value results (``query.compile_masks``), one launch; every result is a fresh row."""
+    assert program.results and not program.keep
+    dev = launch_device([*(columns[name] for name in columns.keys()), *(rows or {}).values()], dev)
+    inputs = _expr_inputs(columns, program, dev, rows)
+    n = _n_rows(columns, inputs)
+    outs = [torch.empty(n, dtype=torch.float64, device=dev) for _ in program.results]
+    if n:
+        native.obs_row_expr(_expr_code(program), inputs, program.consts, outs, n)
+    return dict(zip(program.results, outs))
