@@ -1,6 +1,5 @@
 // Library-level entry points of libatx: version, error strings, device probe.
 #include "atx_common.hpp"
-#include "atx_obs_rows.hpp"
 
 #include <cstring>
 #include <string>
@@ -153,90 +152,3 @@ extern "C" int atx_stream_copy(const void* src, void* dst, int64_t n_bytes, void
     ATX_LAUNCH_CHECK("stream_copy");
     return ATX_OK;
 }
-
-// ---- row expressions: the third family of atx_obs_column_ops' codes.  atx_obs_column_ops.hip reads the slots into the flat program
-// ---- that is validated here; the kernels are in atx_obs_row_expr.hip --------------------------------------------------------------------
-namespace atx {
-
-int obs_row_expr_call(int32_t n_instr, const int32_t* code, const int32_t* arg0, const int32_t* arg1, int32_t n_inputs,
-                      const double* const* in, int32_t n_consts, const double* consts, int32_t n_results, double* const* out, bool keep,
-                      uint64_t* keep_words, int64_t* chunk_counts, int64_t n, void* stream) {
-    ATX_REQUIRE(n >= 0, ATX_EINVAL, "atx_obs_column_ops, row expression: %lld rows", (long long)n);
-    ATX_REQUIRE(code && arg0 && arg1, ATX_EINVAL, "atx_obs_column_ops, row expression: null program array");
-    ATX_REQUIRE(n_instr >= 1 && n_instr <= ATX_EXPR_MAX_INSTR, ATX_EINVAL, "atx_obs_column_ops, row expression: 1 .. %d instructions, got %d", ATX_EXPR_MAX_INSTR,
-                (int)n_instr);
-    ATX_REQUIRE(n_inputs >= 0 && n_inputs <= ATX_EXPR_MAX_INPUTS, ATX_EINVAL, "atx_obs_column_ops, row expression: 0 .. %d input columns, got %d",
-                ATX_EXPR_MAX_INPUTS, (int)n_inputs);
-    ATX_REQUIRE(n_consts >= 0 && n_consts <= ATX_EXPR_MAX_CONSTS, ATX_EINVAL, "atx_obs_column_ops, row expression: 0 .. %d constants, got %d", ATX_EXPR_MAX_CONSTS,
-                (int)n_consts);
-    ATX_REQUIRE(n_results >= 0 && n_results <= ATX_EXPR_MAX_RESULTS, ATX_EINVAL, "atx_obs_column_ops, row expression: 0 .. %d value results, got %d",
-                ATX_EXPR_MAX_RESULTS, (int)n_results);
-    ATX_REQUIRE(n_results > 0 || keep, ATX_EINVAL, "atx_obs_column_ops, row expression: neither a value result nor keep_words is asked for");
-    ATX_REQUIRE((in || n_inputs == 0) && (consts || n_consts == 0) && (out || n_results == 0), ATX_EINVAL, "atx_obs_column_ops, row expression: null table");
-    ATX_REQUIRE(!keep || (keep_words && chunk_counts) || n == 0, ATX_EINVAL, "atx_obs_column_ops, row expression: a null keep_words or chunk_counts row");
-    ExprProgram p = {};
-    int depth = 0;
-    for (int t = 0; t < n_instr; ++t) {
-        const int op = code[t];
-        ATX_REQUIRE(op >= ATX_EXPR_PUSH_COL && op <= ATX_EXPR_NAN_WHERE, ATX_EINVAL, "atx_obs_column_ops, row expression: instruction %d has the unknown code %d", t, op);
-        int pops = 1, pushes = 1;  // the unary ones
-        if (op == ATX_EXPR_PUSH_COL) {
-            ATX_REQUIRE(arg0[t] >= 0 && arg0[t] < n_inputs, ATX_EINVAL, "atx_obs_column_ops, row expression: instruction %d reads column %d of %d", t, (int)arg0[t],
-                        (int)n_inputs);
-            pops = 0;
-        } else if (op == ATX_EXPR_PUSH_CONST) {
-            ATX_REQUIRE(arg0[t] >= 0 && arg0[t] < n_consts, ATX_EINVAL, "atx_obs_column_ops, row expression: instruction %d reads constant %d of %d", t,
-                        (int)arg0[t], (int)n_consts);
-            pops = 0;
-        } else if (op == ATX_EXPR_DUP) {
-            ATX_REQUIRE(arg0[t] >= 0 && arg0[t] < depth, ATX_EINVAL, "atx_obs_column_ops, row expression: instruction %d copies the value %d below the top of a stack of %d: stack underflow",
-                        t, (int)arg0[t], depth);
-            pops = 0;
-        } else if (op == ATX_EXPR_IN_SET) {
-            ATX_REQUIRE(arg0[t] >= 0 && arg1[t] >= 1 && (int64_t)arg0[t] + arg1[t] <= n_consts, ATX_EINVAL,
-                        "atx_obs_column_ops, row expression: instruction %d: the IN_SET slice [%d, %d + %d) lies outside the table of %d constants", t, (int)arg0[t],
-                        (int)arg0[t], (int)arg1[t], (int)n_consts);
-        } else if (op == ATX_EXPR_SWAP) {
-            pops = pushes = 2;
-        } else if (op != ATX_EXPR_NEG && op != ATX_EXPR_ABS && op != ATX_EXPR_ROUND_F32 && op != ATX_EXPR_NOT) {
-            pops = 2;  // + - * /, the compares, AND, OR, NAN_WHERE
-        }
-        ATX_REQUIRE(depth >= pops, ATX_EINVAL, "atx_obs_column_ops, row expression: instruction %d (code %d) takes %d values of a stack of %d: stack underflow", t, op,
-                    pops, depth);
-        depth += pushes - pops;
-        ATX_REQUIRE(depth <= ATX_EXPR_MAX_STACK, ATX_EINVAL, "atx_obs_column_ops, row expression: instruction %d: stack overflow, the depth is at most %d", t,
-                    ATX_EXPR_MAX_STACK);
-        p.code[t] = op;
-        p.arg0[t] = arg0[t];
-        p.arg1[t] = op == ATX_EXPR_IN_SET ? arg1[t] : 0;
-    }
-    ATX_REQUIRE(depth == n_results + (keep ? 1 : 0), ATX_EINVAL,
-                "atx_obs_column_ops, row expression: the program leaves %d values, %d value results%s are asked for", depth, (int)n_results,
-                keep ? " and a keep condition" : "");
-    for (int k = 0; k < n_inputs; ++k) {
-        ATX_REQUIRE(in[k] || n == 0, ATX_EINVAL, "atx_obs_column_ops, row expression: input column %d is null", k);
-        p.in[k] = in[k];
-    }
-    for (int r = 0; r < n_results; ++r) {
-        ATX_REQUIRE(out[r] || n == 0, ATX_EINVAL, "atx_obs_column_ops, row expression: output row %d is null", r);
-        p.out[r] = out[r];
-    }
-    for (int k = 0; k < n_consts; ++k) p.consts[k] = consts[k];
-    p.n_instr = n_instr;
-    p.n_results = n_results;
-    p.keep_words = keep ? reinterpret_cast<unsigned long long*>(keep_words) : nullptr;
-    p.chunk_counts = keep ? chunk_counts : nullptr;
-    if (n == 0) return ATX_OK;
-    return launch_obs_row_expr(p, n, static_cast<hipStream_t>(stream));
-}
-
-int obs_keep_positions_call(const uint64_t* words, const int64_t* chunk_offsets, int64_t n, int64_t* positions, int64_t n_positions,
-                            void* stream) {
-    ATX_REQUIRE(n >= 0 && n_positions >= 0, ATX_EINVAL, "atx_obs_column_ops, keep positions: %lld rows, %lld positions", (long long)n, (long long)n_positions);
-    if (n == 0 || n_positions == 0) return ATX_OK;
-    ATX_REQUIRE(words && chunk_offsets && positions, ATX_EINVAL, "atx_obs_column_ops, keep positions: null pointer");
-    return launch_obs_keep_positions(reinterpret_cast<const unsigned long long*>(words), chunk_offsets, n, positions, n_positions,
-                                     static_cast<hipStream_t>(stream));
-}
-
-}  // namespace atx

@@ -22,8 +22,6 @@
 // QC filters (atx_obs_row_program.hip).  A program is of one family; the check below decides which kernel runs.
 #include "atx_obs_rows.hpp"
 
-#include <functional>
-
 namespace atx {
 
 __device__ __forceinline__ double column_op(int op, double x) {
@@ -70,106 +68,9 @@ __global__ void __launch_bounds__(kBlock) obs_column_ops_kernel(const ColumnProg
 
 using namespace atx;
 
-// The third family: a postfix row-expression program, its results and its keep rows, or a keep-positions call, written as slots
-// (include/atx.h).  The slots are read into the flat program that obs_row_expr_call validates: columns by their pointers (one input per
-// distinct pointer), constants by value from the HOST doubles in[t] points to.
-static int expr_slots(int32_t n_ops, const int32_t* op, const int32_t* src, const double* const* in, double* const* out, int64_t n, void* stream) {
-    ATX_REQUIRE(n_ops <= ATX_EXPR_MAX_SLOTS, ATX_EINVAL, "atx_obs_column_ops, row expression: 1 .. %d slots, got %d", ATX_EXPR_MAX_SLOTS, (int)n_ops);
-    ATX_REQUIRE(src && in && out, ATX_EINVAL, "atx_obs_column_ops: null program array");
-    if (op[0] == ATX_COLOP_KEEP_POSITIONS) {
-        ATX_REQUIRE(n_ops == 2 && op[1] == ATX_COLOP_KEEP_OFFSETS && src[0] >= 0 && src[1] >= 0, ATX_EINVAL,
-                    "atx_obs_column_ops, keep positions: two slots, KEEP_POSITIONS and KEEP_OFFSETS, with the capacity in src, not negative");
-        return obs_keep_positions_call(reinterpret_cast<const uint64_t*>(in[0]), reinterpret_cast<const int64_t*>(in[1]), n,
-                                       reinterpret_cast<int64_t*>(out[0]), (int64_t)src[0] + ((int64_t)src[1] << 31), stream);
-    }
-    int32_t code[ATX_EXPR_MAX_INSTR], arg0[ATX_EXPR_MAX_INSTR], arg1[ATX_EXPR_MAX_INSTR];
-    const double* cols[ATX_EXPR_MAX_INPUTS];
-    double consts[ATX_EXPR_MAX_CONSTS];
-    double* outs[ATX_EXPR_MAX_RESULTS];
-    int n_instr = 0, n_in = 0, n_consts = 0, n_results = 0;
-    // The constants first: the host ranges the PUSH_CONST and IN_SET slots point to, merged where they overlap or touch (slices of one
-    // table are held once), copied in address order.
-    const double* lo[ATX_EXPR_MAX_SLOTS];
-    const double* hi[ATX_EXPR_MAX_SLOTS];
-    int where[ATX_EXPR_MAX_SLOTS];
-    int n_ranges = 0;
-    for (int t = 0; t < n_ops; ++t) {
-        const int e = op[t] - ATX_COLOP_EXPR;
-        if (e != ATX_EXPR_PUSH_CONST && e != ATX_EXPR_IN_SET) continue;
-        const int count = e == ATX_EXPR_IN_SET ? src[t] : 1;
-        ATX_REQUIRE(in[t] && count >= 1, ATX_EINVAL, "atx_obs_column_ops, row expression: slot %d: a constant or IN_SET slot points to %d host doubles", t,
-                    count);
-        int k = n_ranges++;
-        for (; k > 0 && std::less<const double*>()(in[t], lo[k - 1]); --k) {
-            lo[k] = lo[k - 1];
-            hi[k] = hi[k - 1];
-        }
-        lo[k] = in[t];
-        hi[k] = in[t] + count;
-    }
-    int n_merged = 0;
-    for (int k = 0; k < n_ranges; ++k) {
-        if (n_merged > 0 && !std::less<const double*>()(hi[n_merged - 1], lo[k])) {
-            if (std::less<const double*>()(hi[n_merged - 1], hi[k])) hi[n_merged - 1] = hi[k];
-        } else {
-            lo[n_merged] = lo[k];
-            hi[n_merged++] = hi[k];
-        }
-    }
-    for (int k = 0; k < n_merged; ++k) {
-        where[k] = n_consts;
-        ATX_REQUIRE(hi[k] - lo[k] <= ATX_EXPR_MAX_CONSTS - n_consts, ATX_EINVAL, "atx_obs_column_ops, row expression: 0 .. %d constants", ATX_EXPR_MAX_CONSTS);
-        for (const double* c = lo[k]; c != hi[k]; ++c) consts[n_consts++] = *c;
-    }
-    bool keep = false;
-    uint64_t* words = nullptr;
-    int64_t* counts = nullptr;
-    for (int t = 0; t < n_ops; ++t) {
-        ATX_REQUIRE(!keep, ATX_EINVAL, "atx_obs_column_ops, row expression: slot %d follows the KEEP slot, which is the last", t);
-        if (op[t] == ATX_COLOP_EXPR_RESULT) {
-            ATX_REQUIRE(n_results < ATX_EXPR_MAX_RESULTS, ATX_EINVAL, "atx_obs_column_ops, row expression: 0 .. %d value results", ATX_EXPR_MAX_RESULTS);
-            ATX_REQUIRE(src[t] == n_results, ATX_EINVAL, "atx_obs_column_ops, row expression: RESULT slots name the stack slots 0, 1, .. in order, got %d",
-                        (int)src[t]);
-            outs[n_results++] = out[t];
-            continue;
-        }
-        if (op[t] == ATX_COLOP_EXPR_KEEP) {
-            keep = true;
-            words = reinterpret_cast<uint64_t*>(out[t]);
-            counts = reinterpret_cast<int64_t*>(const_cast<double*>(in[t]));
-            continue;
-        }
-        const int e = op[t] - ATX_COLOP_EXPR;
-        ATX_REQUIRE(e >= ATX_EXPR_PUSH_COL && e <= ATX_EXPR_NAN_WHERE, ATX_EINVAL, "atx_obs_column_ops, row expression: slot %d has the unknown code %d", t,
-                    (int)op[t]);
-        ATX_REQUIRE(n_results == 0, ATX_EINVAL, "atx_obs_column_ops, row expression: instruction slot %d follows a RESULT slot", t);
-        ATX_REQUIRE(n_instr < ATX_EXPR_MAX_INSTR, ATX_EINVAL, "atx_obs_column_ops, row expression: 1 .. %d instructions", ATX_EXPR_MAX_INSTR);
-        int a0 = src[t], a1 = 0;
-        if (e == ATX_EXPR_PUSH_COL) {
-            ATX_REQUIRE(in[t] || n == 0, ATX_EINVAL, "atx_obs_column_ops, row expression: slot %d pushes a null input column", t);
-            for (a0 = 0; a0 < n_in && cols[a0] != in[t]; ++a0) {
-            }
-            if (a0 == n_in) {
-                ATX_REQUIRE(n_in < ATX_EXPR_MAX_INPUTS, ATX_EINVAL, "atx_obs_column_ops, row expression: 0 .. %d input columns", ATX_EXPR_MAX_INPUTS);
-                cols[n_in++] = in[t];
-            }
-        } else if (e == ATX_EXPR_PUSH_CONST || e == ATX_EXPR_IN_SET) {
-            int k = 0;  // the merged range that holds this slot's
-            while (std::less<const double*>()(in[t], lo[k]) || !std::less<const double*>()(in[t], hi[k])) ++k;
-            a0 = where[k] + (int)(in[t] - lo[k]);
-            a1 = e == ATX_EXPR_IN_SET ? src[t] : 0;
-        }
-        code[n_instr] = e;
-        arg0[n_instr] = a0;
-        arg1[n_instr++] = a1;
-    }
-    return obs_row_expr_call(n_instr, code, arg0, arg1, n_in, cols, n_consts, consts, n_results, outs, keep, words, counts, n, stream);
-}
-
 extern "C" int atx_obs_column_ops(int32_t n_ops, const int32_t* op, const int32_t* src, const double* const* in, double* const* out, int64_t n,
                                   void* stream) {
     ATX_REQUIRE(n >= 0, ATX_EINVAL, "atx_obs_column_ops: %lld rows", (long long)n);
-    if (op && n_ops >= 1 && op[0] >= ATX_COLOP_EXPR) return expr_slots(n_ops, op, src, in, out, n, static_cast<hipStream_t>(stream));
     ATX_REQUIRE(n_ops >= 1 && n_ops <= ATX_MAX_COLUMN_OPS, ATX_EINVAL, "atx_obs_column_ops: 1 .. %d operations, got %d", ATX_MAX_COLUMN_OPS,
                 (int)n_ops);
     ATX_REQUIRE(op && src && in && out, ATX_EINVAL, "atx_obs_column_ops: null program array");

@@ -1,5 +1,6 @@
 // filter_query and mask_values_custom: a POSTFIX expression program over float64 columns, one launch, and the
-// ascending positions of the rows it keeps, a second one: the third family of atx_obs_column_ops' codes (ATX_COLOP_EXPR ..).  The instruction set is atx_expr_op (include/atx.h): pushes of a
+// ascending positions of the rows it keeps, a second one: atx_obs_row_expr and atx_obs_keep_positions, with their argument checks at the
+// end of this file.  The instruction set is atx_expr_op (include/atx.h): pushes of a
 // column or a constant, + - * /, negate, abs, round-to-float32, the six compares, membership in a slice of the constant table, and /
 // or / not, DUP / SWAP for chained compares, and NAN_WHERE for Series.mask.
 //
@@ -35,6 +36,21 @@ static_assert(ATX_EXPR_CHUNK_ROWS == kBlock, "one workgroup iteration owns one c
 static_assert(kBlock % kWave == 0, "whole waves");
 constexpr int kBelow = ATX_EXPR_MAX_STACK - 1;  // the slots under the top register
 constexpr int kChunkWords = ATX_EXPR_CHUNK_ROWS / kWave;
+
+// The program of one launch, by value in the kernel arguments (about 1.1 KB).  Everything indexed at run time is dwords or qwords, so a
+// scalar load fetches it.
+struct ExprProgram {
+    const double* in[ATX_EXPR_MAX_INPUTS];
+    double* out[ATX_EXPR_MAX_RESULTS];
+    double consts[ATX_EXPR_MAX_CONSTS];
+    int32_t code[ATX_EXPR_MAX_INSTR];
+    int32_t arg0[ATX_EXPR_MAX_INSTR];
+    int32_t arg1[ATX_EXPR_MAX_INSTR];
+    int32_t n_instr;
+    int32_t n_results;
+    unsigned long long* keep_words;  // with its chunk_counts, or both null
+    int64_t* chunk_counts;
+};
 
 // Seven separate locals, not an array or a struct: the compiler folds a select chain over the members of ONE private object back into
 // a load at a run-time offset, and then moves the object into LDS (14 KB per workgroup) or scratch.
@@ -174,17 +190,91 @@ __global__ void __launch_bounds__(kBlock) obs_keep_positions_kernel(const unsign
     }
 }
 
-int launch_obs_row_expr(const ExprProgram& p, int64_t n, hipStream_t stream) {
-    hipLaunchKernelGGL(obs_row_expr_kernel, dim3(row_grid(n)), dim3(kBlock), 0, stream, p, n);
+}  // namespace atx
+
+using namespace atx;
+
+// Everything is validated, the stack depth by simulation, before anything touches HIP.
+extern "C" int atx_obs_row_expr(int32_t n_instr, const int32_t* code, const int32_t* arg0, const int32_t* arg1, int32_t n_inputs,
+                                const double* const* in, int32_t n_consts, const double* consts, int32_t n_results, double* const* out, int keep,
+                                uint64_t* keep_words, int64_t* chunk_counts, int64_t n, void* stream) {
+    ATX_REQUIRE(n >= 0, ATX_EINVAL, "atx_obs_row_expr: %lld rows", (long long)n);
+    ATX_REQUIRE(code && arg0 && arg1, ATX_EINVAL, "atx_obs_row_expr: null program array");
+    ATX_REQUIRE(n_instr >= 1 && n_instr <= ATX_EXPR_MAX_INSTR, ATX_EINVAL, "atx_obs_row_expr: 1 .. %d instructions, got %d", ATX_EXPR_MAX_INSTR,
+                (int)n_instr);
+    ATX_REQUIRE(n_inputs >= 0 && n_inputs <= ATX_EXPR_MAX_INPUTS, ATX_EINVAL, "atx_obs_row_expr: 0 .. %d input columns, got %d", ATX_EXPR_MAX_INPUTS,
+                (int)n_inputs);
+    ATX_REQUIRE(n_consts >= 0 && n_consts <= ATX_EXPR_MAX_CONSTS, ATX_EINVAL, "atx_obs_row_expr: 0 .. %d constants, got %d", ATX_EXPR_MAX_CONSTS,
+                (int)n_consts);
+    ATX_REQUIRE(n_results >= 0 && n_results <= ATX_EXPR_MAX_RESULTS, ATX_EINVAL, "atx_obs_row_expr: 0 .. %d value results, got %d",
+                ATX_EXPR_MAX_RESULTS, (int)n_results);
+    ATX_REQUIRE(n_results > 0 || keep, ATX_EINVAL, "atx_obs_row_expr: neither a value result nor a keep condition is asked for");
+    ATX_REQUIRE((in || n_inputs == 0) && (consts || n_consts == 0) && (out || n_results == 0), ATX_EINVAL, "atx_obs_row_expr: null table");
+    ATX_REQUIRE(!keep || (keep_words && chunk_counts) || n == 0, ATX_EINVAL, "atx_obs_row_expr: a null keep_words or chunk_counts row");
+    ExprProgram p = {};
+    int depth = 0;
+    for (int t = 0; t < n_instr; ++t) {
+        const int op = code[t];
+        ATX_REQUIRE(op >= ATX_EXPR_PUSH_COL && op <= ATX_EXPR_NAN_WHERE, ATX_EINVAL, "atx_obs_row_expr: instruction %d has the unknown code %d", t, op);
+        int pops = 1, pushes = 1;  // the unary ones
+        if (op == ATX_EXPR_PUSH_COL) {
+            ATX_REQUIRE(arg0[t] >= 0 && arg0[t] < n_inputs, ATX_EINVAL, "atx_obs_row_expr: instruction %d reads column %d of %d", t, (int)arg0[t],
+                        (int)n_inputs);
+            pops = 0;
+        } else if (op == ATX_EXPR_PUSH_CONST) {
+            ATX_REQUIRE(arg0[t] >= 0 && arg0[t] < n_consts, ATX_EINVAL, "atx_obs_row_expr: instruction %d reads constant %d of %d", t, (int)arg0[t],
+                        (int)n_consts);
+            pops = 0;
+        } else if (op == ATX_EXPR_DUP) {
+            ATX_REQUIRE(arg0[t] >= 0 && arg0[t] < depth, ATX_EINVAL,
+                        "atx_obs_row_expr: instruction %d copies the value %d below the top of a stack of %d: stack underflow", t, (int)arg0[t], depth);
+            pops = 0;
+        } else if (op == ATX_EXPR_IN_SET) {
+            ATX_REQUIRE(arg0[t] >= 0 && arg1[t] >= 1 && (int64_t)arg0[t] + arg1[t] <= n_consts, ATX_EINVAL,
+                        "atx_obs_row_expr: instruction %d: the IN_SET slice [%d, %d + %d) lies outside the table of %d constants", t, (int)arg0[t],
+                        (int)arg0[t], (int)arg1[t], (int)n_consts);
+        } else if (op == ATX_EXPR_SWAP) {
+            pops = pushes = 2;
+        } else if (op != ATX_EXPR_NEG && op != ATX_EXPR_ABS && op != ATX_EXPR_ROUND_F32 && op != ATX_EXPR_NOT) {
+            pops = 2;  // + - * /, the compares, AND, OR, NAN_WHERE
+        }
+        ATX_REQUIRE(depth >= pops, ATX_EINVAL, "atx_obs_row_expr: instruction %d (code %d) takes %d values of a stack of %d: stack underflow", t, op, pops,
+                    depth);
+        depth += pushes - pops;
+        ATX_REQUIRE(depth <= ATX_EXPR_MAX_STACK, ATX_EINVAL, "atx_obs_row_expr: instruction %d: stack overflow, the depth is at most %d", t,
+                    ATX_EXPR_MAX_STACK);
+        p.code[t] = op;
+        p.arg0[t] = arg0[t];
+        p.arg1[t] = op == ATX_EXPR_IN_SET ? arg1[t] : 0;
+    }
+    ATX_REQUIRE(depth == n_results + (keep ? 1 : 0), ATX_EINVAL, "atx_obs_row_expr: the program leaves %d values, %d value results%s are asked for", depth,
+                (int)n_results, keep ? " and a keep condition" : "");
+    for (int k = 0; k < n_inputs; ++k) {
+        ATX_REQUIRE(in[k] || n == 0, ATX_EINVAL, "atx_obs_row_expr: null input column %d", k);
+        p.in[k] = in[k];
+    }
+    for (int r = 0; r < n_results; ++r) {
+        ATX_REQUIRE(out[r] || n == 0, ATX_EINVAL, "atx_obs_row_expr: output row %d is null", r);
+        p.out[r] = out[r];
+    }
+    for (int k = 0; k < n_consts; ++k) p.consts[k] = consts[k];
+    p.n_instr = n_instr;
+    p.n_results = n_results;
+    p.keep_words = keep ? reinterpret_cast<unsigned long long*>(keep_words) : nullptr;
+    p.chunk_counts = keep ? chunk_counts : nullptr;
+    if (n == 0) return ATX_OK;
+    hipLaunchKernelGGL(obs_row_expr_kernel, dim3(row_grid(n)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), p, n);
     ATX_LAUNCH_CHECK("obs_row_expr");
     return ATX_OK;
 }
 
-int launch_obs_keep_positions(const unsigned long long* words, const int64_t* chunk_offsets, int64_t n, int64_t* positions, int64_t n_positions,
-                              hipStream_t stream) {
-    hipLaunchKernelGGL(obs_keep_positions_kernel, dim3(row_grid(n)), dim3(kBlock), 0, stream, words, chunk_offsets, n, positions, n_positions);
+extern "C" int atx_obs_keep_positions(const uint64_t* keep_words, const int64_t* chunk_offsets, int64_t n, int64_t* positions, int64_t n_positions,
+                                      void* stream) {
+    ATX_REQUIRE(n >= 0 && n_positions >= 0, ATX_EINVAL, "atx_obs_keep_positions: %lld rows, %lld positions", (long long)n, (long long)n_positions);
+    if (n == 0 || n_positions == 0) return ATX_OK;
+    ATX_REQUIRE(keep_words && chunk_offsets && positions, ATX_EINVAL, "atx_obs_keep_positions: null pointer");
+    hipLaunchKernelGGL(obs_keep_positions_kernel, dim3(row_grid(n)), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
+                       reinterpret_cast<const unsigned long long*>(keep_words), chunk_offsets, n, positions, n_positions);
     ATX_LAUNCH_CHECK("obs_keep_positions");
     return ATX_OK;
 }
-
-}  // namespace atx

@@ -125,6 +125,12 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
          c_void_p, c_void_p, c_void_p],
     ),
     "atx_obs_column_ops": (c_int, [c_int32, POINTER(c_int32), POINTER(c_int32), POINTER(c_void_p), POINTER(c_void_p), c_int64, c_void_p]),
+    "atx_obs_row_expr": (
+        c_int,
+        [c_int32, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), c_int32, POINTER(c_void_p), c_int32, POINTER(c_double), c_int32,
+         POINTER(c_void_p), c_int, c_void_p, c_void_p, c_int64, c_void_p],
+    ),
+    "atx_obs_keep_positions": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     "atx_obs_order_key": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "atx_obs_mark_first": (c_int, [c_int32, POINTER(c_void_p), c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "atx_obs_take_rows": (
@@ -668,18 +674,17 @@ EXPR_OPS = {"push_col": 0, "push_const": 1, "add": 2, "sub": 3, "mul": 4, "div":
             "cmp_lt": 10, "cmp_eq": 11, "cmp_ne": 12, "cmp_ge": 13, "cmp_le": 14, "in_set": 15, "and": 16, "or": 17, "not": 18, "dup": 19,
             "swap": 20, "nan_where": 21}
 EXPR_MAX_INPUTS, EXPR_MAX_INSTR, EXPR_MAX_CONSTS, EXPR_MAX_STACK, EXPR_MAX_RESULTS, EXPR_CHUNK_ROWS = 16, 32, 64, 8, 4, 256
-COLOP_EXPR, COLOP_EXPR_RESULT, COLOP_EXPR_KEEP, COLOP_KEEP_POSITIONS, COLOP_KEEP_OFFSETS = 64, 96, 97, 98, 99  # the third family of ATX_COLOP_*
 
 
 def obs_row_expr(instructions, inputs, consts, outs, n: int, keep_words=None, chunk_counts=None) -> None:
-    """One launch of the row-expression kernel over ``n`` rows: ``atx_obs_column_ops`` with its third family of codes.
+    """One launch of ``atx_obs_row_expr`` over ``n`` rows.
     ``instructions``: tuples ``(code, arg0, arg1)`` in postfix order, ``code`` an ``EXPR_OPS`` value — ``push_col`` takes the index of an
     input, ``push_const`` of a constant, ``in_set`` the start and the count of a slice of the constants, ``dup`` the distance below the
     top; ``inputs``: float64 device rows of ``n``; ``consts``: floats; ``outs``: up to ``EXPR_MAX_RESULTS`` float64 device rows of ``n``,
     which take the stack slots 0 .. from the bottom (an ``out`` may be an input).  With ``keep_words`` (int64 ``[ceil(n / 64)]``) and
     ``chunk_counts`` (int64 ``[ceil(n / EXPR_CHUNK_ROWS)]``) the slot on top of the value results is the keep condition: one bit per
-    row, one count per chunk.  The limits (``EXPR_MAX_*``) and the stack are checked by the library: ``ValueError``.  Does not
-    synchronise."""
+    row, one count per chunk.  The limits (``EXPR_MAX_*``), the indices and the stack are checked by the library: ``ValueError``.  Does
+    not synchronise."""
     for t in (*inputs, *outs):
         _rows(t, None, n=n)
     if (keep_words is None) != (chunk_counts is None):
@@ -688,39 +693,20 @@ def obs_row_expr(instructions, inputs, consts, outs, n: int, keep_words=None, ch
         assert keep_words.dtype == torch.int64 and keep_words.is_contiguous() and keep_words.numel() == (n + 63) // 64
         assert chunk_counts.dtype == torch.int64 and chunk_counts.is_contiguous()
         assert chunk_counts.numel() == (n + EXPR_CHUNK_ROWS - 1) // EXPR_CHUNK_ROWS
-    table = (c_double * max(len(consts), 1))(*[float(c) for c in consts])  # alive until the call returns: the library reads it then
-    slots = []  # (op, src, in, out)
-    for code, a, b in instructions:
-        code, a, b = int(code), int(a), int(b)
-        source = None
-        if code == EXPR_OPS["push_col"]:
-            if not 0 <= a < len(inputs):
-                raise ValueError(f"obs_row_expr: an instruction reads column {a} of {len(inputs)}")
-            source, a = _ptr(inputs[a]), 0
-        elif code in (EXPR_OPS["push_const"], EXPR_OPS["in_set"]):
-            count = b if code == EXPR_OPS["in_set"] else 1
-            if a < 0 or count < 1 or a + count > len(consts):
-                raise ValueError(f"obs_row_expr: an instruction reads the constants [{a}, {a} + {count}) of {len(consts)}: outside the table "
-                                 "(IN_SET takes a slice of 1 or more)")
-            source, a = ctypes.addressof(table) + 8 * a, count
-        slots.append((COLOP_EXPR + code, a, source, None))
-    slots += [(COLOP_EXPR_RESULT, r, None, _ptr(out)) for r, out in enumerate(outs)]
-    if keep_words is not None:
-        slots.append((COLOP_EXPR_KEEP, 0, _ptr(chunk_counts), _ptr(keep_words)))
-    k = len(slots)
-    _call("atx_obs_column_ops", k, (c_int32 * max(k, 1))(*[s[0] for s in slots]), (c_int32 * max(k, 1))(*[s[1] for s in slots]),
-          (c_void_p * max(k, 1))(*[s[2] for s in slots]), (c_void_p * max(k, 1))(*[s[3] for s in slots]), n, _stream())
+    k = len(instructions)
+    code, arg0, arg1 = ((c_int32 * max(k, 1))(*[int(i[field]) for i in instructions]) for field in range(3))
+    _call("atx_obs_row_expr", k, code, arg0, arg1, len(inputs), (c_void_p * max(len(inputs), 1))(*[_ptr(t) for t in inputs]), len(consts),
+          (c_double * max(len(consts), 1))(*[float(c) for c in consts]), len(outs), (c_void_p * max(len(outs), 1))(*[_ptr(t) for t in outs]),
+          int(keep_words is not None), _ptr(keep_words), _ptr(chunk_counts), n, _stream())
 
 
 def obs_keep_positions(keep_words, chunk_offsets, n: int, positions) -> None:
-    """``positions`` (int64 ``[count]``): the rows whose bit is set in ``keep_words``, ascending — the two KEEP slots of
-    ``atx_obs_column_ops``.  ``chunk_offsets``: the exclusive prefix sum of ``obs_row_expr``'s ``chunk_counts``.  Does not synchronise."""
+    """``positions`` (int64 ``[count]``): the rows whose bit is set in ``keep_words``, ascending (``atx_obs_keep_positions``).
+    ``chunk_offsets``: the exclusive prefix sum of ``obs_row_expr``'s ``chunk_counts``.  Does not synchronise."""
     for t in (keep_words, chunk_offsets, positions):
         assert t.dtype == torch.int64 and t.is_contiguous()
     assert keep_words.numel() == (n + 63) // 64 and chunk_offsets.numel() == (n + EXPR_CHUNK_ROWS - 1) // EXPR_CHUNK_ROWS
-    capacity = positions.numel()
-    _call("atx_obs_column_ops", 2, (c_int32 * 2)(COLOP_KEEP_POSITIONS, COLOP_KEEP_OFFSETS), (c_int32 * 2)(capacity & 0x7FFFFFFF, capacity >> 31),
-          (c_void_p * 2)(_ptr(keep_words), _ptr(chunk_offsets)), (c_void_p * 2)(_ptr(positions), None), n, _stream())
+    _call("atx_obs_keep_positions", _ptr(keep_words), _ptr(chunk_offsets), n, _ptr(positions), positions.numel(), _stream())
 
 
 MAX_ROWSET_COLUMNS = 16

@@ -44,7 +44,7 @@ row operations ``native.ROW_OPS``, pure host logic — ``row_program`` runs it (
 
 The eighth is ``filter_query`` and ``mask_values_custom`` (R: filters/tabular/filter_query.py, mask_values_custom.py): ``compile_query``
 turns pandas' query text into an ``ExprProgram`` (``query``: parser, numpy's typing, Sethi-Ullman postfix order), ``query_rows`` runs it and
-lists the rows it keeps (``native.obs_row_expr``: one bit per row; ``native.obs_keep_positions``: the third family of ``atx_obs_column_ops`` codes), ``eval_rows`` returns its value rows.
+lists the rows it keeps (``native.obs_row_expr``: one bit per row; ``native.obs_keep_positions``: their ascending positions), ``eval_rows`` returns its value rows.
 """
 
 from __future__ import annotations

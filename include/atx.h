@@ -68,9 +68,10 @@
 extern "C" {
 #endif
 
-#define ATX_VERSION 420 /* 0.4.2 — additions only, so the number stays: a third family of atx_obs_column_ops codes, ATX_COLOP_EXPR ..
-                           * ATX_COLOP_KEEP_OFFSETS (a postfix row-expression program with its atx_expr_op codes, keep bits and their row
-                           * positions; no new entry point); a second family of atx_obs_column_ops codes, ATX_COLOP_SCALAR ..
+#define ATX_VERSION 420 /* 0.4.2 — additions only, so the number stays: atx_obs_row_expr / atx_obs_keep_positions (a postfix row-expression
+                           * program with its atx_expr_op codes, keep bits and their row positions; for one commit, under this number
+                           * only and with the Python binding as their single caller, they were reached through atx_obs_column_ops codes
+                           * 64 .. 99, which are unknown codes again); a second family of atx_obs_column_ops codes, ATX_COLOP_SCALAR ..
                            * ATX_COLOP_FILL_NAN (the compares, selects and row predicates of the tabular QC filters; no new entry point); atx_obs_order_key / atx_obs_mark_first / atx_obs_take_rows (row
                            * sets: pandas' order and equality as int64 keys, first occurrences, a gather of rows) with the
                            * atx_key_dtype enum; atx_obs_column_ops (a program of library functions over
@@ -614,41 +615,38 @@ enum {
 ATX_API int atx_obs_column_ops(int32_t n_ops, const int32_t* op, const int32_t* src, const double* const* in, double* const* out, int64_t n,
                                void* stream);
 
-/* ---- row expressions: the THIRD FAMILY of atx_obs_column_ops' codes, for filter_query and mask_values_custom ---- */
+/* ---- row expressions: filter_query and mask_values_custom ---- */
 
-/* Codes ATX_COLOP_EXPR (64) and above make a call of atx_obs_column_ops (above) a POSTFIX program over float64 columns of n rows,
- * evaluated per row on a stack of at most ATX_EXPR_MAX_STACK values in ONE pass — no new entry point.  A program is all of this
- * family (decided by op[0]) and has up to ATX_EXPR_MAX_SLOTS slots, in this order:
- *   instruction slots  op[t] = ATX_COLOP_EXPR + an atx_expr_op, at most ATX_EXPR_MAX_INSTR of them:
- *     PUSH_COL           push in[t][row]; in[t] a DEVICE column (at most ATX_EXPR_MAX_INPUTS distinct pointers per call)
- *     PUSH_CONST         push in[t][0];   in[t] a HOST double, read during the call
- *     ADD SUB MUL DIV    (x, y) -> x op y, y the top: IEEE float64, one rounding each, never contracted
- *     NEG ABS            the sign bit flipped / cleared           ROUND_F32      (double)(float)x: round to nearest even, subnormals kept
- *     CMP_GT .. CMP_LE   (x, y) -> (x cmp y) ? 1 : 0, ATX_EXPR_CMP_GT + atx_cmp; IEEE's compares: false against a NaN, except NE
- *     IN_SET             x -> 1 if x == in[t][j] for a j < src[t], else 0; in[t] src[t] >= 1 HOST doubles (a NaN equals nothing;
- *                        -0.0 == 0.0); all constants of a call together at most ATX_EXPR_MAX_CONSTS, host ranges that overlap or touch held once
- *     AND OR             (x, y) -> 0 / 1, an operand is true when it is not 0        NOT   x -> (x == 0) ? 1 : 0
- *     DUP                push a copy of the value src[t] below the top (0: the top)  SWAP  exchange the top two
- *     NAN_WHERE          (x, c) -> the canonical quiet NaN 0x7ff8000000000000 where c is not 0, else the BITS of x
- *   ATX_COLOP_EXPR_RESULT slots, at most ATX_EXPR_MAX_RESULTS: the r-th of them has src[t] = r and stores stack slot r (counted from
- *     the bottom) of what the program leaves to the device row out[t], which may be any input column (a lane loads its row before
- *     it stores it)
- *   one ATX_COLOP_EXPR_KEEP slot, the last: one more stack slot on top of the results is the row's keep condition;
- *     out[t]  device uint64 [ceil(n / 64)] (passed as double*): bit (row % 64) of word (row / 64) is set where the condition is not 0;
- *             the bits past n of the last word are 0
- *     in[t]   device int64 [ceil(n / ATX_EXPR_CHUNK_ROWS)] (passed as const double*, WRITTEN): the rows kept in every chunk
- *   Every word and every count is written by exactly one lane: no atomics, no order between workgroups.
- * ATX_EINVAL, nothing launched: more slots than ATX_EXPR_MAX_SLOTS; instructions outside 1 .. ATX_EXPR_MAX_INSTR, more distinct input
- * columns, constants or results than their limits; neither a RESULT nor a KEEP slot; an unknown code; slots out of order; a stack that
- * underflows or grows beyond ATX_EXPR_MAX_STACK (the depth is simulated on the host); a final depth other than the number of RESULT
- * slots (+ 1 with KEEP); a null constant pointer or an IN_SET of fewer than 1 member; a null column, output or keep row with n > 0;
- * n < 0.  n == 0: validated, nothing launched, ATX_OK.
+/* A POSTFIX program over float64 columns of n rows, evaluated per row on a stack of at most ATX_EXPR_MAX_STACK values in ONE pass.  The
+ * program is flat: instruction t is code[t] (an atx_expr_op) with its operands arg0[t] and arg1[t]; an operand a code does not use is
+ * ignored.  code, arg0, arg1, in, consts and out are HOST arrays, read during the call.
+ *   PUSH_COL           push in[arg0][row]; in: n_inputs (at most ATX_EXPR_MAX_INPUTS) DEVICE columns of n doubles
+ *   PUSH_CONST         push consts[arg0]; consts: n_consts (at most ATX_EXPR_MAX_CONSTS) HOST doubles, copied during the call
+ *   ADD SUB MUL DIV    (x, y) -> x op y, y the top: IEEE float64, one rounding each, never contracted
+ *   NEG ABS            the sign bit flipped / cleared           ROUND_F32      (double)(float)x: round to nearest even, subnormals kept
+ *   CMP_GT .. CMP_LE   (x, y) -> (x cmp y) ? 1 : 0, ATX_EXPR_CMP_GT + atx_cmp; IEEE's compares: false against a NaN, except NE
+ *   IN_SET             x -> 1 if x == consts[j] for a j in [arg0, arg0 + arg1), arg1 >= 1, else 0 (a NaN equals nothing; -0.0 == 0.0)
+ *   AND OR             (x, y) -> 0 / 1, an operand is true when it is not 0        NOT   x -> (x == 0) ? 1 : 0
+ *   DUP                push a copy of the value arg0 below the top (0: the top)    SWAP  exchange the top two
+ *   NAN_WHERE          (x, c) -> the canonical quiet NaN 0x7ff8000000000000 where c is not 0, else the BITS of x
+ * Results: stack slot r (counted from the bottom) of what the program leaves, r < n_results <= ATX_EXPR_MAX_RESULTS, is stored to the
+ * device row out[r], which may be any input column (a lane loads its row before it stores it).  With keep != 0 one more slot, on top of
+ * the results, is the row's keep condition:
+ *   keep_words    device uint64 [ceil(n / 64)]: bit (row % 64) of word (row / 64) is set where the condition is not 0; the bits past
+ *                 n of the last word are 0
+ *   chunk_counts  device int64 [ceil(n / ATX_EXPR_CHUNK_ROWS)]: the rows kept in every chunk
+ * Every word and every count is written by exactly one lane: no atomics, no order between workgroups.  With keep == 0 both are ignored.
+ * ATX_EINVAL, nothing launched: n < 0; a null code, arg0 or arg1; n_instr outside 1 .. ATX_EXPR_MAX_INSTR; n_inputs, n_consts or
+ * n_results negative or above its limit; neither a result nor keep; a null in, consts or out with a count above 0; an unknown code; a
+ * column or constant index outside its table, an IN_SET slice outside consts or of fewer than 1 member; a stack that underflows or
+ * grows beyond ATX_EXPR_MAX_STACK (the depth is simulated on the host); a final depth other than n_results (+ 1 with keep); a null
+ * column, output or keep row with n > 0.  n == 0: validated, nothing launched, ATX_OK.
  *
- * A call of TWO slots, ATX_COLOP_KEEP_POSITIONS then ATX_COLOP_KEEP_OFFSETS, lists the kept rows: out[0][j] (device int64
- * [n_positions], passed as double*) = the j-th row, ascending, whose bit is set in in[0] (the keep words over n rows); in[1] is the
- * EXCLUSIVE prefix sum of the chunk counts (device int64); n_positions = src[0] + src[1] * 2^31, both not negative.  A row's place is
- * its chunk's offset plus the number of set bits below it in its chunk; a place outside [0, n_positions) is not written.  One lane
- * per row, plain stores, no workgroup waits for another.  A null pointer with n > 0 and n_positions > 0: ATX_EINVAL.
+ * atx_obs_keep_positions lists the kept rows: positions[j] (device int64 [n_positions]) = the j-th row, ascending, whose bit is set in
+ * keep_words (over n rows); chunk_offsets is the EXCLUSIVE prefix sum of the chunk counts (device int64).  A row's place is its
+ * chunk's offset plus the number of set bits below it in its chunk; a place outside [0, n_positions) is not written.  One lane per
+ * row, plain stores, no workgroup waits for another.  n < 0 or n_positions < 0: ATX_EINVAL.  n == 0 or n_positions == 0: nothing
+ * launched, ATX_OK.  Otherwise a null pointer: ATX_EINVAL.
  *   R: filters/tabular/filter_query.py:76-92 (obs_df.query(query)); filters/tabular/mask_values_custom.py:47-67
  *   (obs_df.eval(condition), Series.mask) */
 #define ATX_EXPR_MAX_INPUTS 16
@@ -656,13 +654,7 @@ ATX_API int atx_obs_column_ops(int32_t n_ops, const int32_t* op, const int32_t* 
 #define ATX_EXPR_MAX_CONSTS 64
 #define ATX_EXPR_MAX_STACK 8
 #define ATX_EXPR_MAX_RESULTS 4
-#define ATX_EXPR_MAX_SLOTS 37 /* ATX_EXPR_MAX_INSTR + ATX_EXPR_MAX_RESULTS + 1 */
 #define ATX_EXPR_CHUNK_ROWS 256
-#define ATX_COLOP_EXPR 64 /* + atx_expr_op */
-#define ATX_COLOP_EXPR_RESULT 96
-#define ATX_COLOP_EXPR_KEEP 97
-#define ATX_COLOP_KEEP_POSITIONS 98
-#define ATX_COLOP_KEEP_OFFSETS 99
 typedef enum {
     ATX_EXPR_PUSH_COL = 0,
     ATX_EXPR_PUSH_CONST = 1,
@@ -687,6 +679,11 @@ typedef enum {
     ATX_EXPR_SWAP = 20,
     ATX_EXPR_NAN_WHERE = 21
 } atx_expr_op;
+ATX_API int atx_obs_row_expr(int32_t n_instr, const int32_t* code, const int32_t* arg0, const int32_t* arg1, int32_t n_inputs,
+                             const double* const* in, int32_t n_consts, const double* consts, int32_t n_results, double* const* out, int keep,
+                             uint64_t* keep_words, int64_t* chunk_counts, int64_t n, void* stream);
+ATX_API int atx_obs_keep_positions(const uint64_t* keep_words, const int64_t* chunk_offsets, int64_t n, int64_t* positions,
+                                   int64_t n_positions, void* stream);
 
 /* ---- row sets: pandas' order and equality as int64 keys, first occurrences, a gather of rows ---- */
 

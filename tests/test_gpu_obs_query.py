@@ -275,13 +275,13 @@ def test_argument_errors_reach_python(dev):
     counts = torch.zeros(1, dtype=torch.int64, device=dev)
     push, add, in_set = ("push_col", 0), ("add",), native.EXPR_OPS["in_set"]
     bad = [
-        ([push] * 33, [x], (), [out], "instructions"), ([push] * 34, [x], (), [out] * 4, "slots"),
+        ([push] * 33, [x], (), [out], "instructions"), ([push] * 34, [x], (), [out] * 4, "instructions"),
         ([("push_col", k) for k in range(17)], many, (), [out], "input columns"), ([push, (in_set, 0, 65)], [x], [0.0] * 65, [out], "constants"),
         ([push] * 5, [x], (), [out] * 5, "value results"), ([push], [x], (), [], "neither"), ([(22, 0, 0)], [x], (), [out], "unknown code"),
         ([push, (-1, 0, 0)], [x], (), [out], "unknown code"), ([push, add], [x], (), [out], "underflow"), ([("swap",)], [x], (), [out], "underflow"),
         ([("dup", 1)], [x], (), [out], "underflow"), ([push] * 9 + [add] * 8, [x], (), [out], "overflow"), ([push, push], [x], (), [out], "leaves 2 values"),
         ([push], [x], (), [out, out], "leaves 1 values"), ([("push_col", 1)], [x], (), [out], "column 1 of 1"), ([("push_col", -1)], [x], (), [out], "column -1"),
-        ([("push_const", 2)], [x], [1.0, 2.0], [out], r"constants \[2, "), ([push, (in_set, 1, 2)], [x], [1.0, 2.0], [out], "IN_SET"),
+        ([("push_const", 2)], [x], [1.0, 2.0], [out], "constant 2 of 2"), ([push, (in_set, 1, 2)], [x], [1.0, 2.0], [out], "IN_SET"),
         ([push, (in_set, 0, 0)], [x], [1.0, 2.0], [out], "IN_SET"), ([push, (in_set, -1, 1)], [x], [1.0, 2.0], [out], "IN_SET"),
         ([push], [None], (), [out], "null input column"), ([push], [x], (), [None], "output row 0 is null"),
     ]
@@ -293,29 +293,29 @@ def test_argument_errors_reach_python(dev):
         native.obs_row_expr([(0, 0, 0)], [x], (), [out], n, keep_words=words, chunk_counts=counts)
     with pytest.raises(ValueError, match="go together"):
         native.obs_row_expr([(0, 0, 0)], [x], (), [], n, keep_words=words)
-    # the slots themselves, as atx_obs_column_ops reads them
-    E, RESULT, KEEP, POSITIONS, OFFSETS = native.COLOP_EXPR, native.COLOP_EXPR_RESULT, native.COLOP_EXPR_KEEP, native.COLOP_KEEP_POSITIONS, native.COLOP_KEEP_OFFSETS
-
-    def slots(ops, srcs, ins, outs, rows=n):
-        k = len(ops)
-        return ("atx_obs_column_ops", k, (c_int32 * k)(*ops), (c_int32 * k)(*srcs), (c_void_p * k)(*ins), (c_void_p * k)(*outs), rows, None)
-
+    # the entry points themselves, on the device rows: what the wrappers cannot say
     px, po, pw, pc = x.data_ptr(), out.data_ptr(), words.data_ptr(), counts.data_ptr()
-    for call, message in [(("atx_obs_column_ops", 1, (c_int32 * 1)(E), None, (c_void_p * 1)(px), (c_void_p * 1)(po), n, None), "null program array"),
-                          (slots([E, RESULT], [0, 0], [px, None], [None, po], rows=-1), "-1 rows"),
-                          (slots([E, RESULT], [0, 1], [px, None], [None, po]), "in order"),
-                          (slots([E, RESULT, E], [0, 0, 0], [px, None, px], [None, po, None]), "follows a RESULT"),
-                          (slots([E, KEEP, RESULT], [0, 0, 0], [px, pc, None], [None, pw, po]), "follows the KEEP"),
-                          (slots([E, KEEP], [0, 0], [px, None], [None, pw]), "null keep_words or chunk_counts"),
-                          (slots([E + 1, RESULT], [0, 0], [None, None], [None, po]), "host doubles"),
-                          (slots([POSITIONS], [1], [pw], [po]), "two slots"), (slots([POSITIONS, OFFSETS], [-1, 0], [pw, pc], [po, None]), "two slots"),
-                          (slots([POSITIONS, OFFSETS], [1, 0], [pw, pc], [po, None], rows=-1), "-1 rows"),
-                          (slots([POSITIONS, OFFSETS], [1, 0], [None, pc], [po, None]), "null pointer")]:
+    zero, none = (c_int32 * 1)(0), (c_void_p * 1)(None)
+
+    def flat(rows=n, keep=0, keep_words=None, chunk_counts=None, **instead):  # the program [push_col 0] over x: one result, or a keep condition alone
+        args = {"code": zero, "arg0": zero, "arg1": zero, "in": (c_void_p * 1)(px), "consts": (c_double * 1)(0.0), "out": none if keep else (c_void_p * 1)(po)}
+        assert set(instead) <= set(args)
+        args.update(instead)
+        return ("atx_obs_row_expr", 1, args["code"], args["arg0"], args["arg1"], 1, args["in"], 0, args["consts"], 0 if keep else 1, args["out"], keep,
+                keep_words, chunk_counts, rows, None)
+
+    for call, message in [(flat(code=None), "null program array"), (flat(arg0=None), "null program array"), (flat(arg1=None), "null program array"),
+                          (flat(rows=-1), "-1 rows"), (flat(**{"in": None}), "null table"), (flat(out=None), "null table"),
+                          (flat(keep=1, keep_words=None, chunk_counts=pc), "null keep_words or chunk_counts"),
+                          (flat(keep=1, keep_words=pw, chunk_counts=None), "null keep_words or chunk_counts"),
+                          (("atx_obs_keep_positions", pw, pc, -1, po, 1, None), "-1 rows"), (("atx_obs_keep_positions", pw, pc, n, po, -1, None), "-1 positions"),
+                          (("atx_obs_keep_positions", None, pc, n, po, 1, None), "null pointer"), (("atx_obs_keep_positions", pw, None, n, po, 1, None), "null pointer"),
+                          (("atx_obs_keep_positions", pw, pc, n, None, 1, None), "null pointer")]:
         with pytest.raises(ValueError, match=message):
             native._call(*call)
     native.obs_row_expr([(0, 0, 0)], [x[:0]], (), [out[:0]], 0)  # n == 0: validated, nothing launched
-    native._call(*slots([E, KEEP], [0, 0], [None, None], [None, None], rows=0))
-    native._call(*slots([POSITIONS, OFFSETS], [0, 0], [None, None], [None, None], rows=0))
+    native._call(*flat(rows=0, keep=1, **{"in": none}))
+    native._call("atx_obs_keep_positions", None, None, 0, None, 0, None)
     torch.cuda.synchronize()
     assert bool((out_whole == SENTINEL).all()) and _guards_hold(whole, n) and x.cpu().numpy().tolist() == list(range(8))  # nothing was launched
     assert int(words[0]) == 0 and int(counts[0]) == 0

@@ -114,7 +114,7 @@ def test_argument_checks_of_the_second_family():
         return lib.atx_obs_column_ops(k, (ctypes.c_int32 * k)(*ops), (ctypes.c_int32 * k)(*srcs), (ctypes.c_void_p * k)(*(ins or [one] * k)),
                                       (ctypes.c_void_p * k)(*(outs or [one] * k)), n, None)
 
-    for code in (10, 15, 33):
+    for code in (10, 15, 33, 64, 96, 98):
         assert call([code], [-1]) == native.EINVAL and b"unknown code" in lib.atx_last_error() and b"operation 0" in lib.atx_last_error()
     assert call([17, 33], [-1, -1]) == native.EINVAL and b"operation 1 has the unknown code 33" in lib.atx_last_error()
     assert call([17, 16], [-1, 0]) == native.EINVAL and b"operation 1 is a SCALAR" in lib.atx_last_error()

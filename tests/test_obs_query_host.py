@@ -1,10 +1,15 @@
 """``filter_query`` and ``mask_values_custom`` on the host: the query language (parser, numpy's typing, the compiler's order and limits),
 the compiled programs through the plain numpy interpreter of tests/row_expr_restatement.py against pandas ITSELF (``DataFrame.query`` /
 ``eval`` + ``Series.mask``), the two filters against the frames the reference returned (tests/golden/obs_query.json) with the two native
-calls answered by that interpreter, and the constructor errors.  No GPU.  Everything is exact: there is no tolerance in this file.
+calls answered by that interpreter, the constructor errors, and the declarations and argument checks of ``atx_obs_row_expr`` /
+``atx_obs_keep_positions`` through ctypes.  No GPU.  Everything is exact: there is no tolerance in this file.
 """
 
 from __future__ import annotations
+
+import ctypes
+import os
+import re
 
 import numpy as np
 import pytest
@@ -205,3 +210,85 @@ def test_constructor_errors_and_a_missing_column(monkeypatch):
     assert len(empty) == 0 and list(empty.columns) == ["col2"]
     out = create_filter_by_name("filter_query", query="col2 > 4").forward({"col2": np.array([3, 4, 5, 6])})
     assert isinstance(out, dict) and out["col2"].tolist() == [5, 6]
+
+
+# ---- the C ABI ------------------------------------------------------------------------------------------------------------------------------------
+def test_entry_points_are_declared_and_the_slot_codes_are_gone():
+    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "atx.h")).read()
+    for name in ("atx_obs_row_expr", "atx_obs_keep_positions"):
+        assert f"ATX_API int {name}(" in header and name in native.SIGNATURES
+    assert "filters/tabular/filter_query.py" in header and "filters/tabular/mask_values_custom.py" in header
+    for name, code in native.EXPR_OPS.items():  # the codes of the header are the codes of the binding
+        assert f"ATX_EXPR_{name.upper()} = {code}" in header
+    limits = ("MAX_INPUTS", "MAX_INSTR", "MAX_CONSTS", "MAX_STACK", "MAX_RESULTS", "CHUNK_ROWS")
+    for name in limits:
+        assert f"#define ATX_EXPR_{name} {getattr(native, 'EXPR_' + name)}\n" in header
+    # the slot encoding that carried the program through atx_obs_column_ops is gone: its slot limit, and the five codes, which were
+    # the only ATX_COLOP_ names that were defines (the codes of atx_obs_column_ops are enumerators)
+    assert sorted(re.findall(r"#define ATX_EXPR_(\w+)", header)) == sorted(limits) and "#define ATX_COLOP_" not in header
+    assert not [name for name in vars(native) if name.startswith("COLOP_")]
+
+
+def test_entry_points_check_their_arguments_without_a_gpu():
+    lib = native.load()
+    one = ctypes.c_void_p(16).value  # never dereferenced: validation fails first
+    EINVAL, OK = native.EINVAL, native.OK
+    push, add, in_set = ("push_col", 0), ("add",), native.EXPR_OPS["in_set"]
+
+    def expr(program, inputs, table, outs, n=8, keep=0, words=one, counts=one, **instead):
+        """atx_obs_row_expr with the arrays and counts of its arguments, or what ``instead`` names in their place."""
+        code = [(native.EXPR_OPS[i[0]] if isinstance(i[0], str) else i[0], *(list(i[1:]) + [0, 0])[:2]) for i in program]
+        args = {"n_instr": len(code), "n_inputs": len(inputs), "in": (ctypes.c_void_p * max(len(inputs), 1))(*inputs), "n_consts": len(table),
+                "consts": (ctypes.c_double * max(len(table), 1))(*table), "n_results": len(outs), "out": (ctypes.c_void_p * max(len(outs), 1))(*outs)}
+        for field, name in enumerate(("code", "arg0", "arg1")):
+            args[name] = (ctypes.c_int32 * max(len(code), 1))(*[i[field] for i in code])
+        assert set(instead) <= set(args)
+        args.update(instead)
+        return lib.atx_obs_row_expr(args["n_instr"], args["code"], args["arg0"], args["arg1"], args["n_inputs"], args["in"], args["n_consts"],
+                                    args["consts"], args["n_results"], args["out"], keep, words, counts, n, None)
+
+    def refused(status, message):
+        said = lib.atx_last_error().decode()
+        assert status == EINVAL and said.startswith(("atx_obs_row_expr: ", "atx_obs_keep_positions: ")) and re.search(message, said), (message, said)
+
+    # the malformed programs of tests/test_gpu_obs_query.py::test_argument_errors_reach_python, x and out being `one`
+    x = out = one
+    bad = [
+        ([push] * 33, [x], (), [out], "instructions"), ([push] * 34, [x], (), [out] * 4, "instructions"),
+        ([("push_col", k) for k in range(17)], [x] * 17, (), [out], "input columns"), ([push, (in_set, 0, 65)], [x], [0.0] * 65, [out], "constants"),
+        ([push] * 5, [x], (), [out] * 5, "value results"), ([push], [x], (), [], "neither"), ([(22, 0, 0)], [x], (), [out], "unknown code"),
+        ([push, (-1, 0, 0)], [x], (), [out], "unknown code"), ([push, add], [x], (), [out], "underflow"), ([("swap",)], [x], (), [out], "underflow"),
+        ([("dup", 1)], [x], (), [out], "underflow"), ([push] * 9 + [add] * 8, [x], (), [out], "overflow"), ([push, push], [x], (), [out], "leaves 2 values"),
+        ([push], [x], (), [out, out], "leaves 1 values"), ([("push_col", 1)], [x], (), [out], "column 1 of 1"), ([("push_col", -1)], [x], (), [out], "column -1"),
+        ([("push_const", 2)], [x], [1.0, 2.0], [out], "constant 2 of 2"), ([push, (in_set, 1, 2)], [x], [1.0, 2.0], [out], "IN_SET"),
+        ([push, (in_set, 0, 0)], [x], [1.0, 2.0], [out], "IN_SET"), ([push, (in_set, -1, 1)], [x], [1.0, 2.0], [out], "IN_SET"),
+        ([push], [None], (), [out], "null input column"), ([push], [x], (), [None], "output row 0 is null"),
+    ]
+    for code, inputs, consts, outs, message in bad:
+        refused(expr(code, inputs, consts, outs), message)
+    # what only the flat arguments can say
+    for name in ("code", "arg0", "arg1"):
+        refused(expr([push], [x], (), [out], **{name: None}), "null program array")
+    refused(expr([push], [x], (), [out], n=-1), "-1 rows")
+    refused(expr([push], [x], (), [out], n_instr=0), "instructions, got 0")
+    for name, message in (("n_inputs", "input columns, got -1"), ("n_consts", "constants, got -1"), ("n_results", "value results, got -1")):
+        refused(expr([push], [x], (), [out], **{name: -1}), message)
+    refused(expr([("push_const", 0)], [], [1.0], [out], consts=None), "null table")
+    refused(expr([push], [x], (), [out], **{"in": None}), "null table")
+    refused(expr([push], [x], (), [out], out=None), "null table")
+    refused(expr([push], [x], (), [], keep=1, words=None), "null keep_words or chunk_counts")
+    refused(expr([push], [x], (), [], keep=1, counts=None), "null keep_words or chunk_counts")
+    refused(expr([push], [x], (), [out], keep=1), "leaves 1 values, 1 value results and a keep condition")  # a keep condition needs a slot of its own
+    refused(expr([push], [None], (), [None], keep=1, n=0, words=None, counts=None), "leaves 1 values")  # ... without rows too: keep is a flag
+    # no rows: validated, nothing launched, whatever the rows are
+    assert expr([push], [None], (), [None], n=0) == OK
+    assert expr([push], [None], (), [], n=0, keep=1, words=None, counts=None) == OK
+    assert expr([push, ("push_const", 0), ("cmp_gt",)], [None], [1.0], [], n=0, keep=1, words=None, counts=None) == OK
+
+    # atx_obs_keep_positions(keep_words, chunk_offsets, n, positions, n_positions, stream)
+    refused(lib.atx_obs_keep_positions(one, one, -1, one, 1, None), "-1 rows")
+    refused(lib.atx_obs_keep_positions(one, one, 8, one, -1, None), "-1 positions")
+    for words, offsets, positions in ((None, one, one), (one, None, one), (one, one, None)):
+        refused(lib.atx_obs_keep_positions(words, offsets, 8, positions, 1, None), "null pointer")
+    assert lib.atx_obs_keep_positions(None, None, 0, None, 1, None) == OK
+    assert lib.atx_obs_keep_positions(None, None, 8, None, 0, None) == OK

@@ -129,7 +129,7 @@ def test_entry_points_are_declared_bound_and_cite_the_reference():
     for name, code in R.CODES.items():  # the codes of the header are the codes of the binding and of the restatement
         tag = {"float64": "F64", "float32": "F32", "datetime": "DATETIME", "bool": "BOOL"}.get(name, name.upper().replace("INT", "I").replace("UI", "U"))
         assert f"ATX_KEY_{tag} = {code}" in header and getattr(native, f"KEY_{tag}") == code
-    assert len(native.SIGNATURES) == 55
+    assert len(native.SIGNATURES) == 57
 
 
 def test_entry_points_check_their_arguments_without_a_gpu():
