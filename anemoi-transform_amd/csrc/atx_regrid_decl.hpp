@@ -74,6 +74,25 @@ __device__ __forceinline__ void store_out(Pack<T, N>* p, const Pack<T, N>& v) {
     using NV = typename NativeVec<T, N>::type;
     __builtin_nontemporal_store(*reinterpret_cast<const NV*>(&v), reinterpret_cast<NV*>(p));
 }
+// (Write-through stores there — `sc1`, `sc0 sc1` — lost 2.4-5.3 % on k4f64 (3.7 %), k4f32, k1f64 and the slowest 1/8 shard, direct and tiled alike;
+// `sc1 nt` measured +0.4-0.9 %, inside three times the parent's own round-to-round spread, so not adopted: profiles/store_policy_ab.json.
+// The four policies as one -D knob: tools/experiments/gather_store_policy.patch.)
+//
+// One output element of the field-major fixed-k kernel (lane = target: a wave writes 64 consecutive elements of one field): written
+// through and dropped from the XCD's L2 (`sc1 nt`), so that the source fills of the same launch do not find it there as a dirty
+// line to evict.  +3.4-3.9 % on k4f64, +3.2 % k1f64, +6.1 % k1f32, k4f32 +1.6 % (inside its spread) over the plain store it replaces;
+// `nt` alone +1.1-1.3 %, `sc1` +2.3 % (same file).  The compiler has no store with these bits, so it is assembly — one vector store,
+// address and data in VGPRs; the compiler neither counts it nor pads it, and a store of 8 bytes or fewer needs no wait state before
+// its data register is written again (the kernel stores inside its level loop).  The statement orders memory, so the loads of the next
+// level no longer move above it: k = 4 f64 went from 64 to 34 VGPRs, f32 from 56 to 26 — measured as part of the same figures.
+template <typename T>
+__device__ __forceinline__ void store_field(T* p, T v) {
+    static_assert(sizeof(T) == 8 || sizeof(T) == 4, "store_field: f64 / f32 elements");
+    if constexpr (sizeof(T) == 8)
+        asm volatile("global_store_dwordx2 %0, %1, off sc1 nt" : : "v"(p), "v"(v) : "memory");
+    else
+        asm volatile("global_store_dword %0, %1, off sc1 nt" : : "v"(p), "v"(v) : "memory");
+}
 // One source vector of the fixed-k kernels, a plain load.  Kept as a function: written in place, the same load costs three
 // instantiations one or two registers (the copy out of the function is what the compiler sees differently).
 template <typename T, int N>

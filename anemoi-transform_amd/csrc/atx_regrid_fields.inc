@@ -68,7 +68,7 @@ regrid_fields_ell_kernel(const T* __restrict__ src, T* __restrict__ out,
                 for (int st = 0; st < n_stage; ++st)
                     acc = apply_level_op(load_level_op<T>(prog, (int64_t)st * n_lev + l), acc, masked);
             }
-            out[(int64_t)l * out_pitch + t] = acc;  // plain store (a non-temporal one was a knob, off; no log kept)
+            store_field(out + (int64_t)l * out_pitch + t, acc);  // written through (atx_regrid_decl.hpp)
         }
     } else {  // run-time k: the row walked once per 16 fields, one accumulator per field (cf. regrid_fields_csr_kernel)
         constexpr int LC = 16;
@@ -94,7 +94,7 @@ regrid_fields_ell_kernel(const T* __restrict__ src, T* __restrict__ out,
                         for (int st = 0; st < n_stage; ++st)
                             v = apply_level_op(load_level_op<T>(prog, (int64_t)st * n_lev + lc + i), v, masked);
                     }
-                    out[(int64_t)(lc + i) * out_pitch + t] = v;
+                    out[(int64_t)(lc + i) * out_pitch + t] = v;  // plain store: store_field was measured on the compile-time k route only
                 }
             }
         }

@@ -4,7 +4,9 @@
 #   bash tools/build_variant.sh NAME --rev <git-rev> [-D...]          the csrc/ + include/ of an earlier commit
 # The knobs that are left choose the math routes (ATX_FAST_EXP, ATX_FAST_LOG, ATX_FAST_SINCOS, ATX_SNOW_TANH, ATX_FMA_SGPR, ATX_SINCOS_FMA) and
 # the grid cap (ATX_MAX_GRID).  The per-point, the gather, the combine and the relayout kernels' knobs are frozen (HISTORY.md): their other
-# sides need a --rev build of a commit that still had them (402a730 for the gather, e6acba1 for combine and relayout).
+# sides need a --rev build of a commit that still had them (402a730 for the gather, e6acba1 for combine and relayout).  The store
+# policy of the gather kernels (ATX_STORE_POLICY=OutStore::nt|sc1|sc0sc1|sc1nt) is tools/experiments/gather_store_policy.patch, applied to the
+# csrc/ of the parent of the commit that added it.
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 NAME=$1; shift
