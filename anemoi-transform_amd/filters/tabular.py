@@ -74,7 +74,13 @@ Deviations from the reference, each said once when it first matters (``core.say_
   * ``filter_query`` / ``mask_values_custom``: what pandas takes beyond the language of ``query`` (``@local``, ``//``, ``%``, ``**``, other
     functions, arithmetic or compares on booleans, datetimes) raises the reference's ``ValueError``; integers ride in float64 and never
     wrap; the caller's table is not modified.
-The other tabular filters of the reference (``encode_statids``, the tabular ``rename``) are not built: DESIGN.md §7.
+  * ``encode_statids``: the caller's table is not modified; an entry that is not a ``str`` raises ``ValueError`` (the reference:
+    ``AttributeError``); a trailing U+0000 is ignored; a value of 2^63 or more raises ``OverflowError`` for a mapping.
+
+``encode_statids`` turns the one string column recipes carry, the station identifier, into int64 (``obs.encode_statids`` ->
+``atx_text_encode_statids`` of the companion library ``libatx_text``, one launch over the column's byte matrix), after which the whole
+table is numeric and resident; ``rename_tabular`` renames columns (host bookkeeping).  With them every tabular filter of the reference
+is registered here.
 """
 
 from __future__ import annotations
@@ -90,7 +96,7 @@ from .. import healpix, obs, query
 from ..core import Filter, filter_registry, say_once
 from ..fields import MISSING, Field, FieldList, new_field_from_stack
 from ..grids import lookup
-from ..tables import NAT, Table, column_kind, dtype_kind, float_column, host_array, on_device, to_ns
+from ..tables import NAT, Table, column_kind, dtype_kind, float_column, host_array, on_device, text_matrix, to_ns
 
 LOG = logging.getLogger(__name__)
 
@@ -1239,6 +1245,67 @@ class MaskValuesCustom(_MaskFilter):
         return t.replaced(done)
 
 
+# ---- station identifiers and column names -------------------------------------------------------------------------------------------
+class EncodeStatids(Filter):
+    """The station identifier column as int64 (R: filters/tabular/encode_statids.py:18-60): the base-36 value of the stripped,
+    upper-cased identifier if it is made of ``0-9A-Z``, else the first four bytes of the MD5 digest of the stripped identifier.  The
+    column is packed into a byte matrix and encoded in one launch (``obs.encode_statids`` -> ``atx_text_encode_statids``); rows the
+    kernel leaves undecided (non-ASCII, an interior NUL, 13 or more base-36 characters) are the host's, ``last_host_rows`` of them in
+    the last ``forward``.  After it the table has no string column left and stays on the device.  A missing column raises ``ValueError``.
+
+    A value of 2^63 or more has no int64: a DataFrame then gets pandas' own answer for the whole column (``Series.apply``: uint64 or
+    object), a mapping raises ``OverflowError``.
+
+    Deviations: the caller's table is not modified; an entry that is not a ``str`` raises ``ValueError`` (the reference:
+    ``AttributeError`` from ``.strip()``); a trailing U+0000 is lost in numpy's conversion of the column and so ignored."""
+
+    def __init__(self, *, station_id: str = "statid") -> None:
+        self.station_id = station_id
+        self.last_host_rows = 0
+        say_once(LOG, (type(self), "deviations"), "encode_statids: the caller's table is not modified (the reference writes into its "
+                 "argument); an entry that is not a str raises ValueError (the reference: AttributeError); a trailing U+0000 of an "
+                 "identifier is ignored", level=logging.INFO)
+
+    def __repr__(self) -> str:
+        return f"EncodeStatids({self.station_id})"
+
+    def forward(self, table: Any) -> Any:
+        t = Table(table)
+        t.require([self.station_id])
+        packed = text_matrix(t[self.station_id])  # a non-str entry raises here, before the device is looked up
+        try:
+            code, self.last_host_rows = obs.encode_statids(t[self.station_id], t.device, packed=packed)
+        except OverflowError:
+            if not t.frame:
+                raise
+            say_once(LOG, (type(self), "overflow"), "encode_statids: an identifier encodes to 2^63 or more; the whole column is pandas' "
+                     "own answer (uint64 or object), computed on the host")
+            self.last_host_rows = t.n_rows
+            out = table.copy()
+            out[self.station_id] = table[self.station_id].apply(obs.statid_to_int)
+            return out
+        return t.replaced({self.station_id: code})
+
+
+class RenameTabular(Filter):
+    """Renames columns of a table (R: filters/tabular/rename.py:18-45: ``df.rename(columns=columns)``).  ``columns`` maps old names to
+    new ones; a missing old name raises ``ValueError``.  Host bookkeeping (``Table.replaced``): a DataFrame goes through pandas, a mapping
+    gives a new dict in the same order whose columns are the caller's own objects, device tensors included; nothing is copied."""
+
+    def __init__(self, *, columns: dict[str, str]) -> None:
+        self.columns = dict(columns)
+
+    def __repr__(self) -> str:
+        return f"RenameTabular({self.columns})"
+
+    def forward(self, table: Any) -> Any:
+        t = Table(table)
+        t.require(list(self.columns))
+        return t.replaced({}, renamed=self.columns)
+
+
+filter_registry.register("encode_statids", EncodeStatids)
+filter_registry.register("rename_tabular", RenameTabular)
 filter_registry.register("filter_query", FilterQuery)
 filter_registry.register("mask_values_custom", MaskValuesCustom)
 filter_registry.register("mask_tabular", MaskValues)

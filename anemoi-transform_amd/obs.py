@@ -45,11 +45,16 @@ row operations ``native.ROW_OPS``, pure host logic — ``row_program`` runs it (
 The eighth is ``filter_query`` and ``mask_values_custom`` (R: filters/tabular/filter_query.py, mask_values_custom.py): ``compile_query``
 turns pandas' query text into an ``ExprProgram`` (``query``: parser, numpy's typing, Sethi-Ullman postfix order), ``query_rows`` runs it and
 lists the rows it keeps (``native.obs_row_expr``: one bit per row; ``native.obs_keep_positions``: their ascending positions), ``eval_rows`` returns its value rows.
+
+The ninth is ``encode_statids`` (R: filters/tabular/encode_statids.py): the one string column of a table as int64, one launch over its
+byte matrix (``native_text.encode_statids`` -> ``atx_text_encode_statids`` of the companion library), the rows the kernel leaves
+undecided answered by ``statid_to_int`` on the host.
 """
 
 from __future__ import annotations
 
 import datetime
+import logging
 import re
 from collections.abc import Mapping
 from typing import Any, NamedTuple, Sequence
@@ -64,6 +69,7 @@ from .stack import COLUMNS, Stack
 from .tables import NAT, datetime_ns, float_column, host_array, launch_device, take_rows, to_ns  # noqa: F401
 from .tables import dtype_kind as _dtype_kind, gather as _take, on_device as _device  # the names this module, its tests and tools know them by
 
+_LOG = logging.getLogger(__name__)
 _UNIT_NS = {"s": 10**9, "m": 60 * 10**9, "h": 3600 * 10**9, "d": 86400 * 10**9}
 _OFFSET = re.compile(r"^([+-]?)(\d+)([smhd])$")
 _WINDOW = re.compile(r"^([(\[])([^,]*),([^,]*)([)\]])$")
@@ -1184,3 +1190,58 @@ def eval_rows(columns: Mapping[str, Any], program: ExprProgram, dev: torch.devic
     if n:
         native.obs_row_expr(_expr_code(program), inputs, program.consts, outs, n)
     return dict(zip(program.results, outs))
+
+
+# ---- station identifiers: encode_statids ----------------------------------------------------------------------------------------------
+_BASE36 = frozenset("0123456789ABCDEFGHIJKLMNOPQRSTUVWXYZ")
+
+
+def statid_to_int(station_id: str) -> int:
+    """R: filters/tabular/encode_statids.py:45-57 — the base-36 value of the stripped, upper-cased identifier if it is made of 0-9A-Z,
+    else the first four bytes of the MD5 digest of the stripped identifier, little-endian.  The host's answer for the rows the kernel
+    leaves undecided."""
+    import hashlib
+
+    stripped = station_id.strip()
+    s = stripped.upper()
+    if s and _BASE36.issuperset(s):
+        return int(s, 36)
+    return int.from_bytes(hashlib.md5(stripped.encode()).digest()[:4], "little", signed=False)
+
+
+def _int64_codes(values: Sequence[int], what: str) -> np.ndarray:
+    beyond = sum(v >= 2**63 for v in values)
+    if beyond:
+        raise OverflowError(f"encode_statids: {beyond} of {what} encode to 2^63 or more, which no int64 column holds")
+    return np.array(values, dtype=np.int64).reshape(-1)
+
+
+def encode_statids(column: Any, dev: torch.device | None = None, packed: tuple[np.ndarray, int] | None = None) -> tuple[torch.Tensor, int]:
+    """``(code, host_rows)``: a column of station identifiers (``str``) as an int64 device row, and how many rows the host decided.
+    The column is packed into a byte matrix (``tables.text_matrix``), uploaded and encoded in ONE launch
+    (``native_text.encode_statids`` -> ``atx_text_encode_statids``); the rows the kernel flags undecided — non-ASCII, an interior NUL, 13
+    or more base-36 characters — are listed (``torch.nonzero``: the one synchronisation), evaluated by ``statid_to_int`` on the
+    original strings and scattered in.  A column wider than ``native_text.MAX_WIDTH`` bytes is evaluated on the host as a whole.  A value
+    of 2^63 or more raises ``OverflowError``.  ``packed``: what ``text_matrix(column)`` returned, if the caller has it already."""
+    from . import native_text
+    from .core import say_once
+    from .tables import text_matrix
+
+    text, width = packed if packed is not None else text_matrix(column)
+    dev = launch_device((), dev)
+    strings = host_array(column).reshape(-1)
+    n = text.shape[0]
+    if width > native_text.MAX_WIDTH:
+        say_once(_LOG, "statids-wide", "encode_statids: an identifier of %d bytes is wider than the kernel's %d; the whole column is "
+                 "encoded on the host", width, native_text.MAX_WIDTH, level=logging.INFO)
+        return _device(_int64_codes([statid_to_int(s) for s in strings.tolist()], f"{n} rows"), dev), n
+    code = torch.empty(n, dtype=torch.int64, device=dev)
+    if n == 0:
+        return code, 0
+    undecided = torch.empty(n, dtype=torch.uint8, device=dev)
+    native_text.encode_statids(_device(text, dev)[:, :width], code, undecided)
+    rows = torch.nonzero(undecided).reshape(-1)
+    if rows.numel():
+        values = _int64_codes([statid_to_int(strings[i]) for i in rows.cpu().tolist()], f"{n} rows")
+        code[rows] = _device(values, dev)
+    return code, rows.numel()

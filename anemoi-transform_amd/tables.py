@@ -2,8 +2,8 @@
 
 A table is a pandas DataFrame or a plain mapping ``name -> 1-D column``; a column is a numpy array, a pandas Series, a list or a
 torch tensor.  The first half are the column readers every tabular routine shares (``host_array``, ``column_kind``, ``datetime_ns``,
-``to_ns``, ``float_column``, ``on_device``, ``launch_device``) and the one gather of many columns by one row list (``take_rows`` ->
-``atx_obs_take_rows``).  The second half is ``Table``, which every tabular filter wraps its argument in.  The rules it states once:
+``to_ns``, ``float_column``, ``on_device``, ``launch_device``), ``text_matrix`` — what a column of strings is to a text kernel: a
+zero-padded byte matrix — and the one gather of many columns by one row list (``take_rows`` -> ``atx_obs_take_rows``).  The second half is ``Table``, which every tabular filter wraps its argument in.  The rules it states once:
 
   * the launch runs where the table's first CUDA tensor lives, else on this process's device (``stack.device()``) — looked up on
     first use, so a filter that raises a host error first never touches the device;
@@ -104,6 +104,33 @@ def float_column(column: Any, dev: torch.device) -> torch.Tensor:
     if column_kind(a) not in "iuf":
         raise ValueError(f"a numeric column is needed, got dtype {a.dtype}")
     return on_device(np.ascontiguousarray(a.reshape(-1), dtype=np.float64), dev)
+
+
+def text_matrix(column: Any) -> tuple[np.ndarray, int]:
+    """A column of ``str`` as the byte matrix the text kernels read (``include/atx_text.h``): uint8 ``[n, pitch]``, row ``r`` the bytes of
+    its string zero-padded to ``width`` (the longest string, at least 1), ``pitch`` the next multiple of 4.  Returns ``(matrix, width)``.
+    A pandas Series, an object array or a numpy ``U`` array.  The bytes are the code points themselves, which is UTF-8 for ASCII; a row
+    with a code point above 127 gets a first byte of 0x80, so that the kernel's own rule for such bytes hands the row to the host — its
+    other bytes mean nothing.  Anything in the column that is not a ``str`` (None, NaN, ``pd.NA``, a number, ``bytes``, an ``S`` array,
+    a tensor) raises ``ValueError`` with the count: numpy's own conversion would turn ``None`` into ``'None'``.  A ``U`` array is read
+    with vectorised numpy only; an object column goes through numpy's conversion to ``U`` once, which drops trailing U+0000."""
+    if isinstance(column, torch.Tensor):
+        raise ValueError(f"a text column holds str, got a {column.dtype} tensor")
+    a = host_array(column).reshape(-1)
+    if a.dtype.kind == "O":
+        not_str = sum(not isinstance(v, str) for v in a.tolist())
+        if not_str:
+            raise ValueError(f"a text column holds str: {not_str} of {a.size} entries are something else (None, NaN, a number, bytes)")
+        a = a.astype("U") if a.size else np.zeros(0, dtype="U1")
+    elif a.dtype.kind != "U":
+        raise ValueError(f"a text column holds str: {a.size} of {a.size} entries are of dtype {a.dtype}")
+    chars = a.dtype.itemsize // 4
+    points = np.ascontiguousarray(a.astype(a.dtype.newbyteorder("="), copy=False)).view(np.uint32).reshape(a.size, chars)
+    width = max(chars, 1)
+    matrix = np.zeros((a.size, (width + 3) // 4 * 4), dtype=np.uint8)
+    matrix[:, :chars] = points  # narrowed modulo 256: exact for ASCII
+    matrix[(points > 127).any(axis=1), 0] = 0x80
+    return matrix, width
 
 
 def gather(columns: Sequence[torch.Tensor], rows: torch.Tensor, check: bool = True) -> list[torch.Tensor]:

@@ -1,0 +1,231 @@
+"""``encode_statids`` and ``rename_tabular`` without a GPU: the registry names, the constructor default and the missing-column errors as
+the reference's tests state them, ``rename_tabular`` on every kind of table against the recorded frame, ``tables.text_matrix``, the
+restatement (tests/statids_restatement.py) against every recorded row (tests/golden/statids.json) with each of its defects caught by
+the edge table, and the header, binding, exports and argument checks of the companion library ``libatx_text``.
+"""
+
+from __future__ import annotations
+
+import ctypes
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+import statids_restatement as R
+from anemoi_transform_amd import native_text, tables
+from anemoi_transform_amd.filters import create_filter_by_name, filter_registry
+from anemoi_transform_amd.filters.tabular import EncodeStatids, RenameTabular
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "atx_text.h")
+GOLDEN = R.golden()
+EDGE = R.strings_of(GOLDEN["tables"]["edge"]["strings"])
+
+
+# ---- registration, construction, lookup ------------------------------------------------------------------------------------------------
+def test_registered_names_and_classes():
+    assert {"encode_statids", "rename_tabular"} <= set(filter_registry.registered)
+    f = create_filter_by_name("encode_statids")
+    assert isinstance(f, EncodeStatids) and f.station_id == "statid" and f.last_host_rows == 0  # R: encode_statids.py:39-40
+    assert create_filter_by_name("encode_statids", station_id="mystatid").station_id == "mystatid"
+    assert isinstance(create_filter_by_name("rename_tabular", columns={"a": "b"}), RenameTabular)
+    with pytest.raises(TypeError):
+        create_filter_by_name("rename_tabular")  # R: rename.py:39 — columns has no default
+
+
+@pytest.mark.parametrize("kind", ["frame", "mapping"])
+def test_missing_columns_raise_value_error_before_any_launch(kind):
+    """R: tests/tabular_filters/test_encode_statids.py, test_rename.py — the ``ValueError`` of ``raise_if_df_missing_cols``."""
+    pd = pytest.importorskip("pandas")
+    columns = {"col2": np.array(["a", "b"], dtype=object), "col3": np.array([0, 1])}
+    table = pd.DataFrame(columns) if kind == "frame" else columns
+    with pytest.raises(ValueError, match="DataFrame is missing columns: {'statid'}"):
+        create_filter_by_name("encode_statids")(table)
+    with pytest.raises(ValueError, match="DataFrame is missing columns: {'col1'}"):
+        create_filter_by_name("rename_tabular", columns={"col1": "x"})(table)
+
+
+def test_a_non_str_entry_raises_value_error_before_any_launch():
+    with pytest.raises(ValueError, match="1 of 3 entries"):
+        create_filter_by_name("encode_statids")({"statid": np.array(["a", None, "b"], dtype=object)})
+
+
+# ---- rename_tabular --------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", ["frame", "arrays", "tensors"])
+def test_rename_tabular_keeps_order_and_the_callers_table(kind):
+    pd = pytest.importorskip("pandas")
+    rec = GOLDEN["rename"]
+    f = create_filter_by_name("rename_tabular", columns=rec["columns"])
+    names = list(rec["before"])
+    if kind == "frame":
+        table = pd.DataFrame(rec["before"])
+        got = f(table)
+        assert isinstance(got, pd.DataFrame) and got is not table and list(table.columns) == names
+        assert list(got.columns) == rec["after_names"]
+        for j, want in enumerate(rec["after"]):
+            assert got.iloc[:, j].tolist() == want
+        return
+    table = {c: np.array(v, dtype=object if isinstance(v[0], str) else None) for c, v in rec["before"].items()}
+    if kind == "tensors":
+        table = {c: (v if v.dtype == object else torch.from_numpy(v)) for c, v in table.items()}
+    got = f(table)
+    assert isinstance(got, dict) and got is not table and list(table) == names and list(got) == rec["after_names"]
+    for j, (name, want) in enumerate(zip(rec["after_names"], rec["after"])):
+        assert got[name] is table[names[j]]  # nothing is copied: the caller's own columns under their new names
+        assert got[name].tolist() == want
+
+
+# ---- text_matrix -----------------------------------------------------------------------------------------------------------------------
+def test_text_matrix_layout():
+    pd = pytest.importorskip("pandas")
+    strings = ["ab", "", "06610", " x\t", "a\x00b"]
+    for column in (np.array(strings), np.array(strings, dtype=object), pd.Series(strings, dtype=object), np.array(strings).astype(">U5")):
+        m, width = tables.text_matrix(column)
+        assert m.dtype == np.uint8 and m.shape == (5, 8) and width == 5 and m.flags.c_contiguous
+        for row, s in zip(m, strings):
+            assert row.tobytes() == s.encode().ljust(8, b"\x00")
+    m, width = tables.text_matrix(np.array(["", ""]))
+    assert m.shape == (2, 4) and width == 1 and not m.any()
+    m, width = tables.text_matrix(np.array(["abcd"]))
+    assert m.shape == (1, 4) and width == 4
+    m, width = tables.text_matrix(np.zeros(0, dtype=object))
+    assert m.shape[0] == 0 and width >= 1
+
+
+def test_text_matrix_marks_non_ascii_rows_for_the_host():
+    strings = ["abc", "ı", "xéy", "١", "z\x7f"]
+    m, width = tables.text_matrix(np.array(strings))
+    assert width == 3 and list(m[:, 0] == 0x80) == [False, True, True, True, False]
+    undecided, _ = R.kernel_rules(m, width)
+    assert list(undecided) == [False, True, True, True, False]
+    assert m[0].tobytes() == b"abc\x00" and m[4].tobytes() == b"z\x7f\x00\x00"
+
+
+@pytest.mark.parametrize("column, count", [
+    (np.array(["a", None], dtype=object), 1), (np.array(["a", float("nan"), 3], dtype=object), 2), (np.array([b"a", "b"], dtype=object), 1),
+    (np.array([b"ab", b"c"]), 2), (np.array([1, 2, 3]), 3), (np.array([1.5]), 1)])
+def test_text_matrix_takes_str_only(column, count):
+    with pytest.raises(ValueError, match=f"{count} of {len(column)} entries"):
+        tables.text_matrix(column)
+
+
+def test_text_matrix_rejects_pandas_missing_values():
+    pd = pytest.importorskip("pandas")
+    with pytest.raises(ValueError, match="1 of 2 entries"):
+        tables.text_matrix(pd.Series(["a", pd.NA], dtype="string"))
+    with pytest.raises(ValueError):
+        tables.text_matrix(torch.zeros(3))
+
+
+# ---- the restatement against the recorded frames ----------------------------------------------------------------------------------------
+def test_golden_holds_the_stated_literals_and_edges():
+    codes = dict(zip(EDGE, GOLDEN["tables"]["edge"]["codes"]))
+    stated = {"": 3649838548, " ": 3649838548, "a-b": 1508745868, "-" * 56: 413555202, "-" * 64: 3508534743, " ab ": 371, "here": 812282,
+              "there": 49521146, "1001": 46657, "\x1c07\x1f": 7, "1Y2P0IJ32E8E7": 2**63 - 1, "1Y2P0IJ32E8E8": 2**63, "ı": 18, "ſ": 28}
+    for s, v in stated.items():
+        assert codes[s] == v, (s, codes[s], v)
+    assert len(EDGE) >= 80 and GOLDEN["tables"]["edge"]["width"] == R.MAX_WIDTH
+    assert EDGE == R.edge_strings()
+    for n in R.SEEDED_ROWS:
+        table = GOLDEN["tables"][f"seeded_{n}"]
+        assert R.strings_of(table["strings"]) == R.seeded_strings(n) and table["dtype"] == "int64"
+        assert 0 < table["undecided"] * 10 <= n  # the kernel alone decides at least 90 %, and not everything
+    assert GOLDEN["tables"]["overflow"]["dtype"] == "uint64"
+
+
+@pytest.mark.parametrize("name", sorted(GOLDEN["tables"]))
+def test_restatement_equals_every_recorded_row(name):
+    table = GOLDEN["tables"][name]
+    strings = R.strings_of(table["strings"])
+    assert [R.statid_to_int(s) for s in strings] == table["codes"]
+    from anemoi_transform_amd import obs
+
+    assert [obs.statid_to_int(s) for s in strings] == table["codes"]
+    text, width = R.pack(strings)
+    assert width == table["width"] and int(R.kernel_rules(text, width)[0].sum()) == table["undecided"]
+
+
+def test_md5_written_out_is_hashlibs():
+    import hashlib
+
+    for n in (0, 1, 55, 56, 63, 64, 65, 119, 120, 256):
+        message = bytes((7 * i + n) % 251 for i in range(n))
+        assert R.md5_digest(message) == hashlib.md5(message).digest()
+
+
+@pytest.mark.parametrize("defect", R.DEFECTS)
+def test_the_edge_table_catches_every_defect(defect):
+    wrong = [s for s, code in zip(EDGE, GOLDEN["tables"]["edge"]["codes"]) if R.statid_to_int(s, defect) != code]
+    assert wrong, f"no edge row tells {defect} from the reference"
+
+
+def test_kernel_rules_on_the_edge_table():
+    text, width = R.pack(EDGE)
+    undecided, _ = R.kernel_rules(text, width)
+    flagged = {s for s, u in zip(EDGE, undecided) if u}
+    assert {"ı", "ſ", "ß", "\xa0x", "١", "a\x00b", "\x00ab", "1Y2P0IJ32E8E7", "1Y2P0IJ32E8E8", "0000000000001"} <= flagged
+    assert not {"", " ", "a-b", "-" * 64, "zzzzzzzzzzzz", " " * 13, "z" * 12 + " ", "\x1c07\x1f", "\x7f"} & flagged
+    code, flags = R.expected(text, width)
+    want = GOLDEN["tables"]["edge"]["codes"]
+    assert all(int(c) == w for c, w, u in zip(code, want, flags) if not u) and not code[flags != 0].any()
+    text_tm, width_tm = tables.text_matrix(np.array(EDGE, dtype=object))  # the package's packing flags the same rows
+    assert width_tm == width and np.array_equal(R.kernel_rules(text_tm, width_tm)[0], undecided)
+
+
+# ---- the C ABI of the companion library -------------------------------------------------------------------------------------------------
+def header_declarations() -> list[str]:
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    return re.findall(r"^ATX_TEXT_API [^;(]*?\b(atx_text_[a-z_0-9]+)\s*\(", text, flags=re.M)
+
+
+def test_header_declares_three_entry_points_and_cites_the_reference():
+    text = open(HEADER).read()
+    assert header_declarations() == ["atx_text_version", "atx_text_last_error", "atx_text_encode_statids"]
+    assert "R: filters/tabular/encode_statids.py:45-57" in text and '#include "atx.h"' in text
+    assert re.search(r"#define ATX_TEXT_MAX_WIDTH 256\b", text) and native_text.MAX_WIDTH == 256 == R.MAX_WIDTH
+    assert re.search(r"int atx_text_encode_statids\(const uint8_t\* text, int64_t n, int32_t width, int64_t pitch, int64_t\* code, "
+                     r"uint8_t\* undecided,\s+void\* stream\);", text)
+    assert sorted(native_text.SIGNATURES) == sorted(header_declarations())
+    assert len(native_text.SIGNATURES["atx_text_encode_statids"][1]) == 7
+
+
+def test_library_exports_exactly_the_header():
+    nm = shutil.which("nm") or "/opt/rocm/lib/llvm/bin/llvm-nm"
+    if not (shutil.which("nm") or os.path.exists(nm)):
+        pytest.skip("no nm")
+    listing = subprocess.run([nm, "-D", "--defined-only", native_text.lib_path()], capture_output=True, text=True, check=True).stdout
+    defined = sorted(line.split()[-1].split("@")[0] for line in listing.splitlines() if line.strip())
+    assert defined == sorted(header_declarations())
+    assert {line.split()[-2] for line in listing.splitlines() if line.strip()} == {"T"}
+
+
+def test_header_is_plain_c99(tmp_path):
+    gcc = shutil.which("gcc")
+    if gcc is None:
+        pytest.skip("no C compiler")
+    src = tmp_path / "use_header.c"
+    src.write_text('#include "atx_text.h"\nint use(void) { return ATX_TEXT_VERSION + ATX_TEXT_MAX_WIDTH + ATX_OK + ATX_EINVAL; }\n')
+    run = subprocess.run([gcc, "-std=c99", "-Wall", "-Wextra", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), "-c", str(src),
+                          "-o", str(tmp_path / "use_header.o")], capture_output=True, text=True)
+    assert run.returncode == 0, run.stderr
+
+
+def test_abi_argument_validation_without_a_gpu():
+    lib = native_text.load()
+    assert lib.atx_text_version() == 420
+    one = ctypes.c_void_p(16)  # never dereferenced: validation fails first
+    call = lib.atx_text_encode_statids
+    assert call(one, -1, 8, 8, one, one, None) == native_text.EINVAL and b"negative" in lib.atx_text_last_error()
+    for width in (0, -3, 257):
+        assert call(one, 4, width, 512, one, one, None) == native_text.EINVAL and b"width" in lib.atx_text_last_error()
+    assert call(one, 4, 8, 7, one, one, None) == native_text.EINVAL and b"pitch" in lib.atx_text_last_error()
+    for args in ((None, 4, 8, 8, one, one, None), (one, 4, 8, 8, None, one, None), (one, 4, 8, 8, one, None, None)):
+        assert call(*args) == native_text.EINVAL and b"null" in lib.atx_text_last_error()
+    assert call(None, 0, 8, 8, None, None, None) == native_text.OK  # no rows: nothing launched, no storage needed
+    assert call(None, 0, 256, 256, None, None, None) == native_text.OK
+    assert call(None, 0, 0, 8, None, None, None) == native_text.EINVAL  # ... but the rest is still validated

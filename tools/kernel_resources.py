@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Registers, LDS and scratch of every kernel in libatx.so, read from the code objects embedded in the library (no GPU, no recompilation):
-   python tools/kernel_resources.py [--lib PATH] [--scratch] [--match TEXT]
+   python tools/kernel_resources.py [--lib PATH] [--scratch] [--match TEXT] [--json FILE]
+(--lib anemoi-transform_amd/lib/libatx_text.so reads the companion library of the text kernels: profiles/statids_resources.json)
 (--scratch: only kernels that use private scratch memory; --match: only kernels whose name holds TEXT, e.g. --match obs_ for the
 observation kernels: obs_forcings_kernel, obs_view_angles_kernel, obs_planck_bt_kernel, the gridding and superob kernels)
 A kernel that indexes a private array with a run-time subscript ends up in scratch memory and loses most of its bandwidth — round 3
@@ -57,12 +58,21 @@ def main():
     ap.add_argument("--lib", default=os.path.join(ROOT, "anemoi-transform_amd", "lib", "libatx.so"))
     ap.add_argument("--scratch", action="store_true")
     ap.add_argument("--match", default=None)
+    ap.add_argument("--json", default=None, help="also write the rows, with demangled names and waves per SIMD, to this file")
     args = ap.parse_args()
     rows = kernel_resources(args.lib)
     if args.match:
         rows = [r for r in rows if args.match in r["name"]]
     if args.scratch:
         rows = [r for r in rows if r["scratch"] > 0]
+    if args.json:
+        import json
+
+        # gfx950: 512 VGPRs per lane and SIMD, allocated in blocks of 8, at most 8 waves per SIMD; LDS and scratch do not bound these kernels' waves unless listed
+        record = [{**r, "name": nice, "waves_per_simd": min(8, 512 // max(8, (r["vgpr"] + 7) // 8 * 8))} for r, nice in zip(rows, demangle([r["name"] for r in rows]))]
+        with open(args.json, "w") as f:
+            json.dump({"library": os.path.relpath(args.lib, ROOT), "kernels": record}, f, indent=1)
+            f.write("\n")
     for r, nice in zip(rows, demangle([r["name"] for r in rows])):
         print(f"vgpr {r['vgpr']:4d} sgpr {r['sgpr']:4d} lds {r['lds']:6d} scratch {r['scratch']:5d}  {nice[:160]}")
     print(f"{len(rows)} kernels", file=sys.stderr)
