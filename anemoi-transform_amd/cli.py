@@ -8,6 +8,7 @@ package, so recipes such as ``regrid: {matrix: file.npz}`` / ``regrid: {mask: fi
 
     atx make-regrid-file knn-matrix      SOURCE TARGET --k 4 --output m.npz [--device]
     atx make-regrid-file bilinear-matrix o96 1.0 --output m.npz          (octahedral sources)
+    atx make-regrid-file box-average-matrix SOURCE TARGET --output m.npz [--device]   (row-structured grids)
     atx make-regrid-file global-on-lam-mask GLOBAL LAM --distance-km 10 --output mask.npz [--device]
     atx get-grid o1280 --output grid-o1280.npz
     atx filters list
@@ -30,13 +31,14 @@ def _grid(spec: str):
     return lookup(spec)
 
 
-def _rows(spec: str):
-    """Row structure of a formula source grid (O<N>, F<N>, N320-sized, regular lat-lon increments) for the bilinear builder."""
+def _rows(spec: str, kind: str = "bilinear-matrix"):
+    """Row structure of a formula grid (O<N>, F<N>, N320-sized, regular lat-lon increments) for the bilinear and box-average builders."""
     from .grids import row_structure
 
     rows = row_structure(spec)
     if rows is None:
-        raise SystemExit(f"bilinear-matrix needs a row-structured formula source grid (O<N>, F<N>, n320-sized, dlat/dlon), got {spec!r}")
+        which = "source grid" if kind == "bilinear-matrix" else "grid"
+        raise SystemExit(f"{kind} needs a row-structured formula {which} (O<N>, F<N>, n320-sized, dlat/dlon), got {spec!r}")
     return rows
 
 
@@ -55,6 +57,11 @@ def main(argv: list[str] | None = None) -> int:
     bil.add_argument("source_grid")
     bil.add_argument("target_grid")
     bil.add_argument("--output", required=True)
+    box = mk.add_parser("box-average-matrix", help="grid-box-average (cell-overlap) weights between two row-structured grids")
+    box.add_argument("source_grid")
+    box.add_argument("target_grid")
+    box.add_argument("--device", action="store_true", help="build the matrix on the GPU (atx_plan_box_average_*): the same file")
+    box.add_argument("--output", required=True)
     gol = mk.add_parser("global-on-lam-mask", help="indices of the global points near a limited-area grid")
     gol.add_argument("global_grid")
     gol.add_argument("lam_grid")
@@ -93,6 +100,10 @@ def main(argv: list[str] | None = None) -> int:
     elif args.kind == "bilinear-matrix":
         src, tgt = _grid(args.source_grid), _grid(args.target_grid)
         interp.save_matrix_npz(args.output, interp.bilinear_rows(*_rows(args.source_grid), tgt), src, tgt)
+    elif args.kind == "box-average-matrix":
+        src_rows, tgt_rows = _rows(args.source_grid, "box-average-matrix"), _rows(args.target_grid, "box-average-matrix")
+        src, tgt = _grid(args.source_grid), _grid(args.target_grid)
+        interp.save_matrix_npz(args.output, interp.box_average_rows(src_rows, tgt_rows, device=args.device), src, tgt)
     else:
         glob, lam = _grid(args.global_grid), _grid(args.lam_grid)
         mask = spatial.global_on_lam_mask(np.asarray(lam["latitudes"]), np.asarray(lam["longitudes"]), np.asarray(glob["latitudes"]),

@@ -107,11 +107,21 @@ class EarthkitRegrid(_Interpolator):
     Neither the package nor its inventory exists offline, so the MATRIX is built in-tree instead and runs on the same
     HBM gather as ``matrix=``: for ``method="linear"`` between formula grids (``O<N>``, ``F<N>``, ``N320-sized``, regular
     lat-lon increments as the source; any resolvable grid as the target) the 4-point bilinear weights of
-    ``interp.bilinear_rows``.  MIR's linear method triangulates the source points (3 weights per target) — same order of
+    ``interp.bilinear_rows`` (4 of the ~180 source points under an O96 cell when coarsening from O1280: it aliases).  MIR's linear method triangulates the source points (3 weights per target) — same order of
     accuracy, not the same numbers: **parity with MIR is unpinned** (SURVEY.md §8c names this boundary as unpinned in the
     reference's own tests, too: tests/field_filters/test_regrid.py:83-88 is a smoke test).  A warning says so once per
-    filter.  Every other method / grid raises ``NotImplementedError`` pointing at ``matrix=``.
+    filter.
+
+    ``method="grid-box-average"`` (what coarsening needs: O1280 -> O96, 0.25 -> 1 degree) between two such row-structured grids
+    builds the area-weighted cell-overlap matrix of ``interp.box_average_rows`` — on the device (``atx_plan_box_average_count`` /
+    ``_fill``, ``include/atx_plan.h``) when there is one, else on the host; the arrays are the same bit for bit — and runs it
+    through ``GatherPlan.from_matrix`` like any ``matrix=``: fusion, sharding, ordered traversal and float32 stacks are those of
+    the existing routes.  The construction is MIR's grid-box method; parity with MIR is unpinned, and the filter says so once.
+    ``method="nearest-neighbour"`` (earthkit-regrid's spelling) is the k = 1 search of ``method="nearest"`` between two named
+    grids, with the same warning.  Every other method / grid raises ``NotImplementedError`` pointing at ``matrix=``.
     """
+
+    METHODS = ("linear", "grid-box-average", "nearest-neighbour")
 
     def __init__(self, *, in_grid: Any, out_grid: Any, method: str = "linear", check: bool = False) -> None:
         from ..grids import row_structure
@@ -122,19 +132,51 @@ class EarthkitRegrid(_Interpolator):
         self.method = method
         if check:
             LOG.warning("Check is not supported by EarthkitRegrid")
+        if method == "nearest-neighbour":
+            self._nearest(in_grid, out_grid)
+            return
         rows = row_structure(self.in_grid)
-        if method != "linear" or rows is None:
+        out_rows = row_structure(self.out_grid) if method == "grid-box-average" and self.out_grid is not None else None
+        if method not in self.METHODS or rows is None or (method == "grid-box-average" and self.out_grid is not None and out_rows is None):
             raise NotImplementedError(
                 f"regrid(method={method!r}, in_grid={in_grid!r}) needs earthkit-regrid and its remote matrix inventory, which are "
                 "not available here; the in-tree default covers method='linear' from O<N> / F<N> / regular lat-lon source grids. "
                 "Pass a pre-computed `matrix` (anemoi_transform_amd.interp writes the same npz format) or use method='nearest'"
+                + ("; method='grid-box-average' needs BOTH grids to be row-structured formula grids (O<N>, F<N>, N<N>-sized, "
+                   f"regular lat-lon increments), got out_grid={out_grid!r}" if method == "grid-box-average" else "")
             )
         self.out_griddata = as_griddata(out_grid) or {}
         if "latitudes" not in self.out_griddata:
             raise ValueError("out_grid is required, but not provided")
-        LOG.warning("regrid(method='linear'): in-tree 4-point bilinear weights stand in for earthkit-regrid's MIR matrix "
-                    "(remote inventory unavailable); values agree with MIR to interpolation accuracy, not bit for bit")
-        self.plan = _ordered(GatherPlan.from_matrix(bilinear_rows(*rows, self.out_griddata)), self.out_griddata)
+        if method == "grid-box-average":
+            import torch
+
+            from ..interp import box_average_rows
+
+            LOG.warning("regrid(method='grid-box-average'): in-tree cell-overlap weights (interp.box_average_rows) stand in for "
+                        "earthkit-regrid's MIR matrix (remote inventory unavailable); the construction is MIR's grid-box method, "
+                        "parity with MIR is unpinned")
+            matrix = box_average_rows(rows, out_rows, device=torch.cuda.is_available())  # the same arrays either way
+        else:
+            LOG.warning("regrid(method='linear'): in-tree 4-point bilinear weights stand in for earthkit-regrid's MIR matrix "
+                        "(remote inventory unavailable); values agree with MIR to interpolation accuracy, not bit for bit")
+            matrix = bilinear_rows(*rows, self.out_griddata)
+        self.plan = _ordered(GatherPlan.from_matrix(matrix), self.out_griddata)
+
+    def _nearest(self, in_grid: Any, out_grid: Any) -> None:
+        """earthkit-regrid's ``nearest-neighbour``: the k = 1 search of ``method="nearest"`` between two named grids."""
+        from ..interp import nearest_grid_points
+
+        src = as_griddata(in_grid)
+        self.out_griddata = as_griddata(out_grid) or {}
+        if src is None:
+            raise ValueError("in_grid is required, but not provided")
+        if "latitudes" not in self.out_griddata:
+            raise ValueError("out_grid is required, but not provided")
+        LOG.warning("regrid(method='nearest-neighbour'): the in-tree k = 1 search of method='nearest' stands in for earthkit-regrid's "
+                    "MIR matrix (remote inventory unavailable); parity with MIR is unpinned (ties between equidistant points)")
+        index = nearest_grid_points(src["latitudes"], src["longitudes"], self.out_griddata["latitudes"], self.out_griddata["longitudes"])
+        self.plan = _ordered(GatherPlan(len(src["latitudes"]), len(index), index=index), self.out_griddata)
 
     def plan_for(self, first_field: Any) -> GatherPlan:
         n = int(np.prod(first_field.shape))

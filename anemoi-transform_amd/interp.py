@@ -30,6 +30,8 @@ __all__ = [
     "csr_uniform_k",
     "bilinear_octahedral",
     "bilinear_rows",
+    "box_row_table",
+    "box_average_rows",
     "save_matrix_npz",
     "load_matrix_npz",
 ]
@@ -433,6 +435,137 @@ def bilinear_rows(row_latitudes: np.ndarray, row_lengths: np.ndarray, out_grid: 
 def bilinear_octahedral(n: int, out_grid: dict) -> dict[str, np.ndarray]:
     """``bilinear_rows`` from the octahedral grid ``O<n>`` (BASELINE config 2: O96 -> 1 degree)."""
     return bilinear_rows(gaussian_latitudes(2 * n), octahedral_row_lengths(n), out_grid)
+
+
+def box_row_table(rows: tuple[np.ndarray, np.ndarray]) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """``(z, lengths, starts)`` of a row-structured grid's CELLS: ``z`` float64 ``[R + 1]`` is the sine of the rows' latitude edges
+    (90, the midpoints between adjacent row latitudes, -90), descending, with ``z[0] = 1`` and ``z[R] = -1`` set exactly; ``lengths``
+    int64 ``[R]``; ``starts`` int64 ``[R + 1]`` (``starts[R]`` is the number of points).  Rows that do not descend strictly or hold
+    fewer than 2 points raise ``ValueError``."""
+    lats = np.asarray(rows[0], dtype=np.float64)
+    lengths = np.asarray(rows[1])
+    if lats.ndim != 1 or lats.shape != lengths.shape or len(lats) < 1 or lengths.dtype.kind not in "iu":
+        raise ValueError("a row structure is (row latitudes [R], integer row lengths [R]) with R >= 1")
+    lengths = lengths.astype(np.int64)
+    if np.any(np.diff(lats) >= 0) or lats[0] > 90.0 or lats[-1] < -90.0:
+        raise ValueError("rows must be given north to south with strictly decreasing latitudes within [-90, 90]")
+    if np.any(lengths < 2):
+        raise ValueError("grid-box averaging needs at least 2 points in every row")
+    edges = np.concatenate([[90.0], 0.5 * (lats[:-1] + lats[1:]), [-90.0]])
+    z = np.sin(np.deg2rad(edges))
+    z[0], z[-1] = 1.0, -1.0
+    if np.any(np.diff(z) >= 0):  # a pole row AT the pole is a half-height cell; two rows there would be a cell of no height
+        raise ValueError("the latitude edges of the rows do not descend strictly")
+    starts = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+    if starts[-1] >= 2**31:
+        raise NotImplementedError("grids with 2^31 or more points are not supported")
+    return z, lengths, starts
+
+
+def _sequential_row_sums(raw: np.ndarray, indptr: np.ndarray) -> np.ndarray:
+    """Sum of every CSR row accumulated from 0 in the order of its entries (``np.add.reduceat`` may add pairwise)."""
+    counts = np.diff(indptr)
+    tot = np.zeros(len(counts), dtype=np.float64)
+    first = indptr[:-1]
+    for k in range(int(counts.max()) if counts.size else 0):
+        live = np.flatnonzero(counts > k)
+        tot[live] += raw[first[live] + k]
+    return tot
+
+
+def box_average_rows(src_rows: tuple[np.ndarray, np.ndarray], tgt_rows: tuple[np.ndarray, np.ndarray], *,
+                     device: bool = False) -> dict[str, np.ndarray]:
+    """Grid-box-average (first-order conservative) weights between two ROW-STRUCTURED global grids, each given as
+    ``(row latitudes north to south, points per row)`` (``grids.row_structure``): the value of a target cell is the mean of the
+    source cells under it, weighted by the area they share.
+
+    Cells.  Row ``r`` spans the latitude edges ``e_r .. e_{r+1}``: ``e_0 = 90``, ``e_R = -90``, midpoints between row latitudes
+    otherwise; ``z = sin(deg2rad(e))`` in float64 here on the host, ``z_0 = 1`` and ``z_R = -1`` exactly (``box_row_table``).  Cell
+    ``j`` of a row of ``n`` is the arc ``[(j - 1/2) 360/n, (j + 1/2) 360/n)``; cell 0 straddles 0 degrees.
+
+    Latitude.  ``dz = min(zt[r], zs[q]) - max(zt[r+1], zs[q+1])``; source row ``q`` takes part in target row ``r`` iff
+    ``dz > 2**-40 * (zt[r] - zt[r+1])`` (edges of aligned lat-lon pairs that are equal in exact arithmetic differ in the last
+    bit; such slivers are ~1e-14 of a row, real overlaps are at least 1 / (row ratio)).
+
+    Longitude.  In units of ``360 / (2 ns nt)`` degrees the edges of target cell ``i`` (of ``nt``) and source cell ``j`` (of ``ns``)
+    are the integers ``(2i -+ 1) ns`` and ``(2j -+ 1) nt`` modulo ``2 ns nt``; ``ov`` is the length of the arcs' intersection, an
+    exact int64 including the wrap.  The entry exists iff ``ov > 0``.
+
+    Weights.  ``raw = dz * (float(ov) / float(2 ns nt))``; the entries of a target are kept in ascending source index, ``tot`` is
+    their sum accumulated from 0 in that order, ``w = raw / tot``.
+
+    Returns the CSR triplet of the MIR npz format, as ``ell_to_csr`` does.  ``device=False`` evaluates the statement in numpy;
+    ``device=True`` runs ``atx_plan_box_average_count`` / ``_fill`` (``include/atx_plan.h``) and returns the same arrays bit
+    for bit.  2^31 or more entries raise ``NotImplementedError``.
+    """
+    zs, slen, sstart = box_row_table(src_rows)
+    zt, tlen, tstart = box_row_table(tgt_rows)
+    n_src, n_tgt = int(sstart[-1]), int(tstart[-1])
+    if device:
+        return _box_average_device((zs, slen, sstart), (zt, tlen, tstart))
+
+    targets, columns, raws = [], [], []
+    for r in range(len(tlen)):
+        top, bot, nt = zt[r], zt[r + 1], int(tlen[r])
+        dz_rows = np.minimum(top, zs[:-1]) - np.maximum(bot, zs[1:])
+        i = np.arange(nt, dtype=np.int64)
+        row_t, row_c, row_w = [], [], []
+        for q in np.flatnonzero(dz_rows > 2.0**-40 * (top - bot)):
+            ns = int(slen[q])
+            a, b = (2 * i - 1) * ns, (2 * i + 1) * ns
+            jlo = (a - nt) // (2 * nt) + 1  # the first source cell whose east edge lies east of the target's west edge ...
+            count = (b + nt - 1) // (2 * nt) - jlo + 1  # ... to the last whose west edge lies west of the target's east edge
+            cell = np.repeat(i, count)
+            ju = np.repeat(jlo, count) + (np.arange(int(count.sum()), dtype=np.int64) - np.repeat(np.cumsum(count) - count, count))
+            ov = np.minimum(b[cell], (2 * ju + 1) * nt) - np.maximum(a[cell], (2 * ju - 1) * nt)
+            row_t.append(cell)
+            row_c.append(sstart[q] + np.mod(ju, ns))
+            row_w.append(dz_rows[q] * (ov.astype(np.float64) / float(2 * ns * nt)))
+        if row_t:
+            cell, column, raw = np.concatenate(row_t), np.concatenate(row_c), np.concatenate(row_w)
+            order = np.lexsort((column, cell))  # by target, ascending source index within it (a wrapped run's j = 0 ... part first)
+            targets.append(tstart[r] + cell[order])
+            columns.append(column[order])
+            raws.append(raw[order])
+    target = np.concatenate(targets) if targets else np.zeros(0, dtype=np.int64)
+    column = np.concatenate(columns) if columns else np.zeros(0, dtype=np.int64)
+    raw = np.concatenate(raws) if raws else np.zeros(0, dtype=np.float64)
+    if len(raw) >= 2**31:
+        raise NotImplementedError("matrices with 2^31 or more entries are not supported")
+    indptr = np.concatenate([[0], np.cumsum(np.bincount(target, minlength=n_tgt))]).astype(np.int64)
+    tot = _sequential_row_sums(raw, indptr)
+    return dict(
+        matrix_data=raw / np.repeat(tot, np.diff(indptr)),
+        matrix_indices=column.astype(np.int32),
+        matrix_indptr=indptr.astype(np.int32),
+        matrix_shape=np.array([n_tgt, n_src]),
+    )
+
+
+def _box_average_device(src: tuple[np.ndarray, np.ndarray, np.ndarray], tgt: tuple[np.ndarray, np.ndarray, np.ndarray]) -> dict[str, np.ndarray]:
+    """``box_average_rows`` on the current device: count, scan (``torch.cumsum``), fill.  The tables were validated by ``box_row_table``."""
+    import torch
+
+    from . import native_plan
+
+    if not torch.cuda.is_available():
+        raise RuntimeError("box_average_rows(device=True) needs a GPU; device=False evaluates the same statement on the host")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    tables = [native_plan.RowTable(*(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in t), n_points=int(t[2][-1])) for t in (src, tgt)]
+    n_src, n_tgt = tables[0].n_points, tables[1].n_points
+    count = torch.empty(n_tgt, dtype=torch.int64, device=dev)
+    native_plan.box_average_count(tables[0], tables[1], count)
+    ends = torch.cumsum(count, dim=0)
+    nnz = int(ends[-1].item())
+    if nnz >= 2**31:
+        raise NotImplementedError("matrices with 2^31 or more entries are not supported")
+    indptr = torch.zeros(n_tgt + 1, dtype=torch.int32, device=dev)
+    indptr[1:] = ends.to(torch.int32)
+    indices = torch.empty(nnz, dtype=torch.int32, device=dev)
+    data = torch.empty(nnz, dtype=torch.float64, device=dev)
+    native_plan.box_average_fill(tables[0], tables[1], indptr, indices, data)
+    return dict(matrix_data=data.cpu().numpy(), matrix_indices=indices.cpu().numpy(), matrix_indptr=indptr.cpu().numpy(),
+                matrix_shape=np.array([n_tgt, n_src]))
 
 
 def save_matrix_npz(path: str, matrix: dict[str, np.ndarray], in_grid: dict, out_grid: dict) -> None:
