@@ -9,6 +9,8 @@ package, so recipes such as ``regrid: {matrix: file.npz}`` / ``regrid: {mask: fi
     atx make-regrid-file knn-matrix      SOURCE TARGET --k 4 --output m.npz [--device]
     atx make-regrid-file bilinear-matrix o96 1.0 --output m.npz          (octahedral sources)
     atx make-regrid-file box-average-matrix SOURCE TARGET --output m.npz [--device]   (row-structured grids)
+    atx make-regrid-file linear-matrix   SOURCE TARGET [--max-edge-km X] [--outside raise|nearest] [--device] --output m.npz
+                                         (any source points: triangulated, three barycentric weights per target)
     atx make-regrid-file global-on-lam-mask GLOBAL LAM --distance-km 10 --output mask.npz [--device]
     atx get-grid o1280 --output grid-o1280.npz
     atx filters list
@@ -62,6 +64,14 @@ def main(argv: list[str] | None = None) -> int:
     box.add_argument("target_grid")
     box.add_argument("--device", action="store_true", help="build the matrix on the GPU (atx_plan_box_average_*): the same file")
     box.add_argument("--output", required=True)
+    lin = mk.add_parser("linear-matrix", help="linear weights from any source points: spherical Delaunay triangulation, 3 weights per target")
+    lin.add_argument("source_grid")
+    lin.add_argument("target_grid")
+    lin.add_argument("--max-edge-km", type=float, default=None,
+                     help="triangles with a longer edge are outside the domain (a limited-area source: a few grid spacings)")
+    lin.add_argument("--outside", choices=("raise", "nearest"), default="raise", help="targets outside the domain: an error, or the nearest source point")
+    lin.add_argument("--device", action="store_true", help="locate the targets on the GPU (atx_mesh_locate): the same file")
+    lin.add_argument("--output", required=True)
     gol = mk.add_parser("global-on-lam-mask", help="indices of the global points near a limited-area grid")
     gol.add_argument("global_grid")
     gol.add_argument("lam_grid")
@@ -104,6 +114,13 @@ def main(argv: list[str] | None = None) -> int:
         src_rows, tgt_rows = _rows(args.source_grid, "box-average-matrix"), _rows(args.target_grid, "box-average-matrix")
         src, tgt = _grid(args.source_grid), _grid(args.target_grid)
         interp.save_matrix_npz(args.output, interp.box_average_rows(src_rows, tgt_rows, device=args.device), src, tgt)
+    elif args.kind == "linear-matrix":
+        src, tgt = _grid(args.source_grid), _grid(args.target_grid)
+        try:
+            matrix = interp.linear_triangulated(src, tgt, max_edge_km=args.max_edge_km, outside=args.outside, device=args.device)
+        except ValueError as e:
+            raise SystemExit(f"linear-matrix: {e}") from None
+        interp.save_matrix_npz(args.output, matrix, src, tgt)
     else:
         glob, lam = _grid(args.global_grid), _grid(args.lam_grid)
         mask = spatial.global_on_lam_mask(np.asarray(lam["latitudes"]), np.asarray(lam["longitudes"]), np.asarray(glob["latitudes"]),

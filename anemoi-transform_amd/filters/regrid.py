@@ -118,10 +118,18 @@ class EarthkitRegrid(_Interpolator):
     through ``GatherPlan.from_matrix`` like any ``matrix=``: fusion, sharding, ordered traversal and float32 stacks are those of
     the existing routes.  The construction is MIR's grid-box method; parity with MIR is unpinned, and the filter says so once.
     ``method="nearest-neighbour"`` (earthkit-regrid's spelling) is the k = 1 search of ``method="nearest"`` between two named
-    grids, with the same warning.  Every other method / grid raises ``NotImplementedError`` pointing at ``matrix=``.
+    grids, with the same warning.
+
+    ``method="linear-unstructured"`` takes ANY source ``as_griddata`` resolves (a dict of coordinates, a grid name, an npz path, a
+    Field: limited-area grids, ICON, scattered points): ``interp.linear_triangulated`` triangulates the source points on the sphere
+    and gives every target the three barycentric weights of the triangle under it, which is how MIR's linear method is built —
+    the point location on the device (``atx_mesh_locate``, ``include/atx_mesh.h``) when there is one, else on the host; the arrays
+    are the same bit for bit.  Targets outside the triangulation raise, and no edge limit is set: a limited-area source goes through
+    ``interp.linear_triangulated(max_edge_km=...)`` or ``atx make-regrid-file linear-matrix`` and then ``matrix=``.  Parity with MIR
+    is unpinned, and the filter says so once.  Every other method / grid raises ``NotImplementedError`` pointing at ``matrix=``.
     """
 
-    METHODS = ("linear", "grid-box-average", "nearest-neighbour")
+    METHODS = ("linear", "grid-box-average", "nearest-neighbour", "linear-unstructured")
 
     def __init__(self, *, in_grid: Any, out_grid: Any, method: str = "linear", check: bool = False) -> None:
         from ..grids import row_structure
@@ -134,6 +142,9 @@ class EarthkitRegrid(_Interpolator):
             LOG.warning("Check is not supported by EarthkitRegrid")
         if method == "nearest-neighbour":
             self._nearest(in_grid, out_grid)
+            return
+        if method == "linear-unstructured":
+            self._linear_unstructured(in_grid, out_grid)
             return
         rows = row_structure(self.in_grid)
         out_rows = row_structure(self.out_grid) if method == "grid-box-average" and self.out_grid is not None else None
@@ -178,10 +189,29 @@ class EarthkitRegrid(_Interpolator):
         index = nearest_grid_points(src["latitudes"], src["longitudes"], self.out_griddata["latitudes"], self.out_griddata["longitudes"])
         self.plan = _ordered(GatherPlan(len(src["latitudes"]), len(index), index=index), self.out_griddata)
 
+    def _linear_unstructured(self, in_grid: Any, out_grid: Any) -> None:
+        """Three barycentric weights per target from a triangulation of the source points (``interp.linear_triangulated``)."""
+        import torch
+
+        from ..interp import linear_triangulated
+
+        src = as_griddata(in_grid)
+        self.out_griddata = as_griddata(out_grid) or {}
+        if src is None:
+            raise ValueError("in_grid is required, but not provided")
+        if "latitudes" not in self.out_griddata:
+            raise ValueError("out_grid is required, but not provided")
+        LOG.warning("regrid(method='linear-unstructured'): in-tree barycentric weights on a spherical Delaunay triangulation of the "
+                    "source points (interp.linear_triangulated) stand in for earthkit-regrid's MIR matrix (remote inventory "
+                    "unavailable); the construction is MIR's linear method, parity with MIR is unpinned")
+        matrix = linear_triangulated(src, self.out_griddata, device=torch.cuda.is_available())  # the same arrays either way
+        self.plan = _ordered(GatherPlan.from_matrix(matrix), self.out_griddata)
+
     def plan_for(self, first_field: Any) -> GatherPlan:
         n = int(np.prod(first_field.shape))
         if n != self.plan.n_src:
-            raise ValueError(f"field has {n} points, in_grid {self.in_grid['grid']!r} has {self.plan.n_src}")
+            grid = self.in_grid.get("grid") if isinstance(self.in_grid, dict) else None
+            raise ValueError(f"field has {n} points, in_grid {grid!r} has {self.plan.n_src}")
         return self.plan
 
     def out_latlon(self, first_field: Any):

@@ -32,6 +32,10 @@ __all__ = [
     "bilinear_rows",
     "box_row_table",
     "box_average_rows",
+    "triangulate_sphere",
+    "locate_walk_host",
+    "locate_brute_host",
+    "linear_triangulated",
     "save_matrix_npz",
     "load_matrix_npz",
 ]
@@ -566,6 +570,293 @@ def _box_average_device(src: tuple[np.ndarray, np.ndarray, np.ndarray], tgt: tup
     native_plan.box_average_fill(tables[0], tables[1], indptr, indices, data)
     return dict(matrix_data=data.cpu().numpy(), matrix_indices=indices.cpu().numpy(), matrix_indptr=indptr.cpu().numpy(),
                 matrix_shape=np.array([n_tgt, n_src]))
+
+
+# ---- linear interpolation from any set of source points: triangulate, locate, three barycentric weights ---------------------------
+SLIVER = 2.0**-20  # a triangle with det(v0, v1, v2) < SLIVER * (longest edge)^2 is not part of the domain
+INSIDE = 2.0**-30  # a target is inside a triangle when every d_i >= -INSIDE * D
+FOUND, UNDECIDED, OUTSIDE, MALFORMED = 0, 1, 2, 3  # the status codes of the walk (include/atx_mesh.h)
+WALK_STEPS = 64  # moves a target is given before brute force decides it
+
+
+def _det(p: np.ndarray, b: np.ndarray, c: np.ndarray) -> np.ndarray:
+    """``p.x (b.y c.z - b.z c.y) + p.y (b.z c.x - b.x c.z) + p.z (b.x c.y - b.y c.x)`` over the last axis: every operation rounded on
+    its own, the sum taken left to right — the expression of ``atx_mesh_locate``."""
+    cx = b[..., 1] * c[..., 2] - b[..., 2] * c[..., 1]
+    cy = b[..., 2] * c[..., 0] - b[..., 0] * c[..., 2]
+    cz = b[..., 0] * c[..., 1] - b[..., 1] * c[..., 0]
+    return (p[..., 0] * cx + p[..., 1] * cy) + p[..., 2] * cz
+
+
+def triangulate_sphere(src_xyz: np.ndarray, max_edge: float | None = None) -> dict[str, np.ndarray]:
+    """The spherical Delaunay triangulation of unit vectors ``src_xyz`` (float64 ``[n, 3]``): the convex hull of points on the unit
+    sphere, from ``scipy.spatial.ConvexHull`` (Qhull).  Returns
+
+    - ``tri`` int32 ``[T, 3]``, every triangle oriented so that ``det(v0, v1, v2) > 0`` (where Qhull's is not, vertices 1 and 2
+      are swapped, and the neighbour columns 1 and 2 with them);
+    - ``nbr`` int32 ``[T, 3]``: ``nbr[t, e]`` is the triangle across the edge opposite vertex ``e``;
+    - ``flag`` uint8 ``[T]``: with ``L`` the longest chord edge and ``D = det(v0, v1, v2)``, set where ``D < 2^-20 L^2`` (slivers:
+      collinear boundary points of a lat-lon box) or where ``max_edge`` is given and ``L > max_edge`` (the faces that close the
+      hull around a limited-area domain);
+    - ``hull_vertices`` int64, sorted: the points that are a vertex of some triangle.  The others (duplicates, such as the surplus
+      pole points of a lat-lon grid) carry no weight;
+    - ``vertex_tri`` int32 ``[n]``: the lowest-numbered unflagged triangle at the vertex, else the lowest flagged one, -1 for a
+      point that is no hull vertex.
+
+    Non-finite coordinates, fewer than four points and a degenerate hull raise ``ValueError``.
+    """
+    from scipy.spatial import ConvexHull, QhullError
+
+    xyz = np.ascontiguousarray(src_xyz, dtype=np.float64)
+    if xyz.ndim != 2 or xyz.shape[1] != 3:
+        raise ValueError(f"source points must be unit vectors [n, 3], got shape {xyz.shape}")
+    if not np.isfinite(xyz).all():
+        raise ValueError("source coordinates must be finite")
+    n = len(xyz)
+    if n < 4:
+        raise ValueError(f"a triangulation needs at least four source points, got {n}")
+    if n >= 2**31:
+        raise NotImplementedError("grids with 2^31 or more points are not supported")
+    try:
+        hull = ConvexHull(xyz)
+    except QhullError as e:
+        raise ValueError(f"the source points have no triangulation (degenerate hull): {str(e).strip().splitlines()[0]}") from None
+    tri = hull.simplices.astype(np.int32)
+    nbr = hull.neighbors.astype(np.int32)
+    if len(tri) < 4 or (nbr < 0).any():
+        raise ValueError("the source points have no triangulation (degenerate hull)")
+    swap = ~(_det(xyz[tri[:, 0]], xyz[tri[:, 1]], xyz[tri[:, 2]]) > 0.0)
+    tri[swap] = tri[swap][:, [0, 2, 1]]
+    nbr[swap] = nbr[swap][:, [0, 2, 1]]
+    v0, v1, v2 = xyz[tri[:, 0]], xyz[tri[:, 1]], xyz[tri[:, 2]]
+    det = _det(v0, v1, v2)
+    longest2 = np.max([np.sum((v1 - v2) ** 2, axis=1), np.sum((v2 - v0) ** 2, axis=1), np.sum((v0 - v1) ** 2, axis=1)], axis=0)
+    flag = det < SLIVER * longest2
+    if max_edge is not None:
+        flag |= np.sqrt(longest2) > float(max_edge)
+    number = np.repeat(np.arange(len(tri), dtype=np.int64), 3)
+    corner = tri.reshape(-1).astype(np.int64)
+    lowest = np.full((2, n), len(tri), dtype=np.int64)  # per vertex: the lowest unflagged, the lowest flagged triangle
+    flagged = np.repeat(flag, 3)
+    np.minimum.at(lowest[0], corner[~flagged], number[~flagged])
+    np.minimum.at(lowest[1], corner[flagged], number[flagged])
+    vertex_tri = np.where(lowest[0] < len(tri), lowest[0], np.where(lowest[1] < len(tri), lowest[1], -1)).astype(np.int32)
+    return dict(tri=np.ascontiguousarray(tri), nbr=np.ascontiguousarray(nbr), flag=flag.astype(np.uint8),
+                hull_vertices=np.flatnonzero(vertex_tri >= 0), vertex_tri=vertex_tri)
+
+
+def _weights(d: np.ndarray) -> np.ndarray:
+    """``w_i = d_i / ((d0 + d1) + d2)`` with negative ``d_i`` clamped to 0, for ``d`` float64 ``[n, 3]``: the barycentric coordinates
+    of the point where the ray through the target meets the triangle's plane."""
+    d = np.where(d < 0.0, 0.0, d)
+    return d / ((d[:, 0] + d[:, 1]) + d[:, 2])[:, None]
+
+
+def locate_walk_host(src_xyz, tri, nbr, flag, tgt_xyz, seed, max_steps: int = 64):
+    """Walk every target from its seed triangle to the triangle under it, vectorised over the targets still walking; the statement
+    that ``atx_mesh_locate`` repeats operation for operation.  Returns ``(tri_out int32 [n], w float64 [n, 3], status int32 [n],
+    steps int32 [n])``.  At triangle ``t = (a, b, c)`` and target ``p``:
+
+    1. ``flag[t]`` set: status 2 (outside), stop.
+    2. ``d0 = det(p, b, c)``, ``d1 = det(p, c, a)``, ``d2 = det(p, a, b)``, ``D = det(a, b, c)`` (``_det``).
+    3. every ``d_i >= -2^-30 D``: status 0 (found), ``w`` from ``_weights``.
+    4. ``max_steps`` moves made already: status 1 (undecided), stop.
+    5. move to ``nbr[t, e]``, ``e`` the first of the smallest ``d_i`` (``np.argmin``'s choice).
+
+    ``tri_out`` is the triangle at which the target stopped.  A seed or neighbour outside ``[0, T)`` or a vertex outside
+    ``[0, n_src)`` ends the target with status 3, ``tri_out`` -1 and NaN weights; ``w`` is 0 with status 1 and 2.
+    """
+    xyz = np.asarray(src_xyz, dtype=np.float64)
+    tgt = np.asarray(tgt_xyz, dtype=np.float64)
+    tri, nbr, flag = np.asarray(tri), np.asarray(nbr), np.asarray(flag)
+    n, n_tri, n_src = len(tgt), len(tri), len(xyz)
+    current = np.asarray(seed).astype(np.int64).copy()
+    w = np.zeros((n, 3), dtype=np.float64)
+    status = np.full(n, UNDECIDED, dtype=np.int32)
+    steps = np.zeros(n, dtype=np.int32)
+    active = np.arange(n, dtype=np.int64)
+
+    def stop(rows, code):
+        status[rows] = code
+        if code == MALFORMED:
+            current[rows], w[rows] = -1, np.nan
+
+    while active.size:
+        t = current[active]
+        ok = (t >= 0) & (t < n_tri)
+        stop(active[~ok], MALFORMED)
+        active, t = active[ok], t[ok]
+        inside = flag[t] == 0
+        stop(active[~inside], OUTSIDE)
+        active, t = active[inside], t[inside]
+        corners = tri[t].astype(np.int64)
+        ok = ((corners >= 0) & (corners < n_src)).all(axis=1)
+        stop(active[~ok], MALFORMED)
+        active, t, corners = active[ok], t[ok], corners[ok]
+        p, a, b, c = tgt[active], xyz[corners[:, 0]], xyz[corners[:, 1]], xyz[corners[:, 2]]
+        d = np.stack([_det(p, b, c), _det(p, c, a), _det(p, a, b)], axis=1)
+        tol = -INSIDE * _det(a, b, c)
+        found = (d[:, 0] >= tol) & (d[:, 1] >= tol) & (d[:, 2] >= tol)
+        w[active[found]] = _weights(d[found])
+        stop(active[found], FOUND)
+        active, t, d = active[~found], t[~found], d[~found]
+        spent = steps[active] >= max_steps
+        stop(active[spent], UNDECIDED)
+        active, t, d = active[~spent], t[~spent], d[~spent]
+        edge = np.where(d[:, 1] < d[:, 0], 1, 0)  # strict comparisons: the first of equal minima stays
+        edge = np.where(d[:, 2] < np.where(edge == 1, d[:, 1], d[:, 0]), 2, edge)
+        current[active] = nbr[t, edge]
+        steps[active] += 1
+    return current.astype(np.int32), w, status, steps
+
+
+def locate_brute_host(src_xyz, tri, flag, tgt_xyz, chunk: int = 256):
+    """The triangle under every target without a walk: of the unflagged triangles the one with the largest ``min_i d_i / D``, the
+    lowest-numbered on ties; the target is inside (status 0) iff that value is ``>= -2^-30``, with the clamp and the weights of
+    ``locate_walk_host``, and outside (status 2, ``tri_out`` -1, weights 0) otherwise.  Returns ``(tri_out int32 [n], w float64
+    [n, 3], status int32 [n])``.  Targets are taken ``chunk`` at a time, fewer on a large mesh: O(chunk * T) memory, 2^22 values at most."""
+    xyz = np.asarray(src_xyz, dtype=np.float64)
+    tgt = np.asarray(tgt_xyz, dtype=np.float64).reshape(-1, 3)
+    tri = np.asarray(tri)
+    n = len(tgt)
+    tri_out = np.full(n, -1, dtype=np.int32)
+    w = np.zeros((n, 3), dtype=np.float64)
+    status = np.full(n, OUTSIDE, dtype=np.int32)
+    keep = np.flatnonzero(np.asarray(flag) == 0)
+    if keep.size == 0 or n == 0:
+        return tri_out, w, status
+    a, b, c = (xyz[tri[keep, i]] for i in range(3))
+    det_abc = _det(a, b, c)
+    # det(p, b, c) = (p.x X.x + p.y X.y) + p.z X.z with X = b x c rounded as in _det: the same bits, X computed once per triangle
+    crosses = [np.stack([u[:, 1] * v[:, 2] - u[:, 2] * v[:, 1], u[:, 2] * v[:, 0] - u[:, 0] * v[:, 2], u[:, 0] * v[:, 1] - u[:, 1] * v[:, 0]])
+               for u, v in ((b, c), (c, a), (a, b))]
+    chunk = max(1, min(int(chunk), (1 << 22) // len(keep)))  # at most 2^22 determinants (32 MiB) per temporary
+    for lo in range(0, n, chunk):
+        p = tgt[lo:lo + chunk]
+        least = None
+        for x in crosses:
+            d = (p[:, 0:1] * x[0] + p[:, 1:2] * x[1]) + p[:, 2:3] * x[2]
+            least = d if least is None else np.minimum(least, d)
+        least /= det_abc
+        best = np.argmax(least, axis=1)  # the first of equal maxima: the lowest-numbered triangle
+        rows = np.flatnonzero(least[np.arange(len(p)), best] >= -INSIDE)
+        t = keep[best[rows]]
+        q, ta, tb, tc = p[rows], xyz[tri[t, 0]], xyz[tri[t, 1]], xyz[tri[t, 2]]
+        tri_out[lo + rows] = t
+        w[lo + rows] = _weights(np.stack([_det(q, tb, tc), _det(q, tc, ta), _det(q, ta, tb)], axis=1))
+        status[lo + rows] = FOUND
+    return tri_out, w, status
+
+
+def _nearest_by_index(src_xyz: np.ndarray, tgt_xyz: np.ndarray) -> np.ndarray:
+    """The nearest row of ``src_xyz`` for every target, the lowest-numbered of exactly equidistant ones — what ``device_knn(k=1,
+    ties="index")`` returns.  cKDTree finds the candidates; squared distances are summed in its (and the kernel's) order."""
+    from scipy.spatial import cKDTree
+
+    tree = cKDTree(src_xyz)
+    k = min(2, len(src_xyz))
+    dist, idx = tree.query(tgt_xyz, k=k)
+    dist, idx = dist.reshape(len(tgt_xyz), k), idx.reshape(len(tgt_xyz), k).astype(np.int64)
+    nearest = idx[:, 0].copy()
+    if k == 2:
+        for row in np.flatnonzero(dist[:, 1] <= dist[:, 0] * (1.0 + 2.0**-40) + 2.0**-500):  # a possible tie: look at every candidate
+            near = np.sort(np.asarray(tree.query_ball_point(tgt_xyz[row], dist[row, 1] * (1.0 + 2.0**-40) + 2.0**-500), dtype=np.int64))
+            diff = src_xyz[near] - tgt_xyz[row]
+            d2 = np.zeros(len(near))
+            for axis in range(3):
+                d2 = d2 + diff[:, axis] * diff[:, axis]
+            nearest[row] = near[np.argmin(d2)]  # the first of equal minima: the lowest index
+    return nearest
+
+
+def _grid_xyz(grid: dict, what: str) -> np.ndarray:
+    lat, lon = np.asarray(grid["latitudes"], dtype=np.float64).reshape(-1), np.asarray(grid["longitudes"], dtype=np.float64).reshape(-1)
+    if lat.shape != lon.shape:
+        raise ValueError(f"{what}: latitudes and longitudes differ in length ({lat.shape[0]} and {lon.shape[0]})")
+    if not (np.isfinite(lat).all() and np.isfinite(lon).all()):
+        raise ValueError(f"{what}: coordinates must be finite")
+    return np.ascontiguousarray(unit_sphere_xyz(lat, lon))  # row-major [n, 3], as the kernels read it
+
+
+def linear_triangulated(in_grid: dict, out_grid: dict, *, max_edge_km: float | None = None, outside: str = "raise",
+                        device: bool = False, max_steps: int = WALK_STEPS) -> dict[str, np.ndarray]:
+    """Linear interpolation weights from ANY set of source points (a limited-area grid, ICON, scattered points, a dict of
+    coordinates) to the target points: the source points are triangulated on the sphere (``triangulate_sphere``) and every target
+    gets the three barycentric weights of the triangle under it (``locate_walk_host``) — the construction of MIR's ``linear``
+    method.  Returns the CSR triplet of the MIR npz format with three entries per row, as ``ell_to_csr`` does.
+
+    ``max_edge_km`` takes triangles with a longer edge out of the domain: without it the long faces that close the hull around a
+    limited-area grid count as part of it, and targets well outside the grid get weights from them.  Targets outside the domain raise ``ValueError`` with their count
+    (``outside="raise"``) or get the nearest source point with weight 1 and two entries of weight 0 (``outside="nearest"``).
+
+    Each walk starts at ``vertex_tri`` of the nearest hull vertex (the lowest-numbered of equidistant ones) and is given
+    ``max_steps`` moves; targets still undecided after ``WALK_STEPS`` (64) moves are answered by ``locate_brute_host``.  A smaller
+    ``max_steps`` only bounds the first pass: its undecided rows resume the host walk where they stopped, up to 64 moves in all, so
+    the matrix does not depend on ``max_steps <= 64`` (the walk is a function of the triangle it stands on; brute force may name the
+    triangle on the other side of an edge that the target lies on).  ``device=True`` uploads the mesh once and runs the neighbour
+    search (``atx_knn_*``, as ``device_knn(ties="index")``) and the first pass (``atx_mesh_locate``, ``include/atx_mesh.h``) on the
+    GPU; only the undecided rows come back to the host statement.  The arrays are the same bit for bit either way.  The hull itself
+    is always built on the host, in Qhull.
+    """
+    if outside not in ("raise", "nearest"):
+        raise ValueError(f"outside must be 'raise' or 'nearest', got {outside!r}")
+    src_xyz, tgt_xyz = _grid_xyz(in_grid, "in_grid"), _grid_xyz(out_grid, "out_grid")
+    max_edge = None
+    if max_edge_km is not None:
+        from .spatial import R_earth_km
+
+        if not max_edge_km > 0:
+            raise ValueError(f"max_edge_km must be positive, got {max_edge_km!r}")
+        max_edge = 2.0 * np.sin(min(float(max_edge_km) / R_earth_km, np.pi) / 2.0)  # the chord of that arc on the unit sphere
+    mesh = triangulate_sphere(src_xyz, max_edge)
+    tri, hull_vertices = mesh["tri"], mesh["hull_vertices"]
+    n_src, n_tgt = len(src_xyz), len(tgt_xyz)
+    if device:
+        tri_out, w, status = _locate_device(src_xyz, mesh, tgt_xyz, max_steps)
+    else:
+        seed = mesh["vertex_tri"][hull_vertices[_nearest_by_index(src_xyz[hull_vertices], tgt_xyz)]] if n_tgt else np.zeros(0, dtype=np.int32)
+        tri_out, w, status, _ = locate_walk_host(src_xyz, tri, mesh["nbr"], mesh["flag"], tgt_xyz, seed, max_steps)
+    undecided = np.flatnonzero(status == UNDECIDED)
+    if undecided.size and max_steps < WALK_STEPS:  # a bounded first pass: the walk goes on from where it stopped
+        tri_out[undecided], w[undecided], status[undecided], _ = locate_walk_host(
+            src_xyz, tri, mesh["nbr"], mesh["flag"], tgt_xyz[undecided], tri_out[undecided], WALK_STEPS - max_steps)
+        undecided = np.flatnonzero(status == UNDECIDED)
+    if undecided.size:
+        tri_out[undecided], w[undecided], status[undecided] = locate_brute_host(src_xyz, tri, mesh["flag"], tgt_xyz[undecided])
+    if (status == MALFORMED).any():
+        raise RuntimeError("the walk left the triangulation: triangulate_sphere returned an inconsistent mesh")
+    indices = tri[np.where(status == FOUND, tri_out, 0)].astype(np.int32)
+    lost = np.flatnonzero(status != FOUND)
+    if lost.size:
+        if outside == "raise":
+            raise ValueError(f"{lost.size} of {n_tgt} target points lie outside the triangulated source domain; give max_edge_km a "
+                             "larger value (or none), or pass outside='nearest' to give them the nearest source point")
+        nearest = _nearest_by_index(src_xyz, tgt_xyz[lost])
+        indices[lost] = nearest[:, None]
+        w[lost] = [1.0, 0.0, 0.0]
+    return ell_to_csr(indices, w, n_src)
+
+
+def _locate_device(src_xyz: np.ndarray, mesh: dict[str, np.ndarray], tgt_xyz: np.ndarray, max_steps: int):
+    """Seeds and walk of ``linear_triangulated`` on the current device: ``(tri_out, w, status)`` as numpy arrays."""
+    import torch
+
+    from . import native, native_mesh
+
+    if not torch.cuda.is_available():
+        raise RuntimeError("linear_triangulated(device=True) needs a GPU; device=False evaluates the same statement on the host")
+    n_tgt = len(tgt_xyz)
+    if n_tgt == 0:
+        return np.zeros(0, dtype=np.int32), np.zeros((0, 3)), np.zeros(0, dtype=np.int32)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    hull_vertices = mesh["hull_vertices"]
+    src_d, tgt_d = torch.from_numpy(src_xyz).to(dev), torch.from_numpy(np.ascontiguousarray(tgt_xyz)).to(dev)
+    hull_d = torch.from_numpy(hull_vertices).to(dev)
+    nearest, _ = native.KnnIndex(src_d[hull_d].contiguous()).query(tgt_d, 1)  # equidistant candidates by index (device_knn, ties="index")
+    seed = torch.from_numpy(mesh["vertex_tri"]).to(dev)[hull_d[nearest[:, 0].long()]].contiguous()
+    on_device = native_mesh.Mesh(src_d, *(torch.from_numpy(mesh[name]).to(dev) for name in ("tri", "nbr", "flag")))
+    tri_out, w, status, _ = native_mesh.locate(on_device, tgt_d, seed, max_steps)
+    return tri_out.cpu().numpy(), w.cpu().numpy(), status.cpu().numpy()
 
 
 def save_matrix_npz(path: str, matrix: dict[str, np.ndarray], in_grid: dict, out_grid: dict) -> None:
