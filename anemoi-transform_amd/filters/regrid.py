@@ -15,7 +15,7 @@ from typing import Any
 
 import numpy as np
 
-from ..core import Filter, filter_registry
+from ..core import Filter, filter_registry, say_once
 from ..fields import Field, FieldList, group_into_stacks, new_field_from_stack
 from ..gather import GatherPlan, target_order_for
 
@@ -67,8 +67,11 @@ class _Interpolator:
     def out_latlon(self, first_field: Any) -> tuple[np.ndarray, np.ndarray]:
         raise NotImplementedError
 
-    def regrid_fieldlist(self, data: Any, *, shard: tuple[int, int] | None = None) -> FieldList:
+    def regrid_fieldlist(self, data: Any, *, shard: tuple[int, int] | None = None, missing: str | None = None,
+                         min_valid: float = 0.0) -> FieldList:
+        """``missing`` / ``min_valid``: the missing-value policy of ``GatherPlan.apply`` (``None``: the plain product)."""
         fields = list(data)
+        policy = {} if missing is None else dict(missing=missing, min_valid=min_valid)
         out: list[Any] = [None] * len(fields)
         # stacks that share a plan (several variables / time steps on one grid pair) go through ONE batched launch
         batches: dict[int, tuple[GatherPlan, np.ndarray, np.ndarray, Any, list[Any]]] = {}
@@ -82,7 +85,7 @@ class _Interpolator:
                 plan, lat, lon = self._sharded(plan, shard), lat[lo:hi], lon[lo:hi]
             batches.setdefault(id(plan), (plan, lat, lon, window, []))[4].append(group)
         for plan, lat, lon, window, groups in batches.values():
-            for group, regridded in zip(groups, plan.apply_many([g.stack for g in groups])):
+            for group, regridded in zip(groups, plan.apply_many([g.stack for g in groups], **policy)):
                 for level, (pos, f) in enumerate(zip(group.positions, group.fields)):
                     out[pos] = new_field_from_stack(regridded, level, template=f, latitudes=lat, longitudes=lon, target_range=window)
         return FieldList(out)
@@ -337,13 +340,36 @@ class RegridFilter(Filter):
     ``shard=(rank, world)`` (extension) makes this process compute only its
     contiguous slice of the target points: rows of the operator are independent, so
     the per-rank outputs need no exchange.
+
+    ``missing=`` (extension) says what a NaN among a target's sources does, in MIR's spellings: ``None`` and
+    ``"missing-if-any-missing"`` — the target is NaN (the plain product, the reference's behaviour);
+    ``"missing-if-all-missing"`` — NaN sources are dropped and the remaining weights renormalise, the target is NaN only when
+    every source is; ``"missing-if-heaviest-missing"`` — also when the row's (first) heaviest entry is NaN.  ``min_valid`` in
+    [0, 1]: under the two renormalising policies the target is NaN as well when the valid weights sum to less than that share of
+    the row's.  Both work with every interpolator and with ``shard=``; ``nearest`` / ``mask=`` copy one source per target and are
+    the same under every policy.  The statement is in-tree (``include/atx_missing.h``); the policy names are
+    MIR's, parity with MIR is unpinned, and the filter says so once.  Such a regrid runs alone: the per-point filters after it in
+    a pipeline fuse among themselves.
     """
 
-    def __init__(self, *, in_grid=None, out_grid=None, method=None, matrix=None, mask=None, check=False, shard=None) -> None:
+    MISSING = {None: None, "missing-if-any-missing": None, "missing-if-all-missing": "all", "missing-if-heaviest-missing": "heaviest"}
+
+    def __init__(self, *, in_grid=None, out_grid=None, method=None, matrix=None, mask=None, check=False, shard=None, missing=None,
+                 min_valid=0.0) -> None:
         self.in_grid = in_grid
         self.out_grid = out_grid
         self.method = method
         self.shard = tuple(shard) if shard is not None else None
+        if not (missing is None or isinstance(missing, str)) or missing not in self.MISSING:
+            raise ValueError(f"regrid(missing={missing!r}): one of {', '.join(repr(s) for s in self.MISSING if s)} or None")
+        if not isinstance(min_valid, (int, float, np.floating)) or not 0.0 <= float(min_valid) <= 1.0:  # (NaN fails both comparisons)
+            raise ValueError(f"regrid(min_valid={min_valid!r}): a number in [0, 1]")
+        self.missing = self.MISSING[missing]
+        self.min_valid = float(min_valid)
+        if self.missing is not None:
+            say_once(LOG, "regrid-missing-parity", "regrid(missing=%r): NaN sources are dropped and the remaining weights renormalised by "
+                     "an in-tree statement (include/atx_missing.h); the policy names are MIR's, parity with MIR is "
+                     "unpinned", missing)
         self.interpolator = make_interpolator(
             in_grid=in_grid, out_grid=out_grid, method=method, matrix=matrix, mask=mask, check=check
         )
@@ -352,4 +378,6 @@ class RegridFilter(Filter):
         return self._interpolate(data)
 
     def _interpolate(self, data: Any) -> FieldList:
-        return self.interpolator.regrid_fieldlist(data, shard=self.shard)
+        if self.missing is None:
+            return self.interpolator.regrid_fieldlist(data, shard=self.shard)
+        return self.interpolator.regrid_fieldlist(data, shard=self.shard, missing=self.missing, min_valid=self.min_valid)

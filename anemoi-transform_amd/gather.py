@@ -22,7 +22,7 @@ from typing import Any
 import numpy as np
 import torch
 
-from . import native
+from . import native, native_missing
 from .stack import COLUMNS, Stack
 
 
@@ -296,14 +296,61 @@ class GatherPlan:
             raise ValueError(f"out= must be a {src.layout_name} stack of {self.n_tgt} points x {src.n_lev} levels, {src.dtype}, on {src.device}; "
                              f"got {out.n_pts} points x {out.n_lev} levels, {out.dtype}, layout {out.layout_name}, on {out.device}")
 
+    def _missing_route(self, missing: str | None, min_valid: float, prog=None, tgt_mask=None) -> bool:
+        """Validate ``missing=`` / ``min_valid=``; does this plan run them on the renormalising kernels?  (An unweighted k = 1 plan
+        does not: a copy has nothing to renormalise.)"""
+        if missing is None:
+            return False
+        if missing not in native_missing.MISSING_POLICIES:
+            raise ValueError(f"missing={missing!r}: one of None, {', '.join(repr(p) for p in native_missing.MISSING_POLICIES)}")
+        if not 0.0 <= float(min_valid) <= 1.0:  # (NaN fails both comparisons)
+            raise ValueError(f"min_valid={min_valid!r} is outside [0, 1]")
+        if prog is not None or tgt_mask is not None:
+            raise ValueError("a missing-value policy takes no fused level program or target mask: apply them to the result")
+        return not (self.kind == "ell" and self.weights is None)
+
+    def _apply_missing(self, src: Stack, missing: str, min_valid: float, out: Stack | None) -> Stack:
+        if src.layout != COLUMNS:  # the kernels read column stacks: through them and back, as long rows already go
+            res = self._apply_missing(src.to_layout(COLUMNS), missing, min_valid, None).to_layout(src.layout)
+            if out is None:
+                return res
+            out.data.copy_(res.data)
+            return out
+        if out is None:
+            out = src.new_like(n_pts=self.n_tgt, zero=False)
+        if self.n_tgt == 0:
+            return out
+        # natural-order tables: the visiting order is the plain kernels' matter, and results never depend on it
+        if self.kind == "ell":
+            idx, w, _ = self._tensors(src.device, src.dtype, ordered=False)
+            native_missing.regrid_ell_missing(src.data, out.data, idx, w, n_src=self.n_src, n_tgt=self.n_tgt, k=self.k, n_lev=src.n_lev,
+                                      src_pitch=src.pitch, out_pitch=out.pitch, layout=src.layout, policy=missing, min_valid=min_valid,
+                                      padded=self.padded)
+        else:
+            indptr, indices, data, _ = self._tensors(src.device, src.dtype, ordered=False)
+            native_missing.regrid_csr_missing(src.data, out.data, indptr, indices, data, n_src=self.n_src, n_tgt=self.n_tgt, nnz=len(self.indices),
+                                      n_lev=src.n_lev, src_pitch=src.pitch, out_pitch=out.pitch, layout=src.layout, policy=missing,
+                                      min_valid=min_valid)
+        return out
+
     def apply(self, src: Stack, *, prog: torch.Tensor | None = None, n_stage: int = 0,
-              tgt_mask: torch.Tensor | None = None, out: Stack | None = None) -> Stack:
+              tgt_mask: torch.Tensor | None = None, out: Stack | None = None, missing: str | None = None, min_valid: float = 0.0) -> Stack:
         """Run the gather over every level of ``src``; returns a new stack on the target points — or ``out``, a stack of the
-        right shape the caller keeps across calls (no allocation inside a repeated, launch-bound call)."""
+        right shape the caller keeps across calls (no allocation inside a repeated, launch-bound call).
+
+        ``missing``: ``None`` — a NaN source makes its target NaN (scipy's product, today's kernels); ``"all"`` — NaN sources are dropped
+        and the remaining weights renormalise, the target is NaN only when every source is; ``"heaviest"`` — also when the (first)
+        heaviest entry of the row is NaN.  ``min_valid`` in [0, 1]: under either policy the target is NaN as well when the valid
+        weights sum to less than that share of the row's.  ``include/atx_missing.h`` holds the statement; without a
+        NaN among the sources the result is the plain route's, bit for bit.  A policy takes no ``prog`` / ``tgt_mask`` (``ValueError``),
+        uses the natural-order tables, and sends a field-major stack through a column stack and back.  An unweighted k = 1 plan
+        (``nearest``, ``mask=``, ``remove_nans``) takes the plain route whatever the policy: a copy has nothing to renormalise."""
         # R: regrid.py:377-378 — the field must live on the plan's source grid
         assert src.n_pts == self.n_src, (src.n_pts, self.n_src)
         if out is not None:
             self._check_out(src, out)
+        if self._missing_route(missing, min_valid, prog, tgt_mask):
+            return self._apply_missing(src, missing, float(min_valid), out)
         if src.layout != COLUMNS and self.n_tgt > 0 and self._long_rows():
             # field-major stacks and rows beyond 8 entries: through column stacks and back — the field-major gather re-fetches a source
             # point once per row that uses it (O1280 -> 0.25 deg, k = 16, 137 fields: 11.5 ms direct, 2.5 ms with both conversions)
@@ -333,17 +380,19 @@ class GatherPlan:
         return out
 
     def bind(self, src: Stack, out: Stack | None = None, *, prog: torch.Tensor | None = None, n_stage: int = 0,
-             tgt_mask: torch.Tensor | None = None):
+             tgt_mask: torch.Tensor | None = None, missing: str | None = None, min_valid: float = 0.0):
         """``(launch, out)``: ``launch()`` repeats ``apply(src, out=out)`` with every argument converted once
         (``native.BoundCall``) — for a caller that regrids the same buffers again and again (one surface field per time step:
         BASELINE configs[1] is 3 us of kernel under ~10 us of launch, so what Python adds per call is what there is to save).
         The contents of ``src`` may change between calls, its storage may not.  Fixed-k plans in natural target order; anything
-        else gets a closure over ``apply``."""
+        else gets a closure over ``apply`` — a plan with a ``missing`` policy (see ``apply``) among them."""
         assert src.n_pts == self.n_src, (src.n_pts, self.n_src)
         if out is None:
             out = src.new_like(n_pts=self.n_tgt, zero=False)
         else:
             self._check_out(src, out)
+        if self._missing_route(missing, min_valid, prog, tgt_mask):  # the closure form: apply() with the policy
+            return (lambda: self.apply(src, out=out, missing=missing, min_valid=min_valid) and None), out
         plain = self.kind == "ell" and self.n_tgt > 0 and not (src.layout != COLUMNS and self._long_rows())
         if plain:
             idx, w, rows = self._tensors(src.device, src.dtype, ordered=src.layout == COLUMNS)
@@ -354,11 +403,15 @@ class GatherPlan:
                 return call, out
         return (lambda: self.apply(src, prog=prog, n_stage=n_stage, tgt_mask=tgt_mask, out=out) and None), out
 
-    def apply_many(self, stacks: list[Stack]) -> list[Stack]:
+    def apply_many(self, stacks: list[Stack], *, missing: str | None = None, min_valid: float = 0.0) -> list[Stack]:
         """The gather over several source stacks of identical shape (variables / time steps on one grid) — fixed-k
-        plans on column stacks run them in ONE launch (``atx_regrid_ell_batch``, grid.y = stack); anything else falls back to one launch per stack."""
+        plans on column stacks run them in ONE launch (``atx_regrid_ell_batch``, grid.y = stack); anything else falls back to one launch per stack.
+        With a ``missing`` policy (see ``apply``): one launch per stack."""
         if not stacks:
+            self._missing_route(missing, min_valid)
             return []
+        if self._missing_route(missing, min_valid):
+            return [self.apply(s, missing=missing, min_valid=min_valid) for s in stacks]
         first = stacks[0]
         same = all((s.n_pts, s.n_lev, s.dtype, s.layout, s.pitch) == (first.n_pts, first.n_lev, first.dtype, first.layout, first.pitch)
                    for s in stacks)
