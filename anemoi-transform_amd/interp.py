@@ -94,7 +94,8 @@ def _library_version() -> int:
     try:
         from . import native
 
-        return int(native._lib.atx_version()) if native._lib is not None else 0
+        handle = native.LIBRARY.handle
+        return int(handle.atx_version()) if handle is not None else 0
     except Exception:  # noqa: BLE001 - the version is a label in the file, never a reason to fail a table build
         return 0
 

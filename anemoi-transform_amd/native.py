@@ -19,8 +19,7 @@ from typing import Any
 import numpy as np
 import torch
 
-LIB_NAME = "libatx.so"
-LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
+from ._binding import Library
 
 # atx_dtype / atx_layout / atx_cmp / atx_op / atx_red (include/atx.h)
 F32, F64 = 0, 1
@@ -163,72 +162,27 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     "atx_gather_shards": (c_int, [c_void_p, c_void_p, POINTER(c_int64), c_void_p]),
 }
 
-_lib: ctypes.CDLL | None = None
-
-
 class AtxError(RuntimeError):
     """HIP runtime failure inside libatx."""
 
 
-def lib_path() -> str:
-    """``lib/libatx.so`` next to this file; ``ATX_LIBRARY`` overrides it (A/B builds of the kernels)."""
-    return os.environ.get("ATX_LIBRARY") or os.path.join(LIB_DIR, LIB_NAME)
+def _failure(fn: str, message: str, code: int) -> AtxError:
+    return AtxError(f"{fn}: {message}" if code == ECOMM else f"{fn}: {message} (code {code})")
 
 
-def open_library(path: str, older_build: bool = False) -> ctypes.CDLL:
-    """A build of libatx.so with every prototype declared; raises if a symbol of the header is missing — unless ``older_build`` says the
-    library may predate the header (an A/B timing against an earlier commit): its missing entry points are then left undeclared."""
-    handle = ctypes.CDLL(path)
-    for name, (restype, argtypes) in SIGNATURES.items():
-        if older_build and not hasattr(handle, name):
-            continue
-        fn = getattr(handle, name)  # AttributeError if the symbol is not exported
-        fn.restype = restype
-        fn.argtypes = argtypes
-    return handle
-
-
-def load() -> ctypes.CDLL:
-    """Load libatx.so (once) and declare every prototype.  Raises if it is absent."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    path = lib_path()
-    if not os.path.exists(path):
-        raise RuntimeError(
-            f"{path} not found: the HIP extension is not built. Run `python -c \"import __graft_entry__ as g; "
-            "g.build()\"` (hipcc --offload-arch=gfx950) — this package has no CPU fallback."
-        )
-    _lib = open_library(path)
-    return _lib
-
-
-def use_library(handle: ctypes.CDLL | None) -> ctypes.CDLL | None:
-    """Route every wrapper of this module through ``handle`` (from ``open_library``) and return what was in use before; ``None``
-    goes back to ``load()``'s own.  For side-by-side timing of two builds in one process (tools/kernel_bench.py --lib)."""
-    global _lib
-    before, _lib = _lib, handle
-    return before
-
-
-def _raise(code: int, fn: str) -> None:
-    handle = load()
-    msg = handle.atx_last_error().decode() or handle.atx_strerror(code).decode()
-    if code == EINVAL:
-        raise ValueError(msg)
-    if code == ESHAPE:
-        raise AssertionError(msg)
-    if code == ENOTIMPL:
-        raise NotImplementedError(msg)
-    if code == ECOMM:
-        raise AtxError(f"{fn}: {msg}")
-    raise AtxError(f"{fn}: {msg} (code {code})")
+LIBRARY = Library("libatx.so", "ATX_LIBRARY", SIGNATURES, "atx_last_error", strerror="atx_strerror", unmapped=_failure,
+                  errors={EINVAL: ValueError, ESHAPE: AssertionError, ENOTIMPL: NotImplementedError})
+lib_path = LIBRARY.path  # ``lib/libatx.so`` next to this file; ``ATX_LIBRARY`` overrides it (A/B builds of the kernels)
+load = LIBRARY.load
+# a build of libatx.so opened apart from load()'s and swapped in: side-by-side timing of two builds in one process (tools/kernel_bench.py --lib)
+open_library = LIBRARY.open
+use_library = LIBRARY.use
 
 
 def _call(fn: str, *args: Any) -> None:
     code = getattr(load(), fn)(*args)
     if code != OK:
-        _raise(code, fn)
+        LIBRARY.check(fn, code)
 
 
 def _ptr(t: torch.Tensor | None) -> int | None:
@@ -319,7 +273,7 @@ class BoundCall:
     def __call__(self) -> None:
         code = self._fn(*self._args)
         if code != OK:
-            _raise(code, self._name)
+            LIBRARY.check(self._name, code)
 
 
 def bind_regrid_ell(src, out, idx, w, *, n_src, n_tgt, k, n_lev, src_pitch, out_pitch, layout, prog=None, n_stage=0, tgt_mask=None,
@@ -948,7 +902,7 @@ class Comm:
     def rccl_version() -> int:
         v = load().atx_comm_version()
         if v < 0:
-            _raise(v, "atx_comm_version")
+            LIBRARY.check("atx_comm_version", v)
         return v
 
     def bcast(self, t: torch.Tensor, root: int) -> None:

@@ -6,16 +6,13 @@ There is no CPU fallback: if ``lib/libatx_mesh.so`` is missing, or a tensor hand
 
 from __future__ import annotations
 
-import ctypes
-import os
 from ctypes import c_char_p, c_int, c_int32, c_int64, c_void_p
 from typing import Any
 
 import torch
 
-LIB_NAME = "libatx_mesh.so"
-LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
-OK, EINVAL = 0, -1
+from ._binding import EINVAL, OK, Library  # noqa: F401 - the status codes are part of this module's names
+
 FOUND, UNDECIDED, OUTSIDE, MALFORMED = 0, 1, 2, 3  # the status codes of atx_mesh_locate
 MAX_STEPS = 1 << 20  # ATX_MESH_MAX_STEPS
 
@@ -27,28 +24,9 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
-_lib: ctypes.CDLL | None = None
-
-
-def lib_path() -> str:
-    """``lib/libatx_mesh.so`` next to this file; ``ATX_MESH_LIBRARY`` overrides it."""
-    return os.environ.get("ATX_MESH_LIBRARY") or os.path.join(LIB_DIR, LIB_NAME)
-
-
-def load() -> ctypes.CDLL:
-    """Load libatx_mesh.so (once) and declare every prototype.  Raises if it is absent or lacks a symbol of the header."""
-    global _lib
-    if _lib is None:
-        path = lib_path()
-        if not os.path.exists(path):
-            raise RuntimeError(f"{path} not found: the HIP extension is not built. Run `python -c \"import __graft_entry__ as g; "
-                               "g.build()\"` (hipcc --offload-arch=gfx950) — this package has no CPU fallback.")
-        handle = ctypes.CDLL(path)
-        for name, (restype, argtypes) in SIGNATURES.items():
-            fn = getattr(handle, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _lib = handle
-    return _lib
+LIBRARY = Library("libatx_mesh.so", "ATX_MESH_LIBRARY", SIGNATURES, "atx_mesh_last_error")
+lib_path = LIBRARY.path  # ``lib/libatx_mesh.so`` next to this file; ``ATX_MESH_LIBRARY`` overrides it
+load = LIBRARY.load  # libatx_mesh.so, opened once with every prototype declared; raises if it is absent or lacks a symbol of the header
 
 
 def _check(name: str, t: torch.Tensor, dtype: torch.dtype, shape: tuple[int, ...], dev: torch.device) -> None:
@@ -91,7 +69,5 @@ def locate(mesh: Mesh, tgt_xyz: torch.Tensor, seed: torch.Tensor, max_steps: int
         code = handle.atx_mesh_locate(mesh.src_xyz.data_ptr(), mesh.n_src, mesh.tri.data_ptr(), mesh.nbr.data_ptr(), mesh.flag.data_ptr(),
                                       mesh.n_tri, tgt_xyz.data_ptr(), seed.data_ptr(), n, int(max_steps), tri_out.data_ptr(), w.data_ptr(),
                                       status.data_ptr(), steps.data_ptr(), stream)
-    if code != OK:
-        message = handle.atx_mesh_last_error().decode()
-        raise (ValueError if code == EINVAL else RuntimeError)(message or f"atx_mesh_locate failed with code {code}")
+    LIBRARY.check("atx_mesh_locate", code)
     return tri_out, w, status, steps

@@ -7,17 +7,13 @@ Return codes map to the exception types of ``native``: ``ValueError``, ``Asserti
 
 from __future__ import annotations
 
-import ctypes
-import os
 from ctypes import c_char_p, c_double, c_int, c_int32, c_int64, c_void_p
 from typing import Any
 
 import torch
 
-from .native import EINVAL, ELL_PADDED, ENOTIMPL, ESHAPE, OK, AtxError, _ptr, _stream, dtype_code
-
-LIB_NAME = "libatx_missing.so"
-LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
+from ._binding import Library
+from .native import EINVAL, ELL_PADDED, ENOTIMPL, ESHAPE, OK, AtxError, _ptr, _stream, dtype_code  # noqa: F401 - OK is one of this module's names
 
 MISSING_ALL, MISSING_HEAVIEST = 0, 1  # atx_missing_policy
 MISSING_POLICIES = {"all": MISSING_ALL, "heaviest": MISSING_HEAVIEST}
@@ -38,43 +34,15 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     ),
 }
 
-_lib: ctypes.CDLL | None = None
-
-
-def lib_path() -> str:
-    """``lib/libatx_missing.so`` next to this file; ``ATX_MISSING_LIBRARY`` overrides it."""
-    return os.environ.get("ATX_MISSING_LIBRARY") or os.path.join(LIB_DIR, LIB_NAME)
-
-
-def load() -> ctypes.CDLL:
-    """Load libatx_missing.so (once) and declare every prototype.  Raises if it is absent or lacks a symbol of the header."""
-    global _lib
-    if _lib is None:
-        path = lib_path()
-        if not os.path.exists(path):
-            raise RuntimeError(f"{path} not found: the HIP extension is not built. Run `python -c \"import __graft_entry__ as g; "
-                               "g.build()\"` (hipcc --offload-arch=gfx950) — this package has no CPU fallback.")
-        handle = ctypes.CDLL(path)
-        for name, (restype, argtypes) in SIGNATURES.items():
-            fn = getattr(handle, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _lib = handle
-    return _lib
+LIBRARY = Library("libatx_missing.so", "ATX_MISSING_LIBRARY", SIGNATURES, "atx_missing_last_error",
+                  errors={EINVAL: ValueError, ESHAPE: AssertionError, ENOTIMPL: NotImplementedError},
+                  unmapped=lambda fn, message, code: AtxError(f"{fn}: {message} (code {code})"))
+lib_path = LIBRARY.path  # ``lib/libatx_missing.so`` next to this file; ``ATX_MISSING_LIBRARY`` overrides it
+load = LIBRARY.load  # libatx_missing.so, opened once with every prototype declared; raises if it is absent or lacks a symbol of the header
 
 
 def _call(fn: str, *args: Any) -> None:
-    handle = load()
-    code = getattr(handle, fn)(*args)
-    if code == OK:
-        return
-    message = handle.atx_missing_last_error().decode() or f"{fn} failed with code {code}"
-    if code == EINVAL:
-        raise ValueError(message)
-    if code == ESHAPE:
-        raise AssertionError(message)
-    if code == ENOTIMPL:
-        raise NotImplementedError(message)
-    raise AtxError(f"{fn}: {message} (code {code})")
+    LIBRARY.check(fn, getattr(load(), fn)(*args))
 
 
 def missing_policy_code(policy) -> int:

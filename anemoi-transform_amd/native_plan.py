@@ -5,16 +5,12 @@ There is no CPU fallback: if ``lib/libatx_plan.so`` is missing, or a tensor hand
 
 from __future__ import annotations
 
-import ctypes
-import os
 from ctypes import c_char_p, c_int, c_int64, c_void_p
 from typing import Any
 
 import torch
 
-LIB_NAME = "libatx_plan.so"
-LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
-OK, EINVAL = 0, -1
+from ._binding import EINVAL, OK, Library  # noqa: F401 - the status codes are part of this module's names
 
 _TABLES = [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64]  # zs .. n_src, zt .. n_tgt
 
@@ -26,28 +22,9 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     "atx_plan_box_average_fill": (c_int, [*_TABLES, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
 }
 
-_lib: ctypes.CDLL | None = None
-
-
-def lib_path() -> str:
-    """``lib/libatx_plan.so`` next to this file; ``ATX_PLAN_LIBRARY`` overrides it."""
-    return os.environ.get("ATX_PLAN_LIBRARY") or os.path.join(LIB_DIR, LIB_NAME)
-
-
-def load() -> ctypes.CDLL:
-    """Load libatx_plan.so (once) and declare every prototype.  Raises if it is absent or lacks a symbol of the header."""
-    global _lib
-    if _lib is None:
-        path = lib_path()
-        if not os.path.exists(path):
-            raise RuntimeError(f"{path} not found: the HIP extension is not built. Run `python -c \"import __graft_entry__ as g; "
-                               "g.build()\"` (hipcc --offload-arch=gfx950) — this package has no CPU fallback.")
-        handle = ctypes.CDLL(path)
-        for name, (restype, argtypes) in SIGNATURES.items():
-            fn = getattr(handle, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _lib = handle
-    return _lib
+LIBRARY = Library("libatx_plan.so", "ATX_PLAN_LIBRARY", SIGNATURES, "atx_plan_last_error")
+lib_path = LIBRARY.path  # ``lib/libatx_plan.so`` next to this file; ``ATX_PLAN_LIBRARY`` overrides it
+load = LIBRARY.load  # libatx_plan.so, opened once with every prototype declared; raises if it is absent or lacks a symbol of the header
 
 
 class RowTable:
@@ -67,12 +44,6 @@ class RowTable:
         return self.z.data_ptr(), self.len.data_ptr(), self.start.data_ptr(), self.rows, self.n_points
 
 
-def _raise(handle: ctypes.CDLL, name: str, status: int) -> None:
-    if status != OK:
-        message = handle.atx_plan_last_error().decode()
-        raise (ValueError if status == EINVAL else RuntimeError)(message or f"{name} failed with code {status}")
-
-
 def box_average_count(src: RowTable, tgt: RowTable, count: torch.Tensor) -> None:
     """``atx_plan_box_average_count``: the number of entries of every target cell into ``count`` (int64 ``[n_tgt]``), on the current stream."""
     if count.dtype != torch.int64 or count.shape != (tgt.n_points,) or not count.is_contiguous() or count.device != tgt.z.device or \
@@ -81,7 +52,7 @@ def box_average_count(src: RowTable, tgt: RowTable, count: torch.Tensor) -> None
     handle = load()
     with torch.cuda.device(count.device):
         stream = torch.cuda.current_stream().cuda_stream
-        _raise(handle, "atx_plan_box_average_count", handle.atx_plan_box_average_count(*src.args(), *tgt.args(), count.data_ptr(), stream))
+        LIBRARY.check("atx_plan_box_average_count", handle.atx_plan_box_average_count(*src.args(), *tgt.args(), count.data_ptr(), stream))
 
 
 def box_average_fill(src: RowTable, tgt: RowTable, indptr: torch.Tensor, indices: torch.Tensor, data: torch.Tensor) -> None:
@@ -97,5 +68,5 @@ def box_average_fill(src: RowTable, tgt: RowTable, indptr: torch.Tensor, indices
     handle = load()
     with torch.cuda.device(indptr.device):
         stream = torch.cuda.current_stream().cuda_stream
-        _raise(handle, "atx_plan_box_average_fill", handle.atx_plan_box_average_fill(
+        LIBRARY.check("atx_plan_box_average_fill", handle.atx_plan_box_average_fill(
             *src.args(), *tgt.args(), indptr.data_ptr(), nnz, indices.data_ptr(), data.data_ptr(), stream))

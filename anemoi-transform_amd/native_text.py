@@ -5,17 +5,14 @@ There is no CPU fallback: if ``lib/libatx_text.so`` is missing, or a tensor hand
 
 from __future__ import annotations
 
-import ctypes
-import os
 from ctypes import c_char_p, c_int, c_int32, c_int64, c_void_p
 from typing import Any
 
 import torch
 
-LIB_NAME = "libatx_text.so"
-LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
+from ._binding import EINVAL, OK, Library  # noqa: F401 - the status codes are part of this module's names
+
 MAX_WIDTH = 256  # ATX_TEXT_MAX_WIDTH
-OK, EINVAL = 0, -1
 
 # every symbol include/atx_text.h declares: name -> (restype, argtypes)
 SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
@@ -24,28 +21,9 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     "atx_text_encode_statids": (c_int, [c_void_p, c_int64, c_int32, c_int64, c_void_p, c_void_p, c_void_p]),
 }
 
-_lib: ctypes.CDLL | None = None
-
-
-def lib_path() -> str:
-    """``lib/libatx_text.so`` next to this file; ``ATX_TEXT_LIBRARY`` overrides it."""
-    return os.environ.get("ATX_TEXT_LIBRARY") or os.path.join(LIB_DIR, LIB_NAME)
-
-
-def load() -> ctypes.CDLL:
-    """Load libatx_text.so (once) and declare every prototype.  Raises if it is absent or lacks a symbol of the header."""
-    global _lib
-    if _lib is None:
-        path = lib_path()
-        if not os.path.exists(path):
-            raise RuntimeError(f"{path} not found: the HIP extension is not built. Run `python -c \"import __graft_entry__ as g; "
-                               "g.build()\"` (hipcc --offload-arch=gfx950) — this package has no CPU fallback.")
-        handle = ctypes.CDLL(path)
-        for name, (restype, argtypes) in SIGNATURES.items():
-            fn = getattr(handle, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _lib = handle
-    return _lib
+LIBRARY = Library("libatx_text.so", "ATX_TEXT_LIBRARY", SIGNATURES, "atx_text_last_error")
+lib_path = LIBRARY.path  # ``lib/libatx_text.so`` next to this file; ``ATX_TEXT_LIBRARY`` overrides it
+load = LIBRARY.load  # libatx_text.so, opened once with every prototype declared; raises if it is absent or lacks a symbol of the header
 
 
 def encode_statids(text: torch.Tensor, code: torch.Tensor, undecided: torch.Tensor) -> None:
@@ -66,6 +44,4 @@ def encode_statids(text: torch.Tensor, code: torch.Tensor, undecided: torch.Tens
         stream = torch.cuda.current_stream().cuda_stream
         status = handle.atx_text_encode_statids(text.data_ptr(), n, width, text.stride(0) if n > 1 else max(text.stride(0), width),
                                                 code.data_ptr(), undecided.data_ptr(), stream)
-    if status != OK:
-        message = handle.atx_text_last_error().decode()
-        raise (ValueError if status == EINVAL else RuntimeError)(message or f"atx_text_encode_statids failed with code {status}")
+    LIBRARY.check("atx_text_encode_statids", status)

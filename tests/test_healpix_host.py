@@ -4,13 +4,12 @@ through the pixel centres, the C ABI of ``atx_healpix_ang2pix`` and the surface 
 
 from __future__ import annotations
 
-import subprocess
-
 import numpy as np
 import pytest
 from scipy.spatial import cKDTree
 
 import __graft_entry__ as graft
+import abi_checks
 from anemoi_transform_amd import healpix, native
 from anemoi_transform_amd.filters import create_filter_by_name, filter_registry
 from anemoi_transform_amd.filters.tabular import AddHealpix
@@ -161,8 +160,7 @@ def test_restatement_marks_rows_without_a_pixel():
 # ---- the C ABI ----------------------------------------------------------------------------------------------------------------------
 def test_entry_point_is_declared_bound_and_exported():
     name = "atx_healpix_ang2pix"
-    nm = subprocess.run(["nm", "-D", "--defined-only", graft.LIB], capture_output=True, text=True, check=True).stdout
-    exported = {line.split()[-1] for line in nm.splitlines() if line.strip()}
+    exported, _ = abi_checks.defined_dynamic_symbols(graft.LIB)
     assert name in graft.exported_names(), f"{name} is not declared in include/atx.h"
     assert name in native.SIGNATURES, f"{name} is not bound in native.py"
     assert name in exported, f"{name} is not exported by libatx.so"

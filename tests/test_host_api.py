@@ -14,6 +14,8 @@ import re
 import numpy as np
 import pytest
 
+import __graft_entry__ as graft
+import abi_checks
 from anemoi_transform_amd import grids, interp, native
 from anemoi_transform_amd.core import (
     DispatchingFilter,
@@ -426,25 +428,34 @@ def test_library_exports_nothing_but_the_header():
     """The dynamic symbol table of libatx.so is EXACTLY the ATX_API declarations of include/atx.h (= native.SIGNATURES): built with
     -fvisibility=hidden and a version script, so no C++ helper, kernel stub or template instance can interpose — or be interposed by —
     another library loaded into the same process (round 5 leaked 1 252 such names)."""
-    import shutil
     import subprocess
 
-    nm = shutil.which("nm") or "/opt/rocm/lib/llvm/bin/llvm-nm"
-    if not (shutil.which("nm") or os.path.exists(nm)):
-        pytest.skip("no nm")
-    listing = subprocess.run([nm, "-D", "--defined-only", native.lib_path()], capture_output=True, text=True, check=True).stdout
-    defined = sorted(line.split()[-1].split("@")[0] for line in listing.splitlines() if line.strip())
+    defined, kinds = abi_checks.defined_dynamic_symbols(native.lib_path())
     assert defined == sorted(native.SIGNATURES), sorted(set(defined) ^ set(native.SIGNATURES))[:20]
     assert defined == header_symbols()
     # every one of them a function in the text section, none weak
-    kinds = {line.split()[-2] for line in listing.splitlines() if line.strip()}
     assert kinds == {"T"}, kinds
     # the header marks each declaration, and only those, with ATX_API
     text = open(os.path.join(ROOT, "include", "atx.h")).read()
     assert sorted(re.findall(r"^ATX_API [^;(]*?\b(atx_[a-z_0-9]+)\(", text, flags=re.M)) == defined
     # RCCL stays a run-time binding (dlopen in atx_comm.hip), not a link-time dependency the stand-in could not replace
-    undefined = subprocess.run([nm, "-D", "--undefined-only", native.lib_path()], capture_output=True, text=True, check=True).stdout
+    undefined = subprocess.run([abi_checks.nm_tool(), "-D", "--undefined-only", native.lib_path()], capture_output=True, text=True,
+                               check=True).stdout
     assert "nccl" not in undefined.lower()
+
+
+@pytest.mark.parametrize("lib", graft.LIBRARIES, ids=lambda lib: os.path.basename(lib.path)[:-3])
+def test_library_exports_exactly_its_header(lib):
+    """Each of the five libraries is built, and its dynamic symbol table is exactly what its header declares with its export macro and
+    what its binding module declares prototypes for: functions in the text section, none weak.  A missing library fails: build() builds
+    them all."""
+    import importlib
+
+    assert os.path.exists(lib.path), f"{lib.path} is not built"
+    defined, kinds = abi_checks.defined_dynamic_symbols(lib.path)
+    signatures = importlib.import_module(f"anemoi_transform_amd.{lib.binding}").SIGNATURES
+    assert defined == sorted(abi_checks.header_declarations(lib.header, lib.macro)) == sorted(signatures)
+    assert kinds == {"T"}, kinds
 
 
 def test_header_is_plain_c_and_links(tmp_path):

@@ -5,12 +5,12 @@ the reference's statement (R: filters/tabular/irregular_to_grid.py, tests/tabula
 from __future__ import annotations
 
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import __graft_entry__ as graft
+import abi_checks
 from anemoi_transform_amd import native, obs
 from anemoi_transform_amd.filters import create_filter_by_name, filter_registry
 from anemoi_transform_amd.filters.tabular import AssignToGrid, IrregularToGrid
@@ -192,8 +192,7 @@ def test_restatement_equals_a_pandas_route(seed):
 def test_entry_points_are_declared_bound_and_exported():
     names = ("atx_obs_best_per_cell", "atx_obs_fill_stack")
     declared = graft.exported_names()
-    nm = subprocess.run(["nm", "-D", "--defined-only", graft.LIB], capture_output=True, text=True, check=True).stdout
-    exported = {line.split()[-1] for line in nm.splitlines() if line.strip()}
+    exported, _ = abi_checks.defined_dynamic_symbols(graft.LIB)
     for name in names:
         assert name in declared, f"{name} is not declared in include/atx.h"
         assert name in native.SIGNATURES, f"{name} is not bound in native.py"

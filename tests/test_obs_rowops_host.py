@@ -5,12 +5,11 @@ statements on the generators the GPU tests share."""
 
 from __future__ import annotations
 
-import subprocess
-
 import numpy as np
 import pytest
 
 import __graft_entry__ as graft
+import abi_checks
 from anemoi_transform_amd import native, obs
 from anemoi_transform_amd.filters import create_filter_by_name, filter_registry
 from anemoi_transform_amd.filters.tabular import AddAzimuth, AddForcings, AddMSGAngles, RadianceToBrightnessTemperature
@@ -84,8 +83,7 @@ NAMES = ("atx_obs_forcings", "atx_obs_view_angles", "atx_obs_planck_bt")
 
 def test_entry_points_are_declared_bound_and_exported():
     declared = graft.exported_names()
-    nm = subprocess.run(["nm", "-D", "--defined-only", graft.LIB], capture_output=True, text=True, check=True).stdout
-    exported = {line.split()[-1] for line in nm.splitlines() if line.strip()}
+    exported, _ = abi_checks.defined_dynamic_symbols(graft.LIB)
     for name in NAMES:
         assert name in declared, f"{name} is not declared in include/atx.h"
         assert name in native.SIGNATURES, f"{name} is not bound in native.py"

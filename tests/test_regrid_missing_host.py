@@ -221,21 +221,18 @@ def test_header_exports_and_binding_agree():
     """libatx_missing.so exports exactly the ATX_MISSING_API declarations of include/atx_missing.h, which native_missing binds; libatx
     itself is as it was."""
     import os
-    import re
-    import shutil
-    import subprocess
 
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    text = open(os.path.join(root, "include", "atx_missing.h")).read()
-    declared = re.findall(r"^ATX_MISSING_API [^;(]*?\b(atx_[a-z_0-9]+)\(", text, flags=re.M)
+    import abi_checks
+
+    header = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "atx_missing.h")
+    text = open(header).read()
+    declared = abi_checks.header_declarations(header, "ATX_MISSING_API")
     assert declared == ["atx_missing_version", "atx_missing_last_error", "atx_regrid_ell_missing", "atx_regrid_csr_missing"]
     assert list(native_missing.SIGNATURES) == declared and not set(declared) & set(native.SIGNATURES)
     lib = native_missing.load()
     assert lib.atx_missing_version() == 420 and "#define ATX_MISSING_VERSION 420" in text
-    nm = shutil.which("nm") or "/opt/rocm/lib/llvm/bin/llvm-nm"
-    if shutil.which("nm") or os.path.exists(nm):
-        listing = subprocess.run([nm, "-D", "--defined-only", native_missing.lib_path()], capture_output=True, text=True, check=True).stdout
-        assert sorted(line.split()[-1].split("@")[0] for line in listing.splitlines() if line.strip()) == sorted(declared)
+    if abi_checks.nm_tool():
+        assert abi_checks.defined_dynamic_symbols(native_missing.lib_path())[0] == sorted(declared)
 
 
 def test_no_kernel_uses_scratch_memory():

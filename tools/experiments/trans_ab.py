@@ -96,7 +96,7 @@ def main():
         for c, (fn, nbytes, out) in cases.items():
             ref = None
             for l, h in libs.items():
-                native._lib = h
+                native.use_library(h)
                 times[c][l].append(time_once(fn))
                 if r == 0:  # outputs of every build against the first one's
                     got = out.data.clone()
