@@ -2,35 +2,18 @@
 #include "atx_common.hpp"
 
 #include <cstring>
-#include <string>
 
 namespace atx {
 
-static thread_local std::string g_last_error;
 // The launch form the calling thread's last atx_pointwise_stack took (atx_last_route): a literal, set by the dispatcher of
 // atx_pointwise.hip.  Diagnostic only.
 __thread const char* g_last_route = "none";
-
-void set_error(const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_last_error = buf;
-}
-
-int hip_status(hipError_t e, const char* what) {
-    if (e == hipSuccess) return ATX_OK;
-    set_error("%s: HIP error %d (%s)", what, (int)e, hipGetErrorString(e));
-    return ATX_EHIP;
-}
 
 }  // namespace atx
 
 extern "C" int atx_version(void) { return ATX_VERSION; }
 
-extern "C" const char* atx_last_error(void) { return atx::g_last_error.c_str(); }
+extern "C" const char* atx_last_error(void) { return atx::last_error().c_str(); }
 
 extern "C" const char* atx_last_route(void) { return atx::g_last_route; }
 

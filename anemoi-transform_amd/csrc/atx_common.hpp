@@ -11,33 +11,17 @@
 #include <type_traits>
 
 #include "../../include/atx.h"
+#include "atx_host.hpp"  // the error message, ATX_REQUIRE, ATX_LAUNCH_CHECK, grid_for
 
 namespace atx {
 
-// ---- host-side error plumbing ------------------------------------------------
-void set_error(const char* fmt, ...);  // defined in atx_api.hip
 extern __thread const char* g_last_route;  // defined in atx_api.hip; atx_pointwise.hip names the launch form it takes (atx_last_route)
-int hip_status(hipError_t e, const char* what);
 
 // Internal status, never returned across the C ABI: the per-level operator tables of this call do not fit the 64 KB a workgroup
 // may stage in LDS (tall stacks with long programs: float32, ~1000 levels, 8 stages = 72 KB).  The entry points answer it themselves:
 // atx_pointwise_stack runs the stages in two halves (stages compose, so the bits are the same), the regrid entry points run the gather
 // without the program and apply it to the output in place.  (Round 3 returned ATX_ENOTIMPL for shapes round 2 had served.)
 #define ATX_SPLIT_PROGRAM 1
-
-#define ATX_REQUIRE(cond, code, ...)  \
-    do {                              \
-        if (!(cond)) {                \
-            atx::set_error(__VA_ARGS__); \
-            return (code);            \
-        }                             \
-    } while (0)
-
-#define ATX_LAUNCH_CHECK(what)                                   \
-    do {                                                         \
-        int _st = atx::hip_status(hipGetLastError(), what);      \
-        if (_st != ATX_OK) return _st;                           \
-    } while (0)
 
 constexpr int kWave = 64;    // CDNA4 wavefront
 constexpr int kBlock = 256;  // 4 waves: one per SIMD of a CU

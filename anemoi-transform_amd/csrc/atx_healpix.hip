@@ -136,8 +136,7 @@ extern "C" int atx_healpix_ang2pix(const double* longitude, const double* latitu
     if (st != ATX_OK) return st;
     int order = 0;  // log2(nside), used by the nested scheme only
     while ((int64_t(1) << order) < nside) ++order;
-    const int64_t blocks = (n + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL(healpix_ang2pix_kernel, dim3((unsigned)(blocks < kHpGrid ? blocks : kHpGrid)), dim3(kBlock), 0, s, longitude, latitude, n,
+    hipLaunchKernelGGL(healpix_ang2pix_kernel, dim3(grid_for(n, kBlock, kHpGrid)), dim3(kBlock), 0, s, longitude, latitude, n,
                        nside, order, scheme == ATX_HEALPIX_NEST ? 1 : 0, pix, reinterpret_cast<unsigned long long*>(n_bad));
     ATX_LAUNCH_CHECK("healpix_ang2pix");
     return ATX_OK;

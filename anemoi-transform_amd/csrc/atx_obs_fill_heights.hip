@@ -126,8 +126,7 @@ extern "C" int atx_obs_fill_heights(const double* latitude, const double* longit
     if (n == 0) return ATX_OK;
     ATX_REQUIRE(latitude && longitude && altitude && lat_axis && lat_perm && lon_axis && lon_perm && heights && out && flags, ATX_EINVAL,
                 "atx_obs_fill_heights: null pointer");
-    const int64_t blocks = (n + kBlock - 1) / kBlock;
-    const dim3 grid((unsigned)(blocks < kFhGrid ? blocks : kFhGrid));
+    const dim3 grid(grid_for(n, kBlock, kFhGrid));
     unsigned long long* c = reinterpret_cast<unsigned long long*>(counters);
     if (dtype == ATX_F32)
         hipLaunchKernelGGL(obs_fill_heights_kernel<float>, grid, dim3(kBlock), 0, s, latitude, longitude, altitude, n, lat_axis, lat_perm, (int)n_lat,

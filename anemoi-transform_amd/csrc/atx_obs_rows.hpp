@@ -28,9 +28,6 @@ struct ColumnProgram {
 // atx_obs_row_program.hip: the launch of a program of codes >= ATX_COLOP_SCALAR (validated by atx_obs_column_ops, n > 0)
 int launch_obs_row_program(const ColumnProgram& p, int64_t n, hipStream_t stream);
 
-static unsigned row_grid(int64_t n) {
-    const int64_t blocks = (n + kBlock - 1) / kBlock;
-    return (unsigned)(blocks < kRowGrid ? blocks : kRowGrid);
-}
+static unsigned row_grid(int64_t n) { return grid_for(n, kBlock, kRowGrid); }
 
 }  // namespace atx

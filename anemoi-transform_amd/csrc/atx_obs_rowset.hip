@@ -40,10 +40,7 @@ constexpr int kRsGrid = 2048;
 constexpr int64_t kKeyMax = INT64_MAX;  // the key of every missing value: NaN, NaT
 constexpr int64_t kInfBits = 0x7ff0000000000000ll;
 
-static unsigned rowset_grid(int64_t n) {
-    const int64_t blocks = (n + kBlock - 1) / kBlock;
-    return (unsigned)(blocks < kRsGrid ? blocks : kRsGrid);
-}
+static unsigned rowset_grid(int64_t n) { return grid_for(n, kBlock, kRsGrid); }
 
 __device__ __forceinline__ int64_t float_key(double x) {
     const int64_t b = __double_as_longlong(x);

@@ -727,9 +727,8 @@ static Routed route_row_chunk(const ColumnsCall<T>& k) {
     if (lds_rows > 64 * 1024 && k.n_stage > 1) return ATX_SPLIT_PROGRAM;  // the entry point runs the stages in two halves
     ATX_REQUIRE(lds_rows <= 64 * 1024, ATX_ENOTIMPL, "pointwise: one stage over %d levels needs %zu B of LDS", k.n_lev, lds_rows);
     const int Cg = k.C < kBlock ? k.C : kBlock;
-    const int64_t chunk = (int64_t)(kBlock / Cg) * kPwUnroll;  // rows one workgroup moves per iteration
-    int64_t blocks = (k.n_pts + chunk - 1) / chunk;
-    if (blocks > kStreamGrid) blocks = kStreamGrid;
+    const int chunk = (kBlock / Cg) * kPwUnroll;  // rows one workgroup moves per iteration
+    const unsigned blocks = grid_for(k.n_pts, chunk, kStreamGrid);
     g_last_route = k.wide ? "row_chunk" : "row_chunk_scalar";
     if (k.wide)
         hipLaunchKernelGGL((pointwise_cols_kernel<T, VEC>), dim3((unsigned)blocks), dim3(kBlock), lds_rows, k.st, k.x, k.y, k.n_pts, k.n_lev, k.C, k.xp,

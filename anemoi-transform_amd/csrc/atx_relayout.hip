@@ -183,9 +183,7 @@ static int relayout_typed(const void* src_, void* dst_, int64_t n_pts, int n_lev
     if (src_layout == dst_layout) {
         const int64_t n_rows = src_layout == ATX_COLUMNS ? n_pts : n_lev;
         const int64_t row_len = src_layout == ATX_COLUMNS ? n_lev : n_pts;
-        int64_t blocks = (n_rows * row_len + kBlock - 1) / kBlock;
-        if (blocks > kStreamGrid) blocks = kStreamGrid;
-        hipLaunchKernelGGL(pitched_copy_kernel<T>, dim3((unsigned)blocks), dim3(kBlock), 0, st, src, dst, n_rows, row_len, sp, dp);
+        hipLaunchKernelGGL(pitched_copy_kernel<T>, dim3(grid_for(n_rows * row_len, kBlock, kStreamGrid)), dim3(kBlock), 0, st, src, dst, n_rows, row_len, sp, dp);
         ATX_LAUNCH_CHECK("pitched_copy");
         return ATX_OK;
     }

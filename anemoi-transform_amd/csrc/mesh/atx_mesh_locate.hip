@@ -13,28 +13,12 @@
 // atomics, no LDS; plain vector stores.  Whatever tri, nbr and seed hold, every read stays inside the arrays as sized by the arguments:
 // a triangle number is checked against n_tri and a vertex number against n_src before it is used, and a lane that fails the check
 // stops with status 3.  The walk is bounded by max_steps, which the entry point caps.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <string>
 
 #include "../../../include/atx_mesh.h"
+#include "../atx_host.hpp"
 
 namespace atx_mesh {
-
-static thread_local std::string g_last_error;
-
-static void set_error(const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_last_error = buf;
-}
 
 constexpr int kBlock = 256;  // 4 waves: one per SIMD of a CU
 constexpr int kGrid = 2048;  // grid cap: beyond 2^19 targets a lane takes further targets
@@ -121,16 +105,11 @@ __global__ __launch_bounds__(kBlock) void locate_kernel(const double* __restrict
     }
 }
 
-static unsigned grid_for(int64_t n) {
-    const int64_t blocks = (n + kBlock - 1) / kBlock;
-    return (unsigned)(blocks < kGrid ? blocks : kGrid);
-}
-
 }  // namespace atx_mesh
 
 extern "C" int atx_mesh_version(void) { return ATX_MESH_VERSION; }
 
-extern "C" const char* atx_mesh_last_error(void) { return atx_mesh::g_last_error.c_str(); }
+extern "C" const char* atx_mesh_last_error(void) { return atx::last_error().c_str(); }
 
 extern "C" int atx_mesh_locate(const double* src_xyz, int64_t n_src, const int32_t* tri, const int32_t* nbr, const uint8_t* flag,
                                int64_t n_tri, const double* tgt_xyz, const int32_t* seed, int64_t n_tgt, int32_t max_steps,
@@ -138,31 +117,18 @@ extern "C" int atx_mesh_locate(const double* src_xyz, int64_t n_src, const int32
     using namespace atx_mesh;
     const char* fn = "atx_mesh_locate";
     constexpr int64_t kMax = 2147483647;
-    if (n_src < 1 || n_src > kMax || n_tri < 1 || n_tri > kMax) {
-        set_error("%s: n_src = %lld, n_tri = %lld: a size is outside 1 .. 2^31 - 1", fn, (long long)n_src, (long long)n_tri);
-        return ATX_EINVAL;
-    }
-    if (n_tgt < 0 || n_tgt > kMax) {
-        set_error("%s: n_tgt = %lld is outside 0 .. 2^31 - 1", fn, (long long)n_tgt);
-        return ATX_EINVAL;
-    }
-    if (max_steps < 0 || max_steps > ATX_MESH_MAX_STEPS) {
-        set_error("%s: max_steps = %d is outside 0 .. %d", fn, (int)max_steps, (int)ATX_MESH_MAX_STEPS);
-        return ATX_EINVAL;
-    }
+    ATX_REQUIRE(n_src >= 1 && n_src <= kMax && n_tri >= 1 && n_tri <= kMax, ATX_EINVAL,
+                "%s: n_src = %lld, n_tri = %lld: a size is outside 1 .. 2^31 - 1", fn, (long long)n_src, (long long)n_tri);
+    ATX_REQUIRE(n_tgt >= 0 && n_tgt <= kMax, ATX_EINVAL, "%s: n_tgt = %lld is outside 0 .. 2^31 - 1", fn, (long long)n_tgt);
+    ATX_REQUIRE(max_steps >= 0 && max_steps <= ATX_MESH_MAX_STEPS, ATX_EINVAL, "%s: max_steps = %d is outside 0 .. %d", fn, (int)max_steps,
+                (int)ATX_MESH_MAX_STEPS);
     if (n_tgt == 0) return ATX_OK;
-    if (!src_xyz || !tri || !nbr || !flag || !tgt_xyz || !seed || !tri_out || !w || !status || !steps) {
-        set_error("%s: null pointer (src_xyz=%p tri=%p nbr=%p flag=%p tgt_xyz=%p seed=%p tri_out=%p w=%p status=%p steps=%p) with n_tgt = %lld",
-                  fn, (const void*)src_xyz, (const void*)tri, (const void*)nbr, (const void*)flag, (const void*)tgt_xyz, (const void*)seed,
-                  (void*)tri_out, (void*)w, (void*)status, (void*)steps, (long long)n_tgt);
-        return ATX_EINVAL;
-    }
-    hipLaunchKernelGGL(locate_kernel, dim3(grid_for(n_tgt)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), src_xyz, n_src, tri, nbr,
+    ATX_REQUIRE(src_xyz && tri && nbr && flag && tgt_xyz && seed && tri_out && w && status && steps, ATX_EINVAL,
+                "%s: null pointer (src_xyz=%p tri=%p nbr=%p flag=%p tgt_xyz=%p seed=%p tri_out=%p w=%p status=%p steps=%p) with n_tgt = %lld",
+                fn, (const void*)src_xyz, (const void*)tri, (const void*)nbr, (const void*)flag, (const void*)tgt_xyz, (const void*)seed,
+                (void*)tri_out, (void*)w, (void*)status, (void*)steps, (long long)n_tgt);
+    hipLaunchKernelGGL(locate_kernel, dim3(atx::grid_for(n_tgt, kBlock, kGrid)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), src_xyz, n_src, tri, nbr,
                        flag, n_tri, tgt_xyz, seed, n_tgt, max_steps, tri_out, w, status, steps);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("%s: HIP error %d (%s)", fn, (int)e, hipGetErrorString(e));
-        return ATX_EHIP;
-    }
+    ATX_LAUNCH_CHECK(fn);
     return ATX_OK;
 }

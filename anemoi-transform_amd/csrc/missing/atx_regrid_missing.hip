@@ -5,7 +5,8 @@
 // what MIR does where `self.matrix @ data` (R: filters/fields/regrid.py:310) makes the target NaN as soon as one of its k sources is.
 // Column stacks only, natural target order, no level program: the existing gather kernels and their dispatch are untouched.  The
 // device helpers (Pack, store_out, load_src, xcd_tile, quiet_nan) and cols_vector_ok are libatx's own headers, included, not copied;
-// nothing of libatx is linked: the error string, the argument checks and the ATX_VALIDATE range check below are this library's.
+// nothing of libatx is linked: the message cell (atx_host.hpp), the stack check and the ATX_VALIDATE range check
+// (atx_regrid_check.hpp) are the same source, compiled into this library.
 //
 // One (target, vector) item per lane, consecutive lanes on consecutive vectors of a column, as the direct kernel of
 // atx_regrid_columns.inc: the lane reads its row's index and weight words itself, the source vectors with plain loads, and stores once.
@@ -16,39 +17,12 @@
 // Where no element of the lane's vector met a NaN the lane stores num as it is — scipy's csr_matvec loop, no division; the division and
 // the policy sit behind one branch that a wave of complete data never takes.
 // No LDS, no barrier, no scratch (every private array is indexed by unrolled constants; profiles/regrid_missing_resources.json).
-#include <cstdlib>
-#include <string>
-
 #include "../../../include/atx_missing.h"
 #include "../atx_common.hpp"
+#include "../atx_regrid_check.hpp"
 #include "../atx_regrid_decl.hpp"
 
 namespace atx {
-
-static thread_local std::string g_missing_error;
-
-static void missing_error(const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_missing_error = buf;
-}
-
-#define MISSING_REQUIRE(cond, code, ...)    \
-    do {                                    \
-        if (!(cond)) {                      \
-            atx::missing_error(__VA_ARGS__); \
-            return (code);                  \
-        }                                   \
-    } while (0)
-
-static int missing_hip_status(hipError_t e, const char* what) {
-    if (e == hipSuccess) return ATX_OK;
-    missing_error("%s: HIP error %d (%s)", what, (int)e, hipGetErrorString(e));
-    return ATX_EHIP;
-}
 
 constexpr int kMissingBlock = 256;  // lanes per workgroup, the direct kernel's
 constexpr int kMissingStep = 4;     // entries of a run-time row (k outside the ladder, CSR) whose source vectors are in flight together
@@ -193,13 +167,14 @@ static int launch_ell_missing(const T* src, T* out, const int32_t* idx, const T*
     const int C = (n_lev + VEC - 1) / VEC;
     const int64_t n_items = n_tgt * C;
     const int64_t blocks = (n_items + kMissingBlock - 1) / kMissingBlock;
-    MISSING_REQUIRE(blocks <= INT32_MAX, ATX_ENOTIMPL, "atx_regrid_ell_missing: %lld x %d items exceed one launch", (long long)n_tgt, C);
+    ATX_REQUIRE(blocks <= INT32_MAX, ATX_ENOTIMPL, "atx_regrid_ell_missing: %lld x %d items exceed one launch", (long long)n_tgt, C);
     const unsigned n_blocks = (unsigned)blocks;
-    auto launch = [&](auto kc) {
+    auto launch = [&](auto kc) -> int {
         constexpr int K = decltype(kc)::value;
         hipLaunchKernelGGL((regrid_cols_ell_missing_kernel<T, VEC, K>), dim3(n_blocks), dim3(kMissingBlock), 0, st, src, out, idx, w, n_items, C, k,
                            sp, op, n_blocks, heaviest ? 1 : 0, min_valid);
-        return missing_hip_status(hipGetLastError(), "regrid_cols_ell_missing");
+        ATX_LAUNCH_CHECK("regrid_cols_ell_missing");
+        return ATX_OK;
     };
     // Compile-time rows where a k-NN or bilinear regrid has them (the whole row's source vectors in flight at once), the run-time loop
     // elsewhere.  O1280 -> 0.25 degree, 137 levels, k = 4 (profiles/regrid_missing_bench.json): 0.445 ms f32 / 0.836 ms f64 on the ladder —
@@ -233,11 +208,12 @@ static int launch_csr_missing(const T* src, T* out, const int32_t* indptr, const
     const int C = (n_lev + VEC - 1) / VEC;
     const int64_t n_items = n_tgt * C;
     const int64_t blocks = (n_items + kMissingBlock - 1) / kMissingBlock;
-    MISSING_REQUIRE(blocks <= INT32_MAX, ATX_ENOTIMPL, "atx_regrid_csr_missing: %lld x %d items exceed one launch", (long long)n_tgt, C);
+    ATX_REQUIRE(blocks <= INT32_MAX, ATX_ENOTIMPL, "atx_regrid_csr_missing: %lld x %d items exceed one launch", (long long)n_tgt, C);
     const unsigned n_blocks = (unsigned)blocks;
     hipLaunchKernelGGL((regrid_cols_csr_missing_kernel<T, VEC>), dim3(n_blocks), dim3(kMissingBlock), 0, st, src, out, indptr, indices, data, n_items,
                        C, sp, op, n_blocks, heaviest ? 1 : 0, min_valid);
-    return missing_hip_status(hipGetLastError(), "regrid_cols_csr_missing");
+    ATX_LAUNCH_CHECK("regrid_cols_csr_missing");
+    return ATX_OK;
 }
 
 template <typename T>
@@ -251,71 +227,10 @@ static int regrid_csr_missing_typed(const void* src_, void* out_, const int32_t*
     return launch_csr_missing<T, 1>(src, out, indptr, indices, data, n_tgt, n_lev, sp, op, heaviest, static_cast<T>(min_valid), st);
 }
 
-// The stack's pointers, sizes and pitches, as atx_regrid_ell / atx_regrid_csr check them (atx_regrid.hip: check_stack_args).
-static int check_stack(const char* fn, const void* src, const void* out, int64_t n_src, int64_t n_tgt, int64_t n_lev, int64_t sp, int64_t op,
-                       int dtype, int layout) {
-    MISSING_REQUIRE(src && (out || n_tgt == 0), ATX_EINVAL, "%s: null src/out pointer", fn);  // (an output of zero targets may have no storage)
-    MISSING_REQUIRE(dtype == ATX_F32 || dtype == ATX_F64, ATX_EINVAL, "%s: bad dtype %d", fn, dtype);
-    MISSING_REQUIRE(layout == ATX_COLUMNS || layout == ATX_FIELDS, ATX_EINVAL, "%s: bad layout %d", fn, layout);
-    MISSING_REQUIRE(n_src > 0 && n_tgt >= 0 && n_lev > 0, ATX_EINVAL, "%s: bad sizes n_src=%lld n_tgt=%lld n_lev=%lld", fn, (long long)n_src,
-                    (long long)n_tgt, (long long)n_lev);
-    MISSING_REQUIRE(n_src <= INT32_MAX && n_tgt <= INT32_MAX && n_lev <= 65535, ATX_ENOTIMPL,
-                    "%s: sizes exceed int32 indexing (n_src=%lld n_tgt=%lld n_lev=%lld)", fn, (long long)n_src, (long long)n_tgt, (long long)n_lev);
-    if (layout == ATX_COLUMNS)
-        MISSING_REQUIRE(sp >= n_lev && op >= n_lev, ATX_ESHAPE, "%s: column pitch (%lld, %lld) < n_lev %lld", fn, (long long)sp, (long long)op,
-                        (long long)n_lev);
-    else
-        MISSING_REQUIRE(sp >= n_src && op >= n_tgt, ATX_ESHAPE, "%s: field pitch (%lld, %lld) < points (%lld, %lld)", fn, (long long)sp,
-                        (long long)op, (long long)n_src, (long long)n_tgt);
-    return ATX_OK;
-}
-
-// ATX_VALIDATE=1 (read once per process), as in libatx: the tables are range-checked ON THE DEVICE before the launch, which is refused
-// (ATX_EINVAL, nothing written) if an entry points outside the stack.  It synchronises the stream; off by default.
-__global__ void __launch_bounds__(kBlock)
-missing_check_range_kernel(const int32_t* __restrict__ idx, int64_t n, int64_t lo, int64_t hi, unsigned long long* n_bad) {
-    unsigned long long bad = 0;
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
-        const int64_t v = idx[i];
-        bad += (v < lo || v >= hi) ? 1u : 0u;
-    }
-    if (bad) atomicAdd(n_bad, bad);
-}
-
-static bool validation_on() {
-    static const bool on = [] {
-        const char* v = std::getenv("ATX_VALIDATE");
-        return v && *v && std::strcmp(v, "0") != 0;
-    }();
-    return on;
-}
-
-static int validate_table(const char* fn, const char* what, const int32_t* idx, int64_t n, int64_t lo, int64_t hi, hipStream_t s) {
-    if (n <= 0 || !idx) return ATX_OK;
-    unsigned long long* n_bad = nullptr;
-    int st = missing_hip_status(hipMalloc(reinterpret_cast<void**>(&n_bad), sizeof(unsigned long long)), "ATX_VALIDATE: hipMalloc");
-    if (st != ATX_OK) return st;
-    unsigned long long host = 0;
-    st = missing_hip_status(hipMemsetAsync(n_bad, 0, sizeof(unsigned long long), s), "ATX_VALIDATE: memset");
-    if (st == ATX_OK) {
-        int64_t blocks = (n + kBlock - 1) / kBlock;
-        if (blocks > 2048) blocks = 2048;
-        hipLaunchKernelGGL(missing_check_range_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, s, idx, n, lo, hi, n_bad);
-        st = missing_hip_status(hipGetLastError(), "ATX_VALIDATE: launch");
-    }
-    if (st == ATX_OK) st = missing_hip_status(hipMemcpyAsync(&host, n_bad, sizeof host, hipMemcpyDeviceToHost, s), "ATX_VALIDATE: copy");
-    if (st == ATX_OK) st = missing_hip_status(hipStreamSynchronize(s), "ATX_VALIDATE: synchronise");
-    (void)hipFree(n_bad);
-    if (st != ATX_OK) return st;
-    MISSING_REQUIRE(host == 0, ATX_EINVAL, "%s: ATX_VALIDATE found %llu entries of %s outside [%lld, %lld) — launch refused", fn, host, what,
-                    (long long)lo, (long long)hi);
-    return ATX_OK;
-}
-
 static int check_missing_args(const char* fn, int layout, int policy, double min_valid) {
-    MISSING_REQUIRE(policy == ATX_MISSING_ALL || policy == ATX_MISSING_HEAVIEST, ATX_EINVAL, "%s: unknown missing-value policy %d", fn, policy);
-    MISSING_REQUIRE(min_valid >= 0.0 && min_valid <= 1.0, ATX_EINVAL, "%s: min_valid = %g is outside [0, 1]", fn, min_valid);  // (NaN fails both)
-    MISSING_REQUIRE(layout == ATX_COLUMNS, ATX_ENOTIMPL, "%s: column stacks only (convert an ATX_FIELDS stack with atx_relayout)", fn);
+    ATX_REQUIRE(policy == ATX_MISSING_ALL || policy == ATX_MISSING_HEAVIEST, ATX_EINVAL, "%s: unknown missing-value policy %d", fn, policy);
+    ATX_REQUIRE(min_valid >= 0.0 && min_valid <= 1.0, ATX_EINVAL, "%s: min_valid = %g is outside [0, 1]", fn, min_valid);  // (NaN fails both)
+    ATX_REQUIRE(layout == ATX_COLUMNS, ATX_ENOTIMPL, "%s: column stacks only (convert an ATX_FIELDS stack with atx_relayout)", fn);
     return ATX_OK;
 }
 
@@ -325,18 +240,18 @@ using namespace atx;
 
 extern "C" int atx_missing_version(void) { return ATX_MISSING_VERSION; }
 
-extern "C" const char* atx_missing_last_error(void) { return g_missing_error.c_str(); }
+extern "C" const char* atx_missing_last_error(void) { return last_error().c_str(); }
 
 extern "C" int atx_regrid_ell_missing(const void* src, void* out, const int32_t* idx, const void* w, int64_t n_src, int64_t n_tgt, int32_t k,
                                       int64_t n_lev, int64_t src_pitch, int64_t out_pitch, int dtype, int layout, int32_t flags, int policy,
                                       double min_valid, void* stream) {
     const char* fn = "atx_regrid_ell_missing";
-    int st = check_stack(fn, src, out, n_src, n_tgt, n_lev, src_pitch, out_pitch, dtype, layout);
+    int st = check_stack_args(fn, src, out, n_src, n_tgt, n_lev, src_pitch, out_pitch, dtype, layout);
     if (st != ATX_OK) return st;
-    MISSING_REQUIRE(idx || n_tgt == 0, ATX_EINVAL, "%s: null idx", fn);
-    MISSING_REQUIRE(k >= 1 && k <= 64, ATX_EINVAL, "%s: k=%d outside [1, 64]", fn, k);
-    MISSING_REQUIRE(w, ATX_EINVAL, "%s: null w (an unweighted gather has nothing to renormalise: use atx_regrid_ell)", fn);
-    MISSING_REQUIRE((flags & ~ATX_ELL_PADDED) == 0, ATX_EINVAL, "%s: unknown flags 0x%x", fn, flags);
+    ATX_REQUIRE(idx || n_tgt == 0, ATX_EINVAL, "%s: null idx", fn);
+    ATX_REQUIRE(k >= 1 && k <= 64, ATX_EINVAL, "%s: k=%d outside [1, 64]", fn, k);
+    ATX_REQUIRE(w, ATX_EINVAL, "%s: null w (an unweighted gather has nothing to renormalise: use atx_regrid_ell)", fn);
+    ATX_REQUIRE((flags & ~ATX_ELL_PADDED) == 0, ATX_EINVAL, "%s: unknown flags 0x%x", fn, flags);
     st = check_missing_args(fn, layout, policy, min_valid);
     if (st != ATX_OK) return st;
     if (n_tgt == 0) return ATX_OK;
@@ -354,11 +269,11 @@ extern "C" int atx_regrid_csr_missing(const void* src, void* out, const int32_t*
                                       int64_t n_tgt, int64_t nnz, int64_t n_lev, int64_t src_pitch, int64_t out_pitch, int dtype, int layout,
                                       int policy, double min_valid, void* stream) {
     const char* fn = "atx_regrid_csr_missing";
-    int st = check_stack(fn, src, out, n_src, n_tgt, n_lev, src_pitch, out_pitch, dtype, layout);
+    int st = check_stack_args(fn, src, out, n_src, n_tgt, n_lev, src_pitch, out_pitch, dtype, layout);
     if (st != ATX_OK) return st;
-    MISSING_REQUIRE(indptr || n_tgt == 0, ATX_EINVAL, "%s: null indptr", fn);
-    MISSING_REQUIRE(nnz >= 0 && nnz <= INT32_MAX, ATX_ENOTIMPL, "%s: nnz=%lld outside int32", fn, (long long)nnz);
-    MISSING_REQUIRE(nnz == 0 || (indices && data), ATX_EINVAL, "%s: null indices/data", fn);
+    ATX_REQUIRE(indptr || n_tgt == 0, ATX_EINVAL, "%s: null indptr", fn);
+    ATX_REQUIRE(nnz >= 0 && nnz <= INT32_MAX, ATX_ENOTIMPL, "%s: nnz=%lld outside int32", fn, (long long)nnz);
+    ATX_REQUIRE(nnz == 0 || (indices && data), ATX_EINVAL, "%s: null indices/data", fn);
     st = check_missing_args(fn, layout, policy, min_valid);
     if (st != ATX_OK) return st;
     if (n_tgt == 0) return ATX_OK;

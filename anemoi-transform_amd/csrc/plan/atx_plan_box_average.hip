@@ -19,27 +19,10 @@
 // counters.  No atomics, no LDS, no scratch (profiles/box_average_resources.json); plain vector stores.  The row tables are validated
 // by the caller before upload; whatever they hold, every read stays inside the tables as sized by the arguments, and `fill` writes
 // only inside [indptr[t], min(indptr[t+1], nnz)).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include <cstdarg>
-#include <cstdio>
-#include <string>
-
 #include "../../../include/atx_plan.h"
+#include "../atx_host.hpp"
 
 namespace atx_plan {
-
-static thread_local std::string g_last_error;
-
-static void set_error(const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_last_error = buf;
-}
 
 constexpr int kBlock = 256;  // 4 waves: one per SIMD of a CU
 constexpr int kGrid = 2048;  // grid cap, as kRsGrid: beyond 2^19 targets a lane takes further targets
@@ -160,41 +143,17 @@ __global__ __launch_bounds__(kBlock) void box_average_fill_kernel(RowTable src, 
     }
 }
 
-static bool check(const char* fn, const void* zs, const void* src_len, const void* src_start, int64_t n_src_rows, int64_t n_src,
-                  const void* zt, const void* tgt_len, const void* tgt_start, int64_t n_tgt_rows, int64_t n_tgt) {
+static int check(const char* fn, const void* zs, const void* src_len, const void* src_start, int64_t n_src_rows, int64_t n_src,
+                 const void* zt, const void* tgt_len, const void* tgt_start, int64_t n_tgt_rows, int64_t n_tgt) {
     constexpr int64_t kMax = 2147483647;
-    if (n_src_rows < 1 || n_src_rows > kMax || n_tgt_rows < 1 || n_tgt_rows > kMax) {
-        set_error("%s: n_src_rows = %lld, n_tgt_rows = %lld: the number of rows is outside 1 .. 2^31 - 1", fn, (long long)n_src_rows,
-                  (long long)n_tgt_rows);
-        return false;
-    }
-    if (n_src < 1 || n_src > kMax) {
-        set_error("%s: n_src = %lld is outside 1 .. 2^31 - 1", fn, (long long)n_src);
-        return false;
-    }
-    if (n_tgt < 0) {
-        set_error("%s: n_tgt = %lld is negative", fn, (long long)n_tgt);
-        return false;
-    }
-    if (n_tgt > 0 && (!zs || !src_len || !src_start || !zt || !tgt_len || !tgt_start)) {
-        set_error("%s: null pointer in a row table (zs=%p src_len=%p src_start=%p zt=%p tgt_len=%p tgt_start=%p)", fn, zs, src_len,
-                  src_start, zt, tgt_len, tgt_start);
-        return false;
-    }
-    return true;
-}
-
-static unsigned grid_for(int64_t n) {
-    const int64_t blocks = (n + kBlock - 1) / kBlock;
-    return (unsigned)(blocks < kGrid ? blocks : kGrid);
-}
-
-static int launched(const char* fn) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("%s: HIP error %d (%s)", fn, (int)e, hipGetErrorString(e));
-        return ATX_EHIP;
-    }
+    ATX_REQUIRE(n_src_rows >= 1 && n_src_rows <= kMax && n_tgt_rows >= 1 && n_tgt_rows <= kMax, ATX_EINVAL,
+                "%s: n_src_rows = %lld, n_tgt_rows = %lld: the number of rows is outside 1 .. 2^31 - 1", fn, (long long)n_src_rows,
+                (long long)n_tgt_rows);
+    ATX_REQUIRE(n_src >= 1 && n_src <= kMax, ATX_EINVAL, "%s: n_src = %lld is outside 1 .. 2^31 - 1", fn, (long long)n_src);
+    ATX_REQUIRE(n_tgt >= 0, ATX_EINVAL, "%s: n_tgt = %lld is negative", fn, (long long)n_tgt);
+    ATX_REQUIRE(n_tgt == 0 || (zs && src_len && src_start && zt && tgt_len && tgt_start), ATX_EINVAL,
+                "%s: null pointer in a row table (zs=%p src_len=%p src_start=%p zt=%p tgt_len=%p tgt_start=%p)", fn, zs, src_len, src_start, zt,
+                tgt_len, tgt_start);
     return ATX_OK;
 }
 
@@ -202,23 +161,22 @@ static int launched(const char* fn) {
 
 extern "C" int atx_plan_version(void) { return ATX_PLAN_VERSION; }
 
-extern "C" const char* atx_plan_last_error(void) { return atx_plan::g_last_error.c_str(); }
+extern "C" const char* atx_plan_last_error(void) { return atx::last_error().c_str(); }
 
 extern "C" int atx_plan_box_average_count(const double* zs, const int64_t* src_len, const int64_t* src_start, int64_t n_src_rows,
                                           int64_t n_src, const double* zt, const int64_t* tgt_len, const int64_t* tgt_start,
                                           int64_t n_tgt_rows, int64_t n_tgt, int64_t* count, void* stream) {
     using namespace atx_plan;
     const char* fn = "atx_plan_box_average_count";
-    if (!check(fn, zs, src_len, src_start, n_src_rows, n_src, zt, tgt_len, tgt_start, n_tgt_rows, n_tgt)) return ATX_EINVAL;
+    const int st = check(fn, zs, src_len, src_start, n_src_rows, n_src, zt, tgt_len, tgt_start, n_tgt_rows, n_tgt);
+    if (st != ATX_OK) return st;
     if (n_tgt == 0) return ATX_OK;
-    if (!count) {
-        set_error("%s: null pointer (count) with n_tgt = %lld", fn, (long long)n_tgt);
-        return ATX_EINVAL;
-    }
+    ATX_REQUIRE(count, ATX_EINVAL, "%s: null pointer (count) with n_tgt = %lld", fn, (long long)n_tgt);
     const RowTable src{zs, src_len, src_start, n_src_rows}, tgt{zt, tgt_len, tgt_start, n_tgt_rows};
-    hipLaunchKernelGGL(box_average_count_kernel, dim3(grid_for(n_tgt)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), src, tgt, n_tgt,
-                       count);
-    return launched(fn);
+    hipLaunchKernelGGL(box_average_count_kernel, dim3(atx::grid_for(n_tgt, kBlock, kGrid)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), src,
+                       tgt, n_tgt, count);
+    ATX_LAUNCH_CHECK(fn);
+    return ATX_OK;
 }
 
 extern "C" int atx_plan_box_average_fill(const double* zs, const int64_t* src_len, const int64_t* src_start, int64_t n_src_rows,
@@ -227,19 +185,15 @@ extern "C" int atx_plan_box_average_fill(const double* zs, const int64_t* src_le
                                          double* data, void* stream) {
     using namespace atx_plan;
     const char* fn = "atx_plan_box_average_fill";
-    if (!check(fn, zs, src_len, src_start, n_src_rows, n_src, zt, tgt_len, tgt_start, n_tgt_rows, n_tgt)) return ATX_EINVAL;
-    if (nnz < 0 || nnz > 2147483647) {
-        set_error("%s: nnz = %lld is outside 0 .. 2^31 - 1", fn, (long long)nnz);
-        return ATX_EINVAL;
-    }
+    const int st = check(fn, zs, src_len, src_start, n_src_rows, n_src, zt, tgt_len, tgt_start, n_tgt_rows, n_tgt);
+    if (st != ATX_OK) return st;
+    ATX_REQUIRE(nnz >= 0 && nnz <= 2147483647, ATX_EINVAL, "%s: nnz = %lld is outside 0 .. 2^31 - 1", fn, (long long)nnz);
     if (n_tgt == 0) return ATX_OK;
-    if (!indptr || (nnz > 0 && (!indices || !data))) {
-        set_error("%s: null pointer (indptr=%p indices=%p data=%p) with n_tgt = %lld, nnz = %lld", fn, (const void*)indptr, (void*)indices,
-                  (void*)data, (long long)n_tgt, (long long)nnz);
-        return ATX_EINVAL;
-    }
+    ATX_REQUIRE(indptr && (nnz == 0 || (indices && data)), ATX_EINVAL, "%s: null pointer (indptr=%p indices=%p data=%p) with n_tgt = %lld, nnz = %lld",
+                fn, (const void*)indptr, (void*)indices, (void*)data, (long long)n_tgt, (long long)nnz);
     const RowTable src{zs, src_len, src_start, n_src_rows}, tgt{zt, tgt_len, tgt_start, n_tgt_rows};
-    hipLaunchKernelGGL(box_average_fill_kernel, dim3(grid_for(n_tgt)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), src, tgt, n_tgt,
-                       indptr, nnz, indices, data);
-    return launched(fn);
+    hipLaunchKernelGGL(box_average_fill_kernel, dim3(atx::grid_for(n_tgt, kBlock, kGrid)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), src,
+                       tgt, n_tgt, indptr, nnz, indices, data);
+    ATX_LAUNCH_CHECK(fn);
+    return ATX_OK;
 }

@@ -23,28 +23,12 @@
 // indices.  A row of `pitch` bytes per lane coalesces when the pitch is small and a multiple of 4: the DWORDS instance (4-byte-aligned
 // base, pitch % 4 == 0) reads the whole dwords of a row as dwords and the last width % 4 bytes singly; the other reads bytes.  Neither
 // reads a byte at or beyond `width`.  No floating point, no LDS, no atomics; plain vector stores.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
-#include <string>
 
 #include "../../../include/atx_text.h"
+#include "../atx_host.hpp"
 
 namespace atx_text {
-
-static thread_local std::string g_last_error;
-
-static void set_error(const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_last_error = buf;
-}
 
 constexpr int kBlock = 256;  // 4 waves: one per SIMD of a CU
 constexpr int kGrid = 2048;  // grid cap, as kRsGrid: beyond 2^19 rows a lane takes further rows
@@ -250,40 +234,24 @@ __global__ __launch_bounds__(kBlock) void text_statids_kernel(const uint8_t* __r
 
 extern "C" int atx_text_version(void) { return ATX_TEXT_VERSION; }
 
-extern "C" const char* atx_text_last_error(void) { return atx_text::g_last_error.c_str(); }
+extern "C" const char* atx_text_last_error(void) { return atx::last_error().c_str(); }
 
 extern "C" int atx_text_encode_statids(const uint8_t* text, int64_t n, int32_t width, int64_t pitch, int64_t* code, uint8_t* undecided,
                                        void* stream) {
     using namespace atx_text;
-    if (n < 0) {
-        set_error("atx_text_encode_statids: n = %lld is negative", (long long)n);
-        return ATX_EINVAL;
-    }
-    if (width < 1 || width > ATX_TEXT_MAX_WIDTH) {
-        set_error("atx_text_encode_statids: width = %d is outside 1 .. %d", (int)width, ATX_TEXT_MAX_WIDTH);
-        return ATX_EINVAL;
-    }
-    if (pitch < width) {
-        set_error("atx_text_encode_statids: pitch = %lld is below width = %d", (long long)pitch, (int)width);
-        return ATX_EINVAL;
-    }
+    ATX_REQUIRE(n >= 0, ATX_EINVAL, "atx_text_encode_statids: n = %lld is negative", (long long)n);
+    ATX_REQUIRE(width >= 1 && width <= ATX_TEXT_MAX_WIDTH, ATX_EINVAL, "atx_text_encode_statids: width = %d is outside 1 .. %d", (int)width,
+                ATX_TEXT_MAX_WIDTH);
+    ATX_REQUIRE(pitch >= width, ATX_EINVAL, "atx_text_encode_statids: pitch = %lld is below width = %d", (long long)pitch, (int)width);
     if (n == 0) return ATX_OK;
-    if (!text || !code || !undecided) {
-        set_error("atx_text_encode_statids: null pointer (text=%p code=%p undecided=%p) with n = %lld", (const void*)text, (void*)code,
-                  (void*)undecided, (long long)n);
-        return ATX_EINVAL;
-    }
-    const int64_t blocks = (n + kBlock - 1) / kBlock;
-    const unsigned grid = (unsigned)(blocks < kGrid ? blocks : kGrid);
+    ATX_REQUIRE(text && code && undecided, ATX_EINVAL, "atx_text_encode_statids: null pointer (text=%p code=%p undecided=%p) with n = %lld",
+                (const void*)text, (void*)code, (void*)undecided, (long long)n);
+    const unsigned grid = atx::grid_for(n, kBlock, kGrid);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if ((reinterpret_cast<uintptr_t>(text) & 3u) == 0 && (pitch & 3) == 0)
         hipLaunchKernelGGL(text_statids_kernel<true>, dim3(grid), dim3(kBlock), 0, s, text, n, (uint32_t)width, pitch, code, undecided);
     else
         hipLaunchKernelGGL(text_statids_kernel<false>, dim3(grid), dim3(kBlock), 0, s, text, n, (uint32_t)width, pitch, code, undecided);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("atx_text_encode_statids: HIP error %d (%s)", (int)e, hipGetErrorString(e));
-        return ATX_EHIP;
-    }
+    ATX_LAUNCH_CHECK("atx_text_encode_statids");
     return ATX_OK;
 }

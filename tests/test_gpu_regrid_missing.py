@@ -108,6 +108,21 @@ def test_csr_rows(kern, T):
         check_case(kern, rs.make_case(T, 0, 5, n_tgt=n_tgt, lengths=some), rs.ALL, 0.5, "tight", "csr")
 
 
+def test_validation_mode_refuses_a_table_that_points_outside_the_stack(dev):
+    """ATX_VALIDATE=1, in a fresh process (tests/regrid_missing_validate_child.py: the variable is read once): the tables are
+    range-checked on the device by the check libatx uses (csrc/atx_regrid_check.hpp) and a launch is refused, with the exact count of
+    bad entries and nothing written, instead of reading outside the stack.  Tables of 7 x 3 = 21 entries (under one wave) and of
+    300 x 4 = 1200 (no multiple of 64 or 256: several waves and a partial last one); per table a bad entry at the first position, at the
+    last and at three positions (three different waves in the long table), -2 under padded rows (-1 is accepted there and refused
+    without), a bad CSR index and an indptr entry above nnz: 7 refusals each.  Valid tables run and equal atx_regrid_ell's bits."""
+    import subprocess
+    import sys
+
+    child = os.path.join(os.path.dirname(os.path.abspath(__file__)), "regrid_missing_validate_child.py")
+    run = subprocess.run([sys.executable, child], capture_output=True, text=True, timeout=120, env=dict(os.environ, ATX_VALIDATE="1"))
+    assert run.returncode == 0 and "refused 14" in run.stdout, run.stdout + run.stderr[-3000:]
+
+
 # ---- GatherPlan ---------------------------------------------------------------------------------------------------------------------
 def plan_case(name, plan: GatherPlan, T, values: np.ndarray) -> rs.MissingCase:
     """The restatement's view of a plan: its natural-order table with the weights rounded to T; ``values`` is [n_lev, n_src]."""

@@ -24,7 +24,9 @@ def kernel_resources(lib: str) -> list[dict]:
     out = []
     with tempfile.TemporaryDirectory() as tmp:
         fat = os.path.join(tmp, "fat.bin")
-        subprocess.run([os.path.join(LLVM, "llvm-objcopy"), f"--dump-section=.hip_fatbin={fat}", lib], check=True, capture_output=True)
+        # with an output file: llvm-objcopy given the input alone rewrites it in place, and `lib` is a library that processes have loaded
+        subprocess.run([os.path.join(LLVM, "llvm-objcopy"), f"--dump-section=.hip_fatbin={fat}", lib, os.path.join(tmp, "copy.so")],
+                       check=True, capture_output=True)
         blob = open(fat, "rb").read()
         starts = [m.start() for m in re.finditer(re.escape(MAGIC), blob)]
         for n, (a, b) in enumerate(zip(starts, starts[1:] + [len(blob)])):
