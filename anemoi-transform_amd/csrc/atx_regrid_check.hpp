@@ -1,5 +1,6 @@
 // The argument checks of the gather entry points, once: the stack check and the ATX_VALIDATE range check of atx_regrid_ell /
-// atx_regrid_csr (atx_regrid.hip) and of atx_regrid_ell_missing / atx_regrid_csr_missing (missing/atx_regrid_missing.hip).  Shared as
+// atx_regrid_csr (atx_regrid.hip), of atx_regrid_ell_missing / atx_regrid_csr_missing (missing/atx_regrid_missing.hip) and of
+// atx_regrid_csr_stat (stat/atx_regrid_stat.hip).  Shared as
 // source: the libraries link nothing of each other, so the kernel has internal linkage and each library carries its own copy.
 #pragma once
 

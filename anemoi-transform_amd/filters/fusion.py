@@ -89,9 +89,11 @@ def flatten(filters: list[Any]) -> list[Any]:
 
 
 def _gather_head(f: Any):
-    """The interpolator of a plain forward ``regrid`` filter, if it runs a GatherPlan.  A regrid with a missing-value policy declines:
-    its kernels take no fused program, so it runs alone and the per-point filters after it fuse among themselves."""
-    if isinstance(f, RegridFilter) and hasattr(f.interpolator, "plan_for") and getattr(f, "missing", None) is None:
+    """The interpolator of a plain forward ``regrid`` filter, if it runs a GatherPlan.  A regrid with a missing-value policy or with a
+    statistic other than the mean declines: its kernels take no fused program, so it runs alone and the per-point filters after it fuse
+    among themselves."""
+    if (isinstance(f, RegridFilter) and hasattr(f.interpolator, "plan_for") and getattr(f, "missing", None) is None
+            and getattr(f, "statistic", None) is None):
         return f
     return None
 

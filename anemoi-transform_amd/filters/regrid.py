@@ -68,8 +68,9 @@ class _Interpolator:
         raise NotImplementedError
 
     def regrid_fieldlist(self, data: Any, *, shard: tuple[int, int] | None = None, missing: str | None = None,
-                         min_valid: float = 0.0) -> FieldList:
-        """``missing`` / ``min_valid``: the missing-value policy of ``GatherPlan.apply`` (``None``: the plain product)."""
+                         min_valid: float = 0.0, statistic: str | None = None) -> FieldList:
+        """``missing`` / ``min_valid``: the missing-value policy of ``GatherPlan.apply`` (``None``: the plain product).  ``statistic``:
+        ``GatherPlan.reduce`` with that statistic and the same policy instead of the weighted mean, one launch per stack."""
         fields = list(data)
         policy = {} if missing is None else dict(missing=missing, min_valid=min_valid)
         out: list[Any] = [None] * len(fields)
@@ -85,7 +86,11 @@ class _Interpolator:
                 plan, lat, lon = self._sharded(plan, shard), lat[lo:hi], lon[lo:hi]
             batches.setdefault(id(plan), (plan, lat, lon, window, []))[4].append(group)
         for plan, lat, lon, window, groups in batches.values():
-            for group, regridded in zip(groups, plan.apply_many([g.stack for g in groups], **policy)):
+            if statistic is None:
+                results = plan.apply_many([g.stack for g in groups], **policy)
+            else:
+                results = [plan.reduce(g.stack, statistic, missing=missing, min_valid=min_valid) for g in groups]
+            for group, regridded in zip(groups, results):
                 for level, (pos, f) in enumerate(zip(group.positions, group.fields)):
                     out[pos] = new_field_from_stack(regridded, level, template=f, latitudes=lat, longitudes=lon, target_range=window)
         return FieldList(out)
@@ -120,6 +125,7 @@ class EarthkitRegrid(_Interpolator):
     ``_fill``, ``include/atx_plan.h``) when there is one, else on the host; the arrays are the same bit for bit — and runs it
     through ``GatherPlan.from_matrix`` like any ``matrix=``: fusion, sharding, ordered traversal and float32 stacks are those of
     the existing routes.  The construction is MIR's grid-box method; parity with MIR is unpinned, and the filter says so once.
+    ``method="grid-box-statistics"`` builds the same matrix, for the filter's ``statistic=`` to take something other than the mean over it.
     ``method="nearest-neighbour"`` (earthkit-regrid's spelling) is the k = 1 search of ``method="nearest"`` between two named
     grids, with the same warning.
 
@@ -132,7 +138,8 @@ class EarthkitRegrid(_Interpolator):
     is unpinned, and the filter says so once.  Every other method / grid raises ``NotImplementedError`` pointing at ``matrix=``.
     """
 
-    METHODS = ("linear", "grid-box-average", "nearest-neighbour", "linear-unstructured")
+    METHODS = ("linear", "grid-box-average", "grid-box-statistics", "nearest-neighbour", "linear-unstructured")
+    BOX_METHODS = ("grid-box-average", "grid-box-statistics")  # the same cells and shares; what is taken over them differs
 
     def __init__(self, *, in_grid: Any, out_grid: Any, method: str = "linear", check: bool = False) -> None:
         from ..grids import row_structure
@@ -150,26 +157,27 @@ class EarthkitRegrid(_Interpolator):
             self._linear_unstructured(in_grid, out_grid)
             return
         rows = row_structure(self.in_grid)
-        out_rows = row_structure(self.out_grid) if method == "grid-box-average" and self.out_grid is not None else None
-        if method not in self.METHODS or rows is None or (method == "grid-box-average" and self.out_grid is not None and out_rows is None):
+        box = method in self.BOX_METHODS
+        out_rows = row_structure(self.out_grid) if box and self.out_grid is not None else None
+        if method not in self.METHODS or rows is None or (box and self.out_grid is not None and out_rows is None):
             raise NotImplementedError(
                 f"regrid(method={method!r}, in_grid={in_grid!r}) needs earthkit-regrid and its remote matrix inventory, which are "
                 "not available here; the in-tree default covers method='linear' from O<N> / F<N> / regular lat-lon source grids. "
                 "Pass a pre-computed `matrix` (anemoi_transform_amd.interp writes the same npz format) or use method='nearest'"
-                + ("; method='grid-box-average' needs BOTH grids to be row-structured formula grids (O<N>, F<N>, N<N>-sized, "
-                   f"regular lat-lon increments), got out_grid={out_grid!r}" if method == "grid-box-average" else "")
+                + (f"; method={method!r} needs BOTH grids to be row-structured formula grids (O<N>, F<N>, N<N>-sized, "
+                   f"regular lat-lon increments), got out_grid={out_grid!r}" if box else "")
             )
         self.out_griddata = as_griddata(out_grid) or {}
         if "latitudes" not in self.out_griddata:
             raise ValueError("out_grid is required, but not provided")
-        if method == "grid-box-average":
+        if box:
             import torch
 
             from ..interp import box_average_rows
 
-            LOG.warning("regrid(method='grid-box-average'): in-tree cell-overlap weights (interp.box_average_rows) stand in for "
+            LOG.warning("regrid(method=%r): in-tree cell-overlap weights (interp.box_average_rows) stand in for "
                         "earthkit-regrid's MIR matrix (remote inventory unavailable); the construction is MIR's grid-box method, "
-                        "parity with MIR is unpinned")
+                        "parity with MIR is unpinned", method)
             matrix = box_average_rows(rows, out_rows, device=torch.cuda.is_available())  # the same arrays either way
         else:
             LOG.warning("regrid(method='linear'): in-tree 4-point bilinear weights stand in for earthkit-regrid's MIR matrix "
@@ -350,12 +358,23 @@ class RegridFilter(Filter):
     the same under every policy.  The statement is in-tree (``include/atx_missing.h``); the policy names are
     MIR's, parity with MIR is unpinned, and the filter says so once.  Such a regrid runs alone: the per-point filters after it in
     a pipeline fuse among themselves.
+
+    ``statistic=`` (extension; MIR's ``grid-box-statistics``) takes something other than the weighted mean of the source cells under a
+    target cell: ``"maximum"``, ``"minimum"``, ``"mode"`` (the class that covers most of the cell, for categorical fields; a tie goes
+    to the smaller value), ``"variance"``, ``"standard-deviation"`` (area-weighted, about the area-weighted mean) — or ``"mean"``,
+    which is ``method="grid-box-average"`` itself, bit for bit, on every route that one takes.  The cells come from
+    ``method="grid-box-statistics"`` between two row-structured grids (the matrix of ``grid-box-average``) or from any ``matrix=``,
+    whose rows are then read as "the source cells of this target and their shares".  ``missing=`` and ``min_valid=`` mean what they
+    mean above (``None``: one NaN source makes the target NaN), and ``shard=`` works.  The statement is in-tree
+    (``include/atx_stat.h``), parity with MIR is unpinned — the tie rule and the policies are this project's — and the filter says so
+    once.  Such a regrid runs alone, as one with ``missing=`` does.
     """
 
+    STATISTICS = ("maximum", "minimum", "mode", "variance", "standard-deviation", "mean")
     MISSING = {None: None, "missing-if-any-missing": None, "missing-if-all-missing": "all", "missing-if-heaviest-missing": "heaviest"}
 
     def __init__(self, *, in_grid=None, out_grid=None, method=None, matrix=None, mask=None, check=False, shard=None, missing=None,
-                 min_valid=0.0) -> None:
+                 min_valid=0.0, statistic=None) -> None:
         self.in_grid = in_grid
         self.out_grid = out_grid
         self.method = method
@@ -366,7 +385,20 @@ class RegridFilter(Filter):
             raise ValueError(f"regrid(min_valid={min_valid!r}): a number in [0, 1]")
         self.missing = self.MISSING[missing]
         self.min_valid = float(min_valid)
-        if self.missing is not None:
+        choices = ", ".join(repr(c) for c in self.STATISTICS)
+        if statistic is not None and not (isinstance(statistic, str) and statistic in self.STATISTICS):
+            raise ValueError(f"regrid(statistic={statistic!r}): one of {choices}")
+        if statistic is None and method == "grid-box-statistics" and matrix is None and mask is None:
+            raise ValueError(f"regrid(method='grid-box-statistics') needs statistic=: one of {choices}")
+        if statistic is not None and (mask is not None or method not in (None, "grid-box-statistics") or (matrix is None and method is None)):
+            raise ValueError(f"regrid(statistic={statistic!r}) goes with method='grid-box-statistics' or with matrix= (not with mask=, "
+                             f"method='nearest' or another method; got method={method!r}); the statistics are {choices}")
+        self.statistic = None if statistic == "mean" else statistic  # the mean is the gather itself
+        if self.statistic is not None:
+            say_once(LOG, "regrid-statistic-parity", "regrid(statistic=%r): taken over the source cells of each target by an in-tree "
+                     "statement (include/atx_stat.h); MIR's grid-box-statistics is the same family, parity with MIR is unpinned (the tie "
+                     "rule and the missing-value policies are this project's)", statistic)
+        if self.missing is not None and self.statistic is None:  # (under a statistic the policy is part of that statement)
             say_once(LOG, "regrid-missing-parity", "regrid(missing=%r): NaN sources are dropped and the remaining weights renormalised by "
                      "an in-tree statement (include/atx_missing.h); the policy names are MIR's, parity with MIR is "
                      "unpinned", missing)
@@ -378,6 +410,9 @@ class RegridFilter(Filter):
         return self._interpolate(data)
 
     def _interpolate(self, data: Any) -> FieldList:
+        if self.statistic is not None:
+            return self.interpolator.regrid_fieldlist(data, shard=self.shard, missing=self.missing, min_valid=self.min_valid,
+                                                      statistic=self.statistic)
         if self.missing is None:
             return self.interpolator.regrid_fieldlist(data, shard=self.shard)
         return self.interpolator.regrid_fieldlist(data, shard=self.shard, missing=self.missing, min_valid=self.min_valid)

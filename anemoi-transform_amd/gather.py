@@ -22,7 +22,7 @@ from typing import Any
 import numpy as np
 import torch
 
-from . import native, native_missing
+from . import native, native_missing, native_stat
 from .stack import COLUMNS, Stack
 
 
@@ -331,6 +331,83 @@ class GatherPlan:
             native_missing.regrid_csr_missing(src.data, out.data, indptr, indices, data, n_src=self.n_src, n_tgt=self.n_tgt, nnz=len(self.indices),
                                       n_lev=src.n_lev, src_pitch=src.pitch, out_pitch=out.pitch, layout=src.layout, policy=missing,
                                       min_valid=min_valid)
+        return out
+
+    # ---- grid-box statistics -----------------------------------------------------------------
+    def _stat_rows(self) -> tuple[np.ndarray, np.ndarray, np.ndarray | None]:
+        """``(indptr, indices, data)`` of this plan's rows as the statistics kernel reads them, made once per plan: a CSR plan as it
+        is; fixed-k rows through ``interp.ell_to_csr``, the absent entries of padded rows dropped; ``data`` is ``None`` for an
+        unweighted plan."""
+        if "_stat_csr" not in self.__dict__:
+            if self.kind == "csr":
+                rows = (self.indptr.astype(np.int32), self.indices, self.data)
+            else:
+                from .interp import ell_to_csr
+
+                weights = np.zeros(self.index.shape) if self.weights is None else self.weights
+                m = ell_to_csr(self.index, weights, self.n_src)
+                indptr, indices, data = m["matrix_indptr"], m["matrix_indices"], m["matrix_data"]
+                present = indices >= 0
+                if not present.all():
+                    lengths = present.reshape(self.n_tgt, self.k).sum(axis=1)
+                    indptr = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)
+                    indices, data = np.ascontiguousarray(indices[present]), np.ascontiguousarray(data[present])
+                rows = (indptr, indices, None if self.weights is None else data)
+            self.__dict__["_stat_csr"] = rows
+        return self.__dict__["_stat_csr"]
+
+    def _stat_tensors(self, device: torch.device, dtype: torch.dtype):
+        """The device copies of ``_stat_rows`` for a stack's type, and whether every weight, rounded to that type, is finite and not
+        negative (the maximum and the minimum then need no weights under ``None`` / ``"all"`` with ``min_valid=0``: include/atx_stat.h)."""
+        cache = self.__dict__.setdefault("_stat_device", {})
+        key = (str(device), dtype)
+        if key not in cache:
+            indptr, indices, data = self._stat_rows()
+            w = None if data is None else data.astype(np.float32 if dtype == torch.float32 else np.float64)
+            plain = w is None or bool((np.isfinite(w) & (w >= 0)).all())
+            cache[key] = (torch.from_numpy(indptr).to(device), torch.from_numpy(indices).to(device),
+                          None if w is None else torch.from_numpy(w).to(device), plain)
+        return cache[key]
+
+    def reduce(self, src: Stack, statistic: str, *, missing: str | None = None, min_valid: float = 0.0, out: Stack | None = None) -> Stack:
+        """A statistic other than the mean of the sources each row names, over every level of ``src`` (``atx_regrid_csr_stat``;
+        ``include/atx_stat.h`` holds the statement): ``"maximum"``, ``"minimum"``, ``"mode"`` (the class with the largest weight; a
+        tie goes to the smaller value), ``"variance"``, ``"standard-deviation"`` (weighted, about the weighted mean).  Returns a new
+        stack on the target points, or ``out``.
+
+        ``missing``: ``None`` — a NaN source makes its target NaN; ``"all"`` — NaN sources are left out, the target is NaN only when
+        every source is; ``"heaviest"`` — also when the (first) heaviest entry of the row is NaN.  ``min_valid`` in [0, 1]: the target
+        is NaN as well when the valid weights sum to less than that share of the row's.  Any plan: fixed-k rows are read as CSR rows
+        (converted once per plan); an unweighted plan has the maximum and the minimum only (``ValueError`` otherwise).  A field-major
+        stack goes through a column stack and back.  A shard of a plan reduces its own targets.  The mean is ``apply``'s."""
+        if statistic == "mean":
+            raise ValueError("statistic='mean' is the weighted gather: use GatherPlan.apply")
+        code = native_stat.statistic_code(statistic)
+        if missing not in native_stat.MISSING_POLICIES:
+            raise ValueError(f"missing={missing!r}: one of None, 'all', 'heaviest'")
+        if not 0.0 <= float(min_valid) <= 1.0:  # (NaN fails both comparisons)
+            raise ValueError(f"min_valid={min_valid!r} is outside [0, 1]")
+        if self.kind == "ell" and self.weights is None and code not in native_stat.UNWEIGHTED:
+            raise ValueError(f"statistic={statistic!r} needs weights: an unweighted plan has 'maximum' and 'minimum' only")
+        assert src.n_pts == self.n_src, (src.n_pts, self.n_src)
+        if out is not None:
+            self._check_out(src, out)
+        if src.layout != COLUMNS:  # the kernel reads column stacks: through them and back, as _apply_missing goes
+            res = self.reduce(src.to_layout(COLUMNS), statistic, missing=missing, min_valid=min_valid).to_layout(src.layout)
+            if out is None:
+                return res
+            out.data.copy_(res.data)
+            return out
+        if out is None:
+            out = src.new_like(n_pts=self.n_tgt, zero=False)
+        if self.n_tgt == 0:
+            return out
+        indptr, indices, data, plain = self._stat_tensors(src.device, src.dtype)
+        if plain and code in native_stat.UNWEIGHTED and missing != "heaviest" and float(min_valid) == 0.0:
+            data = None  # the same bits, and no weight word read
+        native_stat.regrid_csr_stat(src.data, out.data, indptr, indices, data, n_src=self.n_src, n_tgt=self.n_tgt, nnz=int(indices.numel()),
+                                    n_lev=src.n_lev, src_pitch=src.pitch, out_pitch=out.pitch, layout=src.layout, statistic=code,
+                                    policy=missing, min_valid=float(min_valid))
         return out
 
     def apply(self, src: Stack, *, prog: torch.Tensor | None = None, n_stage: int = 0,
