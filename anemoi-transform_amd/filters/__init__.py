@@ -10,6 +10,7 @@ Registered names:
                   r_to_d, d_to_r, q_to_r, r_to_q, q_to_r_height_with_p, r_to_q_height_with_p
                                                              (multi-input, filters/domain.py)
                   rotate_winds, unrotate_winds               (vector frames, filters/winds.py)
+                  ml_to_pl                                   (model levels to pressure levels, filters/vertical.py)
   tabular         irregular_to_grid, assign_to_grid, superob (observation tables onto a grid, filters/tabular.py)
                   add_forcings, add_azimuth, add_msg_angles, radiance_to_brightness_temperature, add_healpix,
                   fill_orography, geopotential_to_height_tabular, apply_column_transformations
@@ -57,6 +58,7 @@ from . import multi as _multi  # noqa: E402
 from . import pointwise as _pointwise  # noqa: E402
 from . import regrid as _regrid  # noqa: E402
 from . import tabular as _tabular_filters  # noqa: E402
+from . import vertical as _vertical  # noqa: E402
 from . import winds as _winds  # noqa: E402
 from .masks import MaskVariable, RemoveNaNs as RemoveNaNsFields
 from .pointwise import Clipper, ImputeNaNs as ImputeNaNsFields, Orography

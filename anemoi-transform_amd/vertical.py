@@ -1,0 +1,48 @@
+"""Vertical interpolation of stacks: model levels to pressure levels (``atx_levels_interpolate``, include/atx_levels.h holds the
+statement).  The layer below the ``ml_to_pl`` filter, next to ``GatherPlan`` in spirit: device stacks in, device stacks out, no host
+round trip — so ``interpolate_levels`` followed by a gather reads 13 levels per variable instead of 137.
+"""
+
+from __future__ import annotations
+
+from typing import Any, Sequence
+
+import numpy as np
+import torch
+
+from . import native_levels
+from .stack import Stack
+
+
+def _device_f64(values: Any, device: torch.device) -> torch.Tensor:
+    if isinstance(values, torch.Tensor):
+        return values.to(device=device, dtype=torch.float64).contiguous()
+    return torch.tensor(np.asarray(values, dtype=np.float64).reshape(-1), dtype=torch.float64, device=device)
+
+
+def interpolate_levels(stack: Stack, sp: torch.Tensor, A: Any, B: Any, targets_pa: Sequence[float], *, n_var: int = 1,
+                       level_index: Sequence[int] | None = None, coordinate: str = "linear", outside: str = "nearest") -> Stack:
+    """``stack`` holds ``n_var`` variables of ``stack.n_lev // n_var`` model levels each, variables adjacent, top level first; the result
+    holds ``n_var x len(targets_pa)`` rows in the same layout and type: row ``v * n_tgt + t`` is variable ``v`` at ``targets_pa[t]`` (Pa, any
+    order).  ``sp`` is the surface pressure of every point (Pa, a device tensor); ``A`` / ``B`` the half-level coefficients (host arrays
+    or device tensors); ``level_index`` the rows' 0-based model levels where the stack holds a subset of the model (strictly increasing).
+    ``coordinate``: ``"linear"`` or ``"log"`` in pressure; ``outside``: ``"nearest"`` or ``"missing"`` above the top full level and below
+    the ground.  One launch."""
+    if n_var < 1 or stack.n_lev % n_var:
+        raise ValueError(f"a stack of {stack.n_lev} rows does not hold {n_var} variables of equally many levels")
+    n_lev = stack.n_lev // n_var
+    coordinate, outside = native_levels.coordinate_code(coordinate), native_levels.outside_code(outside)
+    A, B = _device_f64(A, stack.device), _device_f64(B, stack.device)
+    assert A.shape == B.shape, "A and B coefficients must have same shape"
+    if level_index is None:  # the whole model (R: q_height.py:44-54, the same assertion)
+        assert A.numel() == n_lev + 1, f"model level AB-coefficients should have one more vertical level than the stack's {n_lev}"
+    targets = _device_f64(targets_pa if isinstance(targets_pa, torch.Tensor) else list(targets_pa), stack.device).reshape(-1)
+    sp = sp.reshape(-1)
+    assert sp.numel() == stack.n_pts, (sp.numel(), stack.n_pts)
+    if sp.dtype != stack.dtype or not sp.is_contiguous():
+        sp = sp.to(stack.dtype).contiguous()
+    out = Stack.empty(stack.n_pts, n_var * targets.numel(), stack.dtype, stack.device, stack.layout)
+    native_levels.interpolate(stack.data, out.data, sp, A, B, targets, n_pts=stack.n_pts, n_var=n_var, n_lev=n_lev, n_tgt=targets.numel(),
+                              src_pitch=stack.pitch, out_pitch=out.pitch, layout=stack.layout, level_index=level_index, coordinate=coordinate,
+                              outside=outside)
+    return out
