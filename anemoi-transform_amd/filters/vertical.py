@@ -9,6 +9,10 @@ results are levels of a resident stack: ``ml_to_pl | regrid`` gathers 13 levels 
 The statement (include/atx_levels.h) is in-tree: linear in pressure or in its logarithm between the two full levels that bracket the
 target, the lowest level's value in the half layer above the ground, ``outside`` above the top full level and below the ground.  The
 ``t`` / ``z`` extrapolations of IFS below the ground and height-level targets (which need the geopotential integral) are out of scope.
+
+``geopotential_on_model_levels`` (below) is that integral: ``z`` is not archived on IFS model levels, so it is integrated hydrostatically
+from ``t``, ``q``, the surface pressure and the surface geopotential (``atx_geopotential_on_model_levels``, include/atx_geopotential.h),
+and ``ml_to_pl`` takes it to pressure levels as any other variable.  A height-level filter on top of it is not here yet.
 """
 
 from __future__ import annotations
@@ -23,7 +27,8 @@ from .. import native, native_levels
 from ..core import Filter, filter_registry, say_once
 from ..fields import FieldList, fields_to_stack, new_field_from_stack
 from ..grouping import identity_of
-from ..vertical import interpolate_levels
+from ..stack import Stack
+from ..vertical import geopotential_on_model_levels, interpolate_levels
 from .domain import _one_field, _set_AB
 
 LOG = logging.getLogger(__name__)
@@ -162,4 +167,142 @@ class ModelToPressureLevels(Filter):
                 out, first = outputs[param]
                 for t, level in enumerate(self.levels):
                     result.append(new_field_from_stack(out, first + t, template=templates[param], metadata=dict(levtype="pl", levelist=level)))
+        return FieldList(result)
+
+
+GEOPOTENTIAL_PARITY_NOTE = ("geopotential_on_model_levels: the hydrostatic integral is an in-tree statement (include/atx_geopotential.h) — the IFS "
+                            "discretisation as ECMWF's compute-geopotential-on-model-levels script writes it, with the moist gas constant "
+                            "Rd (1 - q) + Rv q in the place of Rd Tv — and unpinned against earthkit-meteo / MARS")
+
+#: how a COLUMNS stack is served by ``geopotential_on_model_levels``: "columns" (the LDS-tile kernel on the stacks as they are) or "fields"
+#: (relayout, the FIELDS kernel, relayout back).  Set to the route that measured faster (tools/geopotential_bench.py,
+#: profiles/geopotential_bench.json; DESIGN.md §3 "Geopotential kernel"): O1280 x 137 on one MI355X, "columns" 6.81 / 6.72 ms (float32 /
+#: float64), "fields" with its three relayouts 7.60 / 13.16 ms — in float32 a margin of 12 % over a run-to-run spread of 1 %.  The FIELDS
+#: kernel on stacks that already are field-major takes 2.70 / 4.21 ms: fields handed over in that layout stay in it.
+GEOPOTENTIAL_COLUMNS_ROUTE = "columns"
+
+
+@filter_registry.register("geopotential_on_model_levels")
+class GeopotentialOnModelLevels(Filter):
+    """``z`` on model levels from ``t``, ``q``, the surface pressure and the surface geopotential — what MARS holds — so that
+    ``lnsp_to_sp | geopotential_on_model_levels | ml_to_pl`` yields z500 and the rest on the device.  An extension: the reference has no
+    such filter.  ``model_level_AB`` as for ``ml_to_pl``; the other arguments name the ``param`` of each input and of the output.  The
+    ``t`` and ``q`` fields of a group (the fields that share every MARS key but ``param``, ``levelist`` and ``levtype``) must hold the
+    same model levels, without a gap down to the lowest level of the table; the group's one ``surface_pressure`` field and its one
+    ``surface_geopotential`` field (any levtype: MARS keeps it as ``z``, ``ml``, ``levelist=1``) go with them.  Every input passes
+    through, except a field whose ``(param, levtype, levelist)`` an output field takes — in the default spelling the surface ``z``."""
+
+    def __init__(self, *, model_level_AB: Any, temperature: str = "t", specific_humidity: str = "q", surface_pressure: str = "sp",
+                 surface_geopotential: str = "z", output: str = "z") -> None:
+        self.temperature, self.specific_humidity = temperature, specific_humidity
+        self.surface_pressure, self.surface_geopotential, self.output = surface_pressure, surface_geopotential, output
+        if len({temperature, specific_humidity, surface_pressure}) != 3:
+            raise ValueError(f"geopotential_on_model_levels: temperature, specific_humidity and surface_pressure must be three params, got "
+                             f"{temperature!r}, {specific_humidity!r}, {surface_pressure!r}")
+        self.A, self.B = _set_AB(model_level_AB)
+        if self.A.shape != self.B.shape or self.A.ndim != 1 or len(self.A) < 2:
+            raise ValueError(f"geopotential_on_model_levels: A and B must be two lists of the same length (model levels + 1), got {self.A.shape} "
+                             f"and {self.B.shape}")
+        self._device_AB: dict[Any, tuple[torch.Tensor, torch.Tensor]] = {}
+        say_once(LOG, (type(self), "parity"), GEOPOTENTIAL_PARITY_NOTE)
+
+    def __repr__(self) -> str:
+        return f"GeopotentialOnModelLevels({self.temperature!r}, {self.specific_humidity!r} -> {self.output!r})"
+
+    # ---- grouping: host bookkeeping, every ValueError before any launch ------------------------------------------------------------
+    def _plan(self, fields: list[Any]) -> tuple[list[Any], list[dict[str, Any]]]:
+        """``(passed through, [group])`` in first-seen order; a group: ``sp``, ``zs``, ``levels`` (top first) and the ``t`` / ``q`` fields
+        in that order."""
+        name = "geopotential_on_model_levels"
+        n_model = len(self.A) - 1
+        groups: dict[Any, dict[str, Any]] = {}
+        owner: list[tuple[Any, Any, tuple[Any, Any, Any]]] = []  # (field, identity, (param, levtype, levelist)) in input order
+        for field in fields:
+            identity, taken = identity_of(field, ("param", "levelist", "levtype"), ("variable",))
+            group = groups.setdefault(identity, dict(sp=None, zs=None, lnsp=False, t={}, q={}))
+            param = taken["param"]
+            owner.append((field, identity, (param, taken["levtype"], taken["levelist"])))
+            group["lnsp"] = group["lnsp"] or param == "lnsp"
+            if param == self.surface_pressure:
+                if group["sp"] is not None:
+                    raise ValueError(f"Duplicate component {param} for {identity}")
+                group["sp"] = field
+            elif param in (self.temperature, self.specific_humidity) and taken["levtype"] == "ml":
+                try:
+                    level = int(taken["levelist"])
+                except (TypeError, ValueError):
+                    raise ValueError(f"{name}: model-level field {param} has levelist {taken['levelist']!r}") from None
+                members = group["t" if param == self.temperature else "q"]
+                if level in members:
+                    raise ValueError(f"Duplicate component {param} for {identity} and level {level}")
+                if not 1 <= level <= n_model:
+                    raise ValueError(f"{name}: level {level} of {param} is outside the {n_model} model levels of the A / B table")
+                members[level] = field
+            elif param == self.surface_geopotential:  # (after t and q: a surface geopotential never shares their param on ml ... unless it is told to)
+                if group["zs"] is not None:
+                    raise ValueError(f"Duplicate component {param} for {identity}")
+                group["zs"] = field
+        plan = []
+        for identity, group in groups.items():
+            if not group["t"] and not group["q"]:
+                continue
+            for key, param in (("t", self.temperature), ("q", self.specific_humidity)):
+                if not group[key]:
+                    raise ValueError(f"{name}: no model-level fields of {param!r} for {sorted(identity)}")
+            levels, q_levels = sorted(group["t"]), sorted(group["q"])
+            if levels != q_levels:
+                raise ValueError(f"{name}: mixed level sets for {self.temperature} and {self.specific_humidity}: {levels} and {q_levels} "
+                                 f"(in {sorted(identity)})")
+            missing = sorted(set(range(levels[0], n_model + 1)) - set(levels))
+            if missing:
+                raise ValueError(f"{name}: the levels {levels[0]} .. {levels[-1]} of {self.temperature} have a gap down to the lowest level "
+                                 f"{n_model} of the A / B table: missing levels {missing} (in {sorted(identity)})")
+            if group["sp"] is None:
+                hint = (f" (it has lnsp: lnsp_to_sp | {name} is the route, lnsp is not taken in place of the surface pressure)"
+                        if group["lnsp"] else "")
+                raise ValueError(f"{name}: no surface pressure {self.surface_pressure!r} for the model-level fields of {sorted(identity)}{hint}")
+            if group["zs"] is None:
+                raise ValueError(f"{name}: no surface geopotential {self.surface_geopotential!r} for the model-level fields of {sorted(identity)}")
+            plan.append(dict(identity=identity, sp=group["sp"], zs=group["zs"], levels=levels, t=[group["t"][v] for v in levels],
+                             q=[group["q"][v] for v in levels]))
+        taken_by_output = {(g["identity"], (self.output, "ml", level)) for g in plan for level in g["levels"]}
+
+        def replaced(identity: Any, key: tuple[Any, Any, Any]) -> bool:
+            param, levtype, levelist = key
+            try:
+                levelist = int(levelist)
+            except (TypeError, ValueError):
+                return False
+            return (identity, (param, levtype, levelist)) in taken_by_output
+
+        passed = [field for field, identity, key in owner if not replaced(identity, key)]
+        return passed, plan
+
+    def _coefficients(self, device: Any) -> tuple[torch.Tensor, torch.Tensor]:
+        if device not in self._device_AB:
+            self._device_AB[device] = tuple(torch.tensor(np.asarray(c, dtype=np.float64), device=device) for c in (self.A, self.B))
+        return self._device_AB[device]
+
+    def _integrate(self, group: dict[str, Any]) -> Any:
+        """One stack of the group's 2 n + 2 fields (one type: float32 only if every field is), its t and q rows as two views, one launch."""
+        n = len(group["levels"])
+        stack = fields_to_stack([*group["t"], *group["q"], group["sp"], group["zs"]])
+        relayout = stack.layout == native.COLUMNS and GEOPOTENTIAL_COLUMNS_ROUTE == "fields"
+        if relayout:
+            stack = stack.to_layout(native.FIELDS)
+        if stack.layout == native.COLUMNS:
+            rows = lambda a, b: Stack(stack.data[:, a:b], stack.n_pts, b - a, native.COLUMNS)  # noqa: E731
+        else:
+            rows = lambda a, b: Stack(stack.data[a:b], stack.n_pts, b - a, native.FIELDS)  # noqa: E731
+        A, B = self._coefficients(stack.device)
+        out = geopotential_on_model_levels(rows(0, n), rows(n, 2 * n), stack.level_view(2 * n), stack.level_view(2 * n + 1), A, B)
+        return out.to_layout(native.COLUMNS) if relayout else out
+
+    def forward(self, data: Any) -> FieldList:
+        passed, plan = self._plan(list(data))
+        result = list(passed)
+        for group in plan:
+            out = self._integrate(group)
+            for k, level in enumerate(group["levels"]):
+                result.append(new_field_from_stack(out, k, template=group["t"][k], metadata=dict(param=self.output, levtype="ml", levelist=level)))
         return FieldList(result)

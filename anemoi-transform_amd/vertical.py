@@ -1,6 +1,8 @@
 """Vertical interpolation of stacks: model levels to pressure levels (``atx_levels_interpolate``, include/atx_levels.h holds the
 statement).  The layer below the ``ml_to_pl`` filter, next to ``GatherPlan`` in spirit: device stacks in, device stacks out, no host
 round trip — so ``interpolate_levels`` followed by a gather reads 13 levels per variable instead of 137.
+``geopotential_on_model_levels`` (``atx_geopotential_on_model_levels``, include/atx_geopotential.h) integrates ``z`` on model levels from ``t``, ``q``, the surface pressure and the
+surface geopotential: the variable IFS does not archive there, and the one ``interpolate_levels`` is most often asked for.
 """
 
 from __future__ import annotations
@@ -10,7 +12,7 @@ from typing import Any, Sequence
 import numpy as np
 import torch
 
-from . import native_levels
+from . import native_geopotential, native_levels
 from .stack import Stack
 
 
@@ -45,4 +47,34 @@ def interpolate_levels(stack: Stack, sp: torch.Tensor, A: Any, B: Any, targets_p
     native_levels.interpolate(stack.data, out.data, sp, A, B, targets, n_pts=stack.n_pts, n_var=n_var, n_lev=n_lev, n_tgt=targets.numel(),
                               src_pitch=stack.pitch, out_pitch=out.pitch, layout=stack.layout, level_index=level_index, coordinate=coordinate,
                               outside=outside)
+    return out
+
+
+def geopotential_on_model_levels(t: Stack, q: Stack, sp: torch.Tensor, zs: torch.Tensor | None, A: Any, B: Any) -> Stack:
+    """The geopotential (m^2/s^2) on the model levels of ``t`` and ``q`` (``atx_geopotential_on_model_levels``, include/atx_geopotential.h
+    holds the statement): the hydrostatic integral from the ground, which ``interpolate_levels`` then takes to pressure levels as any other
+    variable.  ``t`` / ``q``: two stacks of the same shape, layout and type, top level first, holding the LOWEST ``n_lev`` levels of the
+    ``A`` / ``B`` table (the whole model, or a subset such as levels 60-137 that reaches the ground).  ``sp``: the surface pressure of
+    every point (Pa); ``zs``: the surface geopotential of every point, or ``None`` for 0.0 everywhere; both device tensors.  The result
+    is a stack of ``n_lev`` rows in the layout and type of ``t``.  One launch."""
+    if (t.n_pts, t.n_lev, t.layout) != (q.n_pts, q.n_lev, q.layout):
+        raise ValueError(f"t and q differ in shape or layout: {t!r} and {q!r}")
+    if t.dtype != q.dtype:
+        raise ValueError(f"t and q differ in type: {t.dtype} and {q.dtype}")
+    A, B = _device_f64(A, t.device), _device_f64(B, t.device)
+    assert A.shape == B.shape, "A and B coefficients must have same shape"
+    assert A.numel() >= t.n_lev + 1, f"model level AB-coefficients should have at least one more vertical level than the stack's {t.n_lev}"
+
+    def per_point(values: torch.Tensor, what: str) -> torch.Tensor:
+        values = values.reshape(-1)
+        assert values.numel() == t.n_pts, (what, values.numel(), t.n_pts)
+        if values.dtype != t.dtype or not values.is_contiguous():
+            values = values.to(t.dtype).contiguous()
+        return values
+
+    sp = per_point(sp, "sp")
+    zs = None if zs is None else per_point(zs, "zs")
+    out = Stack.empty(t.n_pts, t.n_lev, t.dtype, t.device, t.layout)
+    native_geopotential.geopotential(t.data, q.data, sp, zs, A, B, out.data, n_pts=t.n_pts, n_lev=t.n_lev, t_pitch=t.pitch, q_pitch=q.pitch,
+                               out_pitch=out.pitch, layout=t.layout)
     return out
