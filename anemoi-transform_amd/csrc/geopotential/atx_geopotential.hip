@@ -6,9 +6,9 @@
 // The other hydrostatic kernel, atx_pressure_at_height_stack (atx_vertical.hip), reduces a column to one pressure and gives every lane its
 // own column in global memory.  Here, as in atx_levels.hip, no lane walks a column in HBM.  ATX_COLUMNS, a 256-lane workgroup per tile
 // of PT consecutive points, four phases:
-//   1. stage   the tile's t columns are one run of PT x t_pitch elements, its q columns one of PT x q_pitch: the lanes copy each into
-//              LDS in order, 16 bytes per lane where that stack allows (decided per stack), single elements otherwise; A and B of the
-//              n_lev + 1 half levels the rows touch go to LDS once per workgroup; one lane per point: sp and zs, float64;
+//   1. stage   the tile's t columns are one run of PT x t_pitch elements, its q columns one of PT x q_pitch: stage_columns copies each
+//              into LDS in order, 16 bytes per lane where that stack allows (decided per stack), single elements otherwise; A and B of
+//              the n_lev + 1 half levels the rows touch go to LDS once per workgroup; one lane per point: sp and zs, float64;
 //   2. terms   one lane per (point, level): p_up, p_dn, r, delta = log(p_dn / p_up), alpha — the logarithm and the two divisions sit
 //              here, 256 lanes wide — and the two products the sum needs, (alpha r) t and (delta r) t, into LDS.  A float64 stack's
 //              terms take the places of the t and q they were made of (the lane that read them writes them); a float32 stack's go to
@@ -19,22 +19,16 @@
 //              float32, against 2.7 ms of the field-major kernel — profiles/geopotential_bench.json has the figures of this one);
 //   4. store   one lane per element of the tile's output, in output order: z = zs + (S[k] + a[k]), rounded once; a point's n_lev values
 //              are one contiguous run.
-// PT is what fits the LDS budget of the launch (geopotential_tile below).  ATX_FIELDS: one lane per point, bottom-up; every level is a
+// PT is what fits the LDS budget of the launch (tile_points over GeoCarve).  ATX_FIELDS: one lane per point, bottom-up; every level is a
 // coalesced load of t, one of q and a coalesced store; A and B are uniform.  Both layouts and both load routes evaluate the same
 // float64 statements in the same order: same bits.  No scratch (profiles/geopotential_resources.json).
-//
-// (round16, the tile search and the LDS budgets are copies of atx_levels.hip's: that file is not edited.)
 #include "../../../include/atx_geopotential.h"
-#include "../atx_common.hpp"
+#include "../atx_column_tile.hpp"
 
 namespace atx {
 
-constexpr int kGeoBlock = 256;                      // lanes per workgroup
 constexpr int kGeoMaxLevels = ATX_GEOPOTENTIAL_MAX_LEVELS;
-constexpr int kGeoMaxTile = 256;                    // points per tile at most: one lane per point in the sum phase
 constexpr int kGeoBatch = 8;                        // LDS reads of the sum phase in flight ahead of the dependent adds
-constexpr int64_t kGeoLdsPreferred = 32 * 1024;     // five workgroups share the 160 KiB of a CU: their sum phases hide behind the others' loads
-constexpr int64_t kGeoLdsLimit = 64 * 1024;         // what one workgroup may ask for
 constexpr double kGeoRd = 287.0597, kGeoRv = 461.5250;  // J / (kg K), as in atx_vertical.hip
 constexpr double kGeoLn2 = 0.6931471805599453;      // alpha of the IFS top level
 
@@ -63,8 +57,6 @@ __device__ __forceinline__ GeoTerms geo_terms(int j, double p_up, double p_dn, d
     return g;
 }
 
-__host__ __device__ inline int64_t geo_round16(int64_t bytes) { return (bytes + 15) / 16 * 16; }
-
 // Where the LDS of a tile of `pt` points holds what (byte offsets, multiples of 16): one definition for the launch and the kernel.
 // The staged t columns start at 0.  INPLACE (float64): the terms live in the staged columns, ta == 0 and td == q.
 struct GeoCarve {
@@ -73,59 +65,28 @@ struct GeoCarve {
 };
 __host__ __device__ inline GeoCarve geo_carve(int64_t pt, int lt, int lq, int elem, int n_lev) {
     GeoCarve c;
-    c.q = geo_round16(pt * lt * elem);            // T [pt][lq]
-    int64_t end = c.q + geo_round16(pt * lq * elem);
+    c.q = round16(pt * lt * elem);                 // T [pt][lq]
+    int64_t end = c.q + round16(pt * lq * elem);
     if (elem == 8) {
         c.ta = 0, c.td = c.q, c.pa = lt, c.pd = lq;
     } else {
         c.pa = c.pd = n_lev | 1;                   // odd: the points of the sum phase fall into different banks
         c.ta = end;                                // double [pt][pa]
-        c.td = c.ta + geo_round16(pt * c.pa * 8);  // double [pt][pd]
-        end = c.td + geo_round16(pt * c.pd * 8);
+        c.td = c.ta + round16(pt * c.pa * 8);      // double [pt][pd]
+        end = c.td + round16(pt * c.pd * 8);
     }
     c.sps = end;                                   // double [pt]
-    c.zss = c.sps + geo_round16(pt * 8);           // double [pt]
-    c.coef = c.zss + geo_round16(pt * 8);          // double [2][n_lev + 1]
-    c.total = c.coef + geo_round16((int64_t)2 * (n_lev + 1) * 8);
+    c.zss = c.sps + round16(pt * 8);               // double [pt]
+    c.coef = c.zss + round16(pt * 8);              // double [2][n_lev + 1]
+    c.total = c.coef + round16((int64_t)2 * (n_lev + 1) * 8);
     return c;
 }
 
 // ---- ATX_COLUMNS ---------------------------------------------------------------------------------------------------------------------
 // VT, VQ: elements per load of the staging phase of t and of q (Vec16<T>::N, or 1 for an odd pitch or an unaligned base); lt, lq:
 // elements between the columns of two points in LDS (a multiple of the stack's vector that covers n_lev).
-// Item i = tid, tid + kGeoBlock, ... of a [rows][width] tile as (row, col) = (i / width, i % width): ONE division per lane and loop,
-// then steps of (kGeoBlock / width, kGeoBlock % width) with a carry — a division per item cost as much as a third of a logarithm.
-struct GeoWalk {
-    int row, col, width, step_row, step_col;
-    __device__ __forceinline__ GeoWalk(int tid, int w) : width(w) {
-        row = tid / w;
-        col = tid - row * w;
-        step_row = kGeoBlock / w;
-        step_col = kGeoBlock - step_row * w;
-    }
-    __device__ __forceinline__ void next() {
-        row += step_row;
-        col += step_col;
-        if (col >= width) {
-            col -= width;
-            ++row;
-        }
-    }
-};
-
-template <typename T, int V>
-__device__ __forceinline__ void geo_stage(const T* __restrict__ src, T* __restrict__ xs, int64_t p0, int npt, int64_t pitch, int lds_pitch, int tid) {
-    const int C = lds_pitch / V;
-    GeoWalk w(tid, C);
-    for (int i = tid; i < npt * C; i += kGeoBlock, w.next()) {
-        const int pt = w.row, c = w.col;
-        const Pack<T, V> v = pw_load_nt<T, V>(src + (p0 + pt) * pitch + (int64_t)c * V);
-        *reinterpret_cast<Pack<T, V>*>(xs + (int64_t)pt * lds_pitch + c * V) = v;
-    }
-}
-
 template <typename T, int VT, int VQ>
-__global__ void __launch_bounds__(kGeoBlock)
+__global__ void __launch_bounds__(kTileBlock)
 geopotential_columns_kernel(const T* __restrict__ t, const T* __restrict__ q, const T* __restrict__ sp, const T* __restrict__ zs,
                             const double* __restrict__ A, const double* __restrict__ B, T* __restrict__ out, int64_t n_pts, int n_lev, int first,
                             int64_t t_pitch, int64_t q_pitch, int64_t out_pitch, int PT, int lt, int lq) {
@@ -146,23 +107,23 @@ geopotential_columns_kernel(const T* __restrict__ t, const T* __restrict__ q, co
     const int npt = (int)(n_pts - p0 < PT ? n_pts - p0 : PT);
 
     // 1. stage
-    geo_stage<T, VT>(t, ts, p0, npt, t_pitch, lt, tid);
-    geo_stage<T, VQ>(q, qs, p0, npt, q_pitch, lq, tid);
-    for (int k = tid; k <= n_lev; k += kGeoBlock) {
+    stage_columns<T, VT>(t, ts, p0, npt, t_pitch, lt, tid);
+    stage_columns<T, VQ>(q, qs, p0, npt, q_pitch, lq, tid);
+    for (int k = tid; k <= n_lev; k += kTileBlock) {
         cA[k] = A[first + k];
         cB[k] = B[first + k];
     }
-    for (int pt = tid; pt < npt; pt += kGeoBlock) {
+    for (int pt = tid; pt < npt; pt += kTileBlock) {
         sps[pt] = (double)sp[p0 + pt];
         zss[pt] = zs ? (double)zs[p0 + pt] : 0.0;
     }
     __syncthreads();
     // 2. terms
-    GeoWalk terms(tid, n_lev);
-    for (int i = tid; i < npt * n_lev; i += kGeoBlock, terms.next()) {
+    TileWalk terms(tid, n_lev);
+    for (int i = tid; i < npt * n_lev; i += kTileBlock, terms.next()) {
         const int pt = terms.row, k = terms.col;
         const double s = sps[pt];
-        const double p_up = cA[k] + cB[k] * s, p_dn = cA[k + 1] + cB[k + 1] * s;
+        const double p_up = half_level(cA, cB, k, s), p_dn = half_level(cA, cB, k + 1, s);
         const double tk = (double)ts[pt * lt + k], qk = (double)qs[pt * lq + k];
         const GeoTerms g = geo_terms(first + k, p_up, p_dn, tk, qk);
         ta[pt * pa + k] = g.a;  // (float64: the places of tk and qk, which only this lane reads)
@@ -170,7 +131,7 @@ geopotential_columns_kernel(const T* __restrict__ t, const T* __restrict__ q, co
     }
     __syncthreads();
     // 3. sum
-    for (int pt = tid; pt < npt; pt += kGeoBlock) {
+    for (int pt = tid; pt < npt; pt += kTileBlock) {
         double* d = td + pt * pd;
         double S = 0.0;
         int k = n_lev - 1;
@@ -195,8 +156,8 @@ geopotential_columns_kernel(const T* __restrict__ t, const T* __restrict__ q, co
     }
     __syncthreads();
     // 4. store
-    GeoWalk store(tid, n_lev);
-    for (int i = tid; i < npt * n_lev; i += kGeoBlock, store.next()) {
+    TileWalk store(tid, n_lev);
+    for (int i = tid; i < npt * n_lev; i += kTileBlock, store.next()) {
         const int pt = store.row, k = store.col;
         const double lower = td[pt * pd + k] + ta[pt * pa + k];
         out[(p0 + pt) * out_pitch + k] = (T)(zss[pt] + lower);
@@ -205,18 +166,18 @@ geopotential_columns_kernel(const T* __restrict__ t, const T* __restrict__ q, co
 
 // ---- ATX_FIELDS ----------------------------------------------------------------------------------------------------------------------
 template <typename T>
-__global__ void __launch_bounds__(kGeoBlock)
+__global__ void __launch_bounds__(kTileBlock)
 geopotential_fields_kernel(const T* __restrict__ t, const T* __restrict__ q, const T* __restrict__ sp, const T* __restrict__ zs,
                            const double* __restrict__ A, const double* __restrict__ B, T* __restrict__ out, int64_t n_pts, int n_lev, int first,
                            int64_t t_pitch, int64_t q_pitch, int64_t out_pitch) {
-    const int64_t p = (int64_t)blockIdx.x * kGeoBlock + threadIdx.x;
+    const int64_t p = (int64_t)blockIdx.x * kTileBlock + threadIdx.x;
     if (p >= n_pts) return;
     const double s = (double)sp[p];
     const double z0 = zs ? (double)zs[p] : 0.0;
     double S = 0.0;
     for (int k = n_lev - 1; k >= 0; --k) {  // (k is uniform: scalar loads of A, B)
         const int j = first + k;
-        const double p_up = A[j] + B[j] * s, p_dn = A[j + 1] + B[j + 1] * s;
+        const double p_up = half_level(A, B, j, s), p_dn = half_level(A, B, j + 1, s);
         const GeoTerms g = geo_terms(j, p_up, p_dn, (double)t[(int64_t)k * t_pitch + p], (double)q[(int64_t)k * q_pitch + p]);
         const double lower = S + g.a;
         out[(int64_t)k * out_pitch + p] = (T)(z0 + lower);
@@ -225,17 +186,6 @@ geopotential_fields_kernel(const T* __restrict__ t, const T* __restrict__ q, con
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------------
-// The points of a tile: as many as the preferred LDS budget holds (at most kGeoMaxTile), one at least if the limit holds it; 0: none.
-static int geopotential_tile(int lt, int lq, int elem, int n_lev) {
-    for (const int64_t budget : {kGeoLdsPreferred, kGeoLdsLimit}) {
-        int pt = 0;
-        for (int step = kGeoMaxTile; step > 0; step /= 2)  // the largest pt <= kGeoMaxTile that fits: the bytes grow with pt
-            if (pt + step <= kGeoMaxTile && geo_carve(pt + step, lt, lq, elem, n_lev).total <= budget) pt += step;
-        if (pt > 0) return pt;
-    }
-    return 0;
-}
-
 template <typename T>
 static int geopotential_typed(const void* t_, const void* q_, const void* sp_, const void* zs_, const double* A, const double* B, void* out_,
                               int64_t n_pts, int n_lev, int first, int64_t tp, int64_t qp, int64_t op, int layout, hipStream_t st) {
@@ -246,36 +196,28 @@ static int geopotential_typed(const void* t_, const void* q_, const void* sp_, c
     const T* zs = static_cast<const T*>(zs_);
     T* out = static_cast<T*>(out_);
     if (layout == ATX_FIELDS) {
-        const dim3 grid((unsigned)((n_pts + kGeoBlock - 1) / kGeoBlock));
-        hipLaunchKernelGGL((geopotential_fields_kernel<T>), grid, dim3(kGeoBlock), 0, st, t, q, sp, zs, A, B, out, n_pts, n_lev, first, tp, qp, op);
+        const dim3 grid((unsigned)((n_pts + kTileBlock - 1) / kTileBlock));
+        hipLaunchKernelGGL((geopotential_fields_kernel<T>), grid, dim3(kTileBlock), 0, st, t, q, sp, zs, A, B, out, n_pts, n_lev, first, tp, qp, op);
         ATX_LAUNCH_CHECK("geopotential_fields");
         return ATX_OK;
     }
     constexpr int VEC = Vec16<T>::N;
-    const int covered = (n_lev + VEC - 1) / VEC * VEC;
-    const bool vt = aligned16(t_) && tp % VEC == 0 && covered <= tp;  // the last vector of a column inside the pitch
-    const bool vq = aligned16(q_) && qp % VEC == 0 && covered <= qp;
-    const int lt = vt ? covered : n_lev, lq = vq ? covered : n_lev;
-    const int PT = geopotential_tile(lt, lq, (int)sizeof(T), n_lev);
-    ATX_REQUIRE(PT > 0, ATX_ENOTIMPL, "%s: one point's %d levels need %lld bytes of LDS, a workgroup has %lld", fn, n_lev,
-                (long long)geo_carve(1, lt, lq, (int)sizeof(T), n_lev).total, (long long)kGeoLdsLimit);
+    const ColumnRoute rt = column_route<VEC>(t_, tp, n_lev), rq = column_route<VEC>(q_, qp, n_lev);
+    const int lt = rt.lds_pitch, lq = rq.lds_pitch;
+    auto bytes = [&](int64_t pt) { return geo_carve(pt, lt, lq, (int)sizeof(T), n_lev).total; };
+    const int PT = tile_points(bytes);
+    ATX_REQUIRE(PT > 0, ATX_ENOTIMPL, "%s: one point's %d levels need %lld bytes of LDS, a workgroup has %lld", fn, n_lev, (long long)bytes(1),
+                (long long)kTileLdsLimit);
     const int64_t tiles = (n_pts + PT - 1) / PT;
-    const size_t lds = (size_t)geo_carve(PT, lt, lq, (int)sizeof(T), n_lev).total;
-    auto launch = [&](auto vec_t, auto vec_q) {
-        hipLaunchKernelGGL((geopotential_columns_kernel<T, decltype(vec_t)::value, decltype(vec_q)::value>), dim3((unsigned)tiles), dim3(kGeoBlock), lds,
-                           st, t, q, sp, zs, A, B, out, n_pts, n_lev, first, tp, qp, op, PT, lt, lq);
-        return 0;
-    };
-    using Vector = std::integral_constant<int, VEC>;
-    using Single = std::integral_constant<int, 1>;
-    if (vt && vq)
-        launch(Vector{}, Vector{});
-    else if (vt)
-        launch(Vector{}, Single{});
-    else if (vq)
-        launch(Single{}, Vector{});
-    else
-        launch(Single{}, Single{});
+    const size_t lds = (size_t)bytes(PT);
+    with_flag(rt.vector, [&](auto vec_t) {
+        return with_flag(rq.vector, [&](auto vec_q) {
+            constexpr int VT = decltype(vec_t)::value ? VEC : 1, VQ = decltype(vec_q)::value ? VEC : 1;
+            hipLaunchKernelGGL((geopotential_columns_kernel<T, VT, VQ>), dim3((unsigned)tiles), dim3(kTileBlock), lds, st, t, q, sp, zs, A, B, out,
+                               n_pts, n_lev, first, tp, qp, op, PT, lt, lq);
+            return 0;
+        });
+    });
     ATX_LAUNCH_CHECK("geopotential_columns");
     return ATX_OK;
 }

@@ -4,9 +4,9 @@
 // The one other vertical kernel, atx_pressure_at_height_stack (atx_vertical.hip), gives every lane its own column: in ATX_COLUMNS each
 // of its load instructions touches 64 lines, one per column, and it runs at a tenth of the HBM peak.  Here a column is never walked by
 // a lane.  ATX_COLUMNS, a 256-lane workgroup per tile of PT consecutive points, four phases:
-//   1. stage     the tile's columns are one run of PT x src_pitch elements: the lanes copy it into LDS in order, 16 bytes per lane
-//                where the stack allows (a wave's load covers 1 KiB of consecutive addresses), single elements otherwise (256 B);
-//                the four coefficients of every row (A, B at m[k] and m[k] + 1) go to LDS once per workgroup;
+//   1. stage     the tile's columns are one run of PT x src_pitch elements: stage_columns (atx_column_tile.hpp) copies it into LDS
+//                in order, 16 bytes per lane where the stack allows (a wave's load covers 1 KiB of consecutive addresses), single
+//                elements otherwise (256 B); the four coefficients of every row (A, B at m[k], m[k] + 1): to LDS once per workgroup;
 //   2. pressures one lane per (point, level): p_full into LDS, float64 — and the level below it once more, to learn whether the
 //                point's p_full never decreases; one lane per point: p_ground and sp;
 //   3. brackets  one lane per (point, target): the count over the point's p_full — where it never decreases (and so holds no NaN) the
@@ -15,21 +15,17 @@
 //                for all n_var variables;
 //   4. apply     one lane per element of the tile's output, in output order: two LDS reads, y = x[a] + w (x[b] - x[a]), one store; a
 //                point's n_var x n_tgt outputs are one contiguous run, the tile's runs follow each other at out_pitch.
-// PT is what fits the LDS budget of the launch (levels_tile below).  ATX_FIELDS: one lane per (point, target), the 64 points of a wave
+// PT is what fits the LDS budget of the launch (tile_points over LevelsCarve).  ATX_FIELDS: one lane per (point, target), the 64 points of a wave
 // consecutive: p_full is recomputed level by level from A, B (uniform) and sp, then 2 x n_var loads that coalesce where neighbouring
 // points share a bracket, and n_var coalesced stores.  Both layouts evaluate the same float64 statements in the same order: same bits.
 // The level map m[k] travels by value in the kernel arguments (ATX_LEVELS_MAX_LEVELS 16-bit entries): the host has checked it.
 // No scratch (profiles/levels_resources.json).
 #include "../../../include/atx_levels.h"
-#include "../atx_common.hpp"
+#include "../atx_column_tile.hpp"
 
 namespace atx {
 
-constexpr int kLevBlock = 256;                      // lanes per workgroup
 constexpr int kLevMaxLevels = ATX_LEVELS_MAX_LEVELS;
-constexpr int kLevMaxTile = 256;                    // points per tile at most: one lane per point in the smallest shapes
-constexpr int64_t kLevLdsPreferred = 32 * 1024;     // five workgroups share the 160 KiB of a CU
-constexpr int64_t kLevLdsLimit = 64 * 1024;         // what one workgroup may ask for
 
 struct LevelMap {
     uint16_t m[kLevMaxLevels];  // m[k]: the 0-based model level of row k
@@ -76,13 +72,6 @@ __device__ __forceinline__ T interpolate(const Bracket& r, T xa, T xb) {
     return (T)(a + s);
 }
 
-__device__ __forceinline__ double full_level(const double* __restrict__ A, const double* __restrict__ B, int j, double sp) {
-    const double lo = A[j] + B[j] * sp, hi = A[j + 1] + B[j + 1] * sp;
-    return (lo + hi) / 2.0;
-}
-
-__host__ __device__ inline int64_t round16(int64_t bytes) { return (bytes + 15) / 16 * 16; }
-
 // Where the LDS of a tile of `pt` points holds what (byte offsets, multiples of 16): one definition for the launch and the kernel.
 struct LevelsCarve {
     int64_t pf, sps, pg, bw, ba, bb, mono, coef, total;  // (the staged columns start at 0)
@@ -105,7 +94,7 @@ __host__ __device__ inline LevelsCarve levels_carve(int64_t pt, int lds_pitch, i
 // VEC: elements per load of the staging phase (Vec16<T>::N, or 1 for an odd pitch or an unaligned base); lds_pitch: elements between
 // the columns of two points in LDS (a multiple of VEC that covers n_var * n_lev).
 template <typename T, int VEC, bool LOG>
-__global__ void __launch_bounds__(kLevBlock)
+__global__ void __launch_bounds__(kTileBlock)
 levels_columns_kernel(const T* __restrict__ src, T* __restrict__ out, const T* __restrict__ sp, const double* __restrict__ A,
                       const double* __restrict__ B, const double* __restrict__ targets, const LevelMap map, int64_t n_pts, int n_var, int n_lev,
                       int n_tgt, int n_half, int64_t src_pitch, int64_t out_pitch, int PT, int lds_pitch, int outside) {
@@ -129,23 +118,18 @@ levels_columns_kernel(const T* __restrict__ src, T* __restrict__ out, const T* _
     const int npt = (int)(n_pts - p0 < PT ? n_pts - p0 : PT);
 
     // 1. stage
-    const int C = lds_pitch / VEC;
-    for (int i = tid; i < npt * C; i += kLevBlock) {
-        const int pt = i / C, c = i - pt * C;
-        const Pack<T, VEC> v = pw_load_nt<T, VEC>(src + (p0 + pt) * src_pitch + (int64_t)c * VEC);
-        *reinterpret_cast<Pack<T, VEC>*>(xs + (int64_t)pt * lds_pitch + c * VEC) = v;
-    }
-    for (int k = tid; k < n_lev; k += kLevBlock) {
+    stage_columns<T, VEC>(src, xs, p0, npt, src_pitch, lds_pitch, tid);
+    for (int k = tid; k < n_lev; k += kTileBlock) {
         const int j = map.m[k];
         cA0[k] = A[j];
         cA1[k] = A[j + 1];
         cB0[k] = B[j];
         cB1[k] = B[j + 1];
     }
-    for (int pt = tid; pt < npt; pt += kLevBlock) mono[pt] = 1;
+    for (int pt = tid; pt < npt; pt += kTileBlock) mono[pt] = 1;
     __syncthreads();
     // 2. pressures (full_level's statements on the staged coefficients)
-    for (int i = tid; i < npt * n_lev; i += kLevBlock) {
+    for (int i = tid; i < npt * n_lev; i += kTileBlock) {
         const int pt = i / n_lev, k = i - pt * n_lev;
         const double s = (double)sp[p0 + pt];
         const double lo = cA0[k] + cB0[k] * s, hi = cA1[k] + cB1[k] * s;
@@ -157,14 +141,14 @@ levels_columns_kernel(const T* __restrict__ src, T* __restrict__ out, const T* _
             if (!(here <= below)) mono[pt] = 0;  // (a NaN fails too; every lane that writes, writes 0)
         }
     }
-    for (int pt = tid; pt < npt; pt += kLevBlock) {
+    for (int pt = tid; pt < npt; pt += kTileBlock) {
         const double s = (double)sp[p0 + pt];
         sps[pt] = s;
-        pg[pt] = A[n_half - 1] + B[n_half - 1] * s;
+        pg[pt] = half_level(A, B, n_half - 1, s);
     }
     __syncthreads();
     // 3. brackets
-    for (int i = tid; i < npt * n_tgt; i += kLevBlock) {
+    for (int i = tid; i < npt * n_tgt; i += kTileBlock) {
         const int pt = i / n_tgt, t = i - pt * n_tgt;
         const double P = targets[t];
         const double* col = pf + pt * n_lev;
@@ -189,7 +173,7 @@ levels_columns_kernel(const T* __restrict__ src, T* __restrict__ out, const T* _
     __syncthreads();
     // 4. apply
     const int per_point = n_var * n_tgt;
-    for (int i = tid; i < npt * per_point; i += kLevBlock) {
+    for (int i = tid; i < npt * per_point; i += kTileBlock) {
         const int pt = i / per_point, j = i - pt * per_point;
         const int v = j / n_tgt, t = j - v * n_tgt;
         Bracket r;
@@ -204,18 +188,18 @@ levels_columns_kernel(const T* __restrict__ src, T* __restrict__ out, const T* _
 
 // ---- ATX_FIELDS ----------------------------------------------------------------------------------------------------------------------
 template <typename T, bool LOG>
-__global__ void __launch_bounds__(kLevBlock)
+__global__ void __launch_bounds__(kTileBlock)
 levels_fields_kernel(const T* __restrict__ src, T* __restrict__ out, const T* __restrict__ sp, const double* __restrict__ A,
                      const double* __restrict__ B, const double* __restrict__ targets, const LevelMap map, int64_t n_pts, int n_var, int n_lev,
                      int n_tgt, int n_half, int64_t src_pitch, int64_t out_pitch, int outside) {
-    const int64_t p = (int64_t)blockIdx.x * kLevBlock + threadIdx.x;
+    const int64_t p = (int64_t)blockIdx.x * kTileBlock + threadIdx.x;
     if (p >= n_pts) return;
     const int t = blockIdx.y;
     const double s = (double)sp[p];
     const double P = targets[t];
     int count = 0;
     for (int k = 0; k < n_lev; ++k) count += full_level(A, B, map.m[k], s) <= P ? 1 : 0;  // (k is uniform: scalar loads of m, A, B)
-    const double p_ground = A[n_half - 1] + B[n_half - 1] * s;
+    const double p_ground = half_level(A, B, n_half - 1, s);
     const Bracket r = make_bracket<LOG>(count, n_lev, P, s, p_ground, outside, [&](int k) { return full_level(A, B, map.m[k], s); });
     const int a = r.a < 0 ? 0 : r.a, b = r.b < 0 ? 0 : r.b;
     for (int v = 0; v < n_var; ++v) {
@@ -225,20 +209,6 @@ levels_fields_kernel(const T* __restrict__ src, T* __restrict__ out, const T* __
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------------
-// LDS bytes of a tile of `pt` points.
-static int64_t levels_lds_bytes(int64_t pt, int lds_pitch, int elem, int n_lev, int n_tgt) { return levels_carve(pt, lds_pitch, elem, n_lev, n_tgt).total; }
-
-// The points of a tile: as many as the preferred LDS budget holds (at most kLevMaxTile), one at least if the limit holds it; 0: none.
-static int levels_tile(int lds_pitch, int elem, int n_lev, int n_tgt) {
-    for (const int64_t budget : {kLevLdsPreferred, kLevLdsLimit}) {
-        int pt = 0;
-        for (int step = kLevMaxTile; step > 0; step /= 2)  // the largest pt <= kLevMaxTile that fits: the bytes grow with pt
-            if (pt + step <= kLevMaxTile && levels_lds_bytes(pt + step, lds_pitch, elem, n_lev, n_tgt) <= budget) pt += step;
-        if (pt > 0) return pt;
-    }
-    return 0;
-}
-
 template <typename T>
 static int levels_typed(const void* src_, void* out_, const void* sp_, const double* A, const double* B, const LevelMap& map, const double* targets,
                         int64_t n_pts, int n_var, int n_lev, int n_tgt, int n_half, int64_t sp, int64_t op, int layout, int coordinate, int outside,
@@ -249,9 +219,9 @@ static int levels_typed(const void* src_, void* out_, const void* sp_, const dou
     const T* sfc = static_cast<const T*>(sp_);
     const bool log = coordinate == ATX_LEVELS_LOG;
     if (layout == ATX_FIELDS) {
-        const dim3 grid((unsigned)((n_pts + kLevBlock - 1) / kLevBlock), (unsigned)n_tgt);
+        const dim3 grid((unsigned)((n_pts + kTileBlock - 1) / kTileBlock), (unsigned)n_tgt);
         with_flag(log, [&](auto flag) {
-            hipLaunchKernelGGL((levels_fields_kernel<T, decltype(flag)::value>), grid, dim3(kLevBlock), 0, st, src, out, sfc, A, B, targets, map, n_pts,
+            hipLaunchKernelGGL((levels_fields_kernel<T, decltype(flag)::value>), grid, dim3(kTileBlock), 0, st, src, out, sfc, A, B, targets, map, n_pts,
                                n_var, n_lev, n_tgt, n_half, sp, op, outside);
             return 0;
         });
@@ -260,20 +230,19 @@ static int levels_typed(const void* src_, void* out_, const void* sp_, const dou
     }
     constexpr int VEC = Vec16<T>::N;
     const int rows = n_var * n_lev;
-    const int covered = (rows + VEC - 1) / VEC * VEC;
-    const bool vector = aligned16(src_) && sp % VEC == 0 && covered <= sp;
-    const int lds_pitch = vector ? covered : rows;
-    const int PT = levels_tile(lds_pitch, (int)sizeof(T), n_lev, n_tgt);
+    const ColumnRoute route = column_route<VEC>(src_, sp, rows);
+    auto bytes = [&](int64_t pt) { return levels_carve(pt, route.lds_pitch, (int)sizeof(T), n_lev, n_tgt).total; };
+    const int PT = tile_points(bytes);
     ATX_REQUIRE(PT > 0, ATX_ENOTIMPL, "%s: one point's %d rows, %d levels and %d targets need %lld bytes of LDS, a workgroup has %lld (split the variables)",
-                fn, rows, n_lev, n_tgt, (long long)levels_lds_bytes(1, lds_pitch, (int)sizeof(T), n_lev, n_tgt), (long long)kLevLdsLimit);
+                fn, rows, n_lev, n_tgt, (long long)bytes(1), (long long)kTileLdsLimit);
     const int64_t tiles = (n_pts + PT - 1) / PT;
-    const size_t lds = (size_t)levels_lds_bytes(PT, lds_pitch, (int)sizeof(T), n_lev, n_tgt);
+    const size_t lds = (size_t)bytes(PT);
     auto launch = [&](auto vec, auto flag) {
-        hipLaunchKernelGGL((levels_columns_kernel<T, decltype(vec)::value, decltype(flag)::value>), dim3((unsigned)tiles), dim3(kLevBlock), lds, st, src, out,
-                           sfc, A, B, targets, map, n_pts, n_var, n_lev, n_tgt, n_half, sp, op, PT, lds_pitch, outside);
+        hipLaunchKernelGGL((levels_columns_kernel<T, decltype(vec)::value, decltype(flag)::value>), dim3((unsigned)tiles), dim3(kTileBlock), lds, st, src, out,
+                           sfc, A, B, targets, map, n_pts, n_var, n_lev, n_tgt, n_half, sp, op, PT, route.lds_pitch, outside);
         return 0;
     };
-    with_flag(log, [&](auto flag) { return vector ? launch(std::integral_constant<int, VEC>{}, flag) : launch(std::integral_constant<int, 1>{}, flag); });
+    with_flag(log, [&](auto flag) { return route.vector ? launch(std::integral_constant<int, VEC>{}, flag) : launch(std::integral_constant<int, 1>{}, flag); });
     ATX_LAUNCH_CHECK("levels_columns");
     return ATX_OK;
 }

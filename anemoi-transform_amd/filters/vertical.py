@@ -50,8 +50,36 @@ def _level_key(level: Any) -> Any:
     return int(value) if value == int(value) else value
 
 
+class _HybridLevelFilter(Filter):
+    """What the filters on hybrid model-level columns share; ``name`` is the registered name, which every message starts with."""
+
+    def _set_table(self, name: str, model_level_AB: Any) -> None:
+        self.name, (self.A, self.B) = name, _set_AB(model_level_AB)
+        if self.A.shape != self.B.shape or self.A.ndim != 1 or len(self.A) < 2:
+            raise ValueError(f"{self.name}: A and B must be two lists of the same length (model levels + 1), got {self.A.shape} and {self.B.shape}")
+        self._device_AB: dict[Any, tuple[torch.Tensor, torch.Tensor]] = {}
+
+    def _coefficients(self, device: Any) -> tuple[torch.Tensor, torch.Tensor]:
+        if device not in self._device_AB:
+            self._device_AB[device] = tuple(torch.tensor(np.asarray(c, dtype=np.float64), device=device) for c in (self.A, self.B))
+        return self._device_AB[device]
+
+    def _model_level(self, param: str, levelist: Any) -> int:
+        try:
+            level = int(levelist)
+        except (TypeError, ValueError):
+            raise ValueError(f"{self.name}: model-level field {param} has levelist {levelist!r}") from None
+        if not 1 <= level <= len(self.A) - 1:
+            raise ValueError(f"{self.name}: level {level} of {param} is outside the {len(self.A) - 1} model levels of the A / B table")
+        return level
+
+    def _no_surface_pressure(self, identity: Any, has_lnsp: bool) -> ValueError:
+        hint = f" (it has lnsp: lnsp_to_sp | {self.name} is the route, lnsp is not taken in place of the surface pressure)" if has_lnsp else ""
+        return ValueError(f"{self.name}: no surface pressure {self.surface_pressure!r} for the model-level fields of {sorted(identity)}{hint}")
+
+
 @filter_registry.register("ml_to_pl")
-class ModelToPressureLevels(Filter):
+class ModelToPressureLevels(_HybridLevelFilter):
     """``levels``: the pressure levels in hPa (MARS' unit for ``levtype=pl``), in the order the new fields are to come.
     ``model_level_AB``: the half-level coefficients, a dict ``{"A": [...], "B": [...]}`` or a registered name
     (``filters.domain.register_model_level_AB``).  ``surface_pressure``: the ``param`` of the surface pressure in Pa — ``lnsp`` is not
@@ -76,11 +104,8 @@ class ModelToPressureLevels(Filter):
             raise ValueError(f"ml_to_pl: outside must be one of {', '.join(map(repr, native_levels.OUTSIDE))}, got {outside!r}")
         self.interpolation, self.outside, self.surface_pressure = interpolation, outside, surface_pressure
         self.params = None if params is None else ([params] if isinstance(params, str) else list(params))
-        self.A, self.B = _set_AB(model_level_AB)
-        if self.A.shape != self.B.shape or self.A.ndim != 1 or len(self.A) < 2:
-            raise ValueError(f"ml_to_pl: A and B must be two lists of the same length (model levels + 1), got {self.A.shape} and {self.B.shape}")
+        self._set_table("ml_to_pl", model_level_AB)
         self.targets_pa = [float(v) * 100.0 for v in self.levels]
-        self._device_AB: dict[Any, tuple[torch.Tensor, torch.Tensor]] = {}
         say_once(LOG, (type(self), "parity"), PARITY_NOTE)
 
     def __repr__(self) -> str:
@@ -106,15 +131,10 @@ class ModelToPressureLevels(Filter):
             if not interpolated:
                 passed.append(field)
                 continue
-            try:
-                level = int(taken["levelist"])
-            except (TypeError, ValueError):
-                raise ValueError(f"ml_to_pl: model-level field {param} has levelist {taken['levelist']!r}") from None
+            level = self._model_level(param, taken["levelist"])
             members = group["ml"].setdefault(param, [])
             if any(level == seen for seen, _ in members):
                 raise ValueError(f"Duplicate component {param} for {identity} and level {level}")
-            if not 1 <= level <= len(self.A) - 1:
-                raise ValueError(f"ml_to_pl: level {level} of {param} is outside the {len(self.A) - 1} model levels of the A / B table")
             members.append((level, field))
         plan = []
         level_sets: dict[str, tuple[int, ...]] = {}
@@ -122,19 +142,13 @@ class ModelToPressureLevels(Filter):
             if not group["ml"]:
                 continue
             if group["sp"] is None:
-                hint = " (it has lnsp: lnsp_to_sp | ml_to_pl is the route, lnsp is not taken in place of the surface pressure)" if group["lnsp"] else ""
-                raise ValueError(f"ml_to_pl: no surface pressure {self.surface_pressure!r} for the model-level fields of {sorted(identity)}{hint}")
+                raise self._no_surface_pressure(identity, group["lnsp"])
             for param, members in group["ml"].items():
                 level_set = tuple(sorted(level for level, _ in members))
                 if level_sets.setdefault(param, level_set) != level_set:
                     raise ValueError(f"ml_to_pl: mixed level sets for {param}: {list(level_sets[param])} and {list(level_set)} (in {sorted(identity)})")
             plan.append((group["sp"], group["ml"]))
         return passed, plan
-
-    def _coefficients(self, device: Any) -> tuple[torch.Tensor, torch.Tensor]:
-        if device not in self._device_AB:
-            self._device_AB[device] = tuple(torch.tensor(np.asarray(c, dtype=np.float64), device=device) for c in (self.A, self.B))
-        return self._device_AB[device]
 
     def _interpolate(self, stack: Any, sp: torch.Tensor, n_var: int, levels: tuple[int, ...]) -> Any:
         A, B = self._coefficients(stack.device)
@@ -183,7 +197,7 @@ GEOPOTENTIAL_COLUMNS_ROUTE = "columns"
 
 
 @filter_registry.register("geopotential_on_model_levels")
-class GeopotentialOnModelLevels(Filter):
+class GeopotentialOnModelLevels(_HybridLevelFilter):
     """``z`` on model levels from ``t``, ``q``, the surface pressure and the surface geopotential — what MARS holds — so that
     ``lnsp_to_sp | geopotential_on_model_levels | ml_to_pl`` yields z500 and the rest on the device.  An extension: the reference has no
     such filter.  ``model_level_AB`` as for ``ml_to_pl``; the other arguments name the ``param`` of each input and of the output.  The
@@ -199,11 +213,7 @@ class GeopotentialOnModelLevels(Filter):
         if len({temperature, specific_humidity, surface_pressure}) != 3:
             raise ValueError(f"geopotential_on_model_levels: temperature, specific_humidity and surface_pressure must be three params, got "
                              f"{temperature!r}, {specific_humidity!r}, {surface_pressure!r}")
-        self.A, self.B = _set_AB(model_level_AB)
-        if self.A.shape != self.B.shape or self.A.ndim != 1 or len(self.A) < 2:
-            raise ValueError(f"geopotential_on_model_levels: A and B must be two lists of the same length (model levels + 1), got {self.A.shape} "
-                             f"and {self.B.shape}")
-        self._device_AB: dict[Any, tuple[torch.Tensor, torch.Tensor]] = {}
+        self._set_table("geopotential_on_model_levels", model_level_AB)
         say_once(LOG, (type(self), "parity"), GEOPOTENTIAL_PARITY_NOTE)
 
     def __repr__(self) -> str:
@@ -213,8 +223,7 @@ class GeopotentialOnModelLevels(Filter):
     def _plan(self, fields: list[Any]) -> tuple[list[Any], list[dict[str, Any]]]:
         """``(passed through, [group])`` in first-seen order; a group: ``sp``, ``zs``, ``levels`` (top first) and the ``t`` / ``q`` fields
         in that order."""
-        name = "geopotential_on_model_levels"
-        n_model = len(self.A) - 1
+        name, n_model = self.name, len(self.A) - 1
         groups: dict[Any, dict[str, Any]] = {}
         owner: list[tuple[Any, Any, tuple[Any, Any, Any]]] = []  # (field, identity, (param, levtype, levelist)) in input order
         for field in fields:
@@ -228,15 +237,10 @@ class GeopotentialOnModelLevels(Filter):
                     raise ValueError(f"Duplicate component {param} for {identity}")
                 group["sp"] = field
             elif param in (self.temperature, self.specific_humidity) and taken["levtype"] == "ml":
-                try:
-                    level = int(taken["levelist"])
-                except (TypeError, ValueError):
-                    raise ValueError(f"{name}: model-level field {param} has levelist {taken['levelist']!r}") from None
+                level = self._model_level(param, taken["levelist"])
                 members = group["t" if param == self.temperature else "q"]
                 if level in members:
                     raise ValueError(f"Duplicate component {param} for {identity} and level {level}")
-                if not 1 <= level <= n_model:
-                    raise ValueError(f"{name}: level {level} of {param} is outside the {n_model} model levels of the A / B table")
                 members[level] = field
             elif param == self.surface_geopotential:  # (after t and q: a surface geopotential never shares their param on ml ... unless it is told to)
                 if group["zs"] is not None:
@@ -258,9 +262,7 @@ class GeopotentialOnModelLevels(Filter):
                 raise ValueError(f"{name}: the levels {levels[0]} .. {levels[-1]} of {self.temperature} have a gap down to the lowest level "
                                  f"{n_model} of the A / B table: missing levels {missing} (in {sorted(identity)})")
             if group["sp"] is None:
-                hint = (f" (it has lnsp: lnsp_to_sp | {name} is the route, lnsp is not taken in place of the surface pressure)"
-                        if group["lnsp"] else "")
-                raise ValueError(f"{name}: no surface pressure {self.surface_pressure!r} for the model-level fields of {sorted(identity)}{hint}")
+                raise self._no_surface_pressure(identity, group["lnsp"])
             if group["zs"] is None:
                 raise ValueError(f"{name}: no surface geopotential {self.surface_geopotential!r} for the model-level fields of {sorted(identity)}")
             plan.append(dict(identity=identity, sp=group["sp"], zs=group["zs"], levels=levels, t=[group["t"][v] for v in levels],
@@ -277,11 +279,6 @@ class GeopotentialOnModelLevels(Filter):
 
         passed = [field for field, identity, key in owner if not replaced(identity, key)]
         return passed, plan
-
-    def _coefficients(self, device: Any) -> tuple[torch.Tensor, torch.Tensor]:
-        if device not in self._device_AB:
-            self._device_AB[device] = tuple(torch.tensor(np.asarray(c, dtype=np.float64), device=device) for c in (self.A, self.B))
-        return self._device_AB[device]
 
     def _integrate(self, group: dict[str, Any]) -> Any:
         """One stack of the group's 2 n + 2 fields (one type: float32 only if every field is), its t and q rows as two views, one launch."""

@@ -44,22 +44,23 @@ def _call(fn: str, *args: Any) -> None:
     LIBRARY.check(fn, getattr(load(), fn)(*args))
 
 
+def _code(value, table: dict[str, int], what: str) -> int:
+    """A name of ``table`` (or the enum value itself) as the enum value."""
+    if isinstance(value, str):
+        if value not in table:
+            raise ValueError(f"unknown {what} {value!r}: one of {', '.join(table)}")
+        return table[value]
+    return int(value)
+
+
 def coordinate_code(coordinate) -> int:
     """``"linear"`` / ``"log"`` (or the enum value itself) as ``atx_levels_coordinate``."""
-    if isinstance(coordinate, str):
-        if coordinate not in COORDINATES:
-            raise ValueError(f"unknown coordinate {coordinate!r}: one of {', '.join(COORDINATES)}")
-        return COORDINATES[coordinate]
-    return int(coordinate)
+    return _code(coordinate, COORDINATES, "coordinate")
 
 
 def outside_code(outside) -> int:
     """``"nearest"`` / ``"missing"`` (or the enum value itself) as ``atx_levels_outside``."""
-    if isinstance(outside, str):
-        if outside not in OUTSIDE:
-            raise ValueError(f"unknown outside policy {outside!r}: one of {', '.join(OUTSIDE)}")
-        return OUTSIDE[outside]
-    return int(outside)
+    return _code(outside, OUTSIDE, "outside policy")
 
 
 def interpolate(src, out, sp, A, B, targets, *, n_pts, n_var, n_lev, n_tgt, src_pitch, out_pitch, layout, level_index=None,

@@ -22,6 +22,15 @@ def _device_f64(values: Any, device: torch.device) -> torch.Tensor:
     return torch.tensor(np.asarray(values, dtype=np.float64).reshape(-1), dtype=torch.float64, device=device)
 
 
+def _per_point(values: torch.Tensor, n_pts: int, dtype: torch.dtype, what: str) -> torch.Tensor:
+    """One value per point (``sp``, ``zs``) as a contiguous vector of the stack's type."""
+    values = values.reshape(-1)
+    assert values.numel() == n_pts, (what, values.numel(), n_pts)
+    if values.dtype != dtype or not values.is_contiguous():
+        values = values.to(dtype).contiguous()
+    return values
+
+
 def interpolate_levels(stack: Stack, sp: torch.Tensor, A: Any, B: Any, targets_pa: Sequence[float], *, n_var: int = 1,
                        level_index: Sequence[int] | None = None, coordinate: str = "linear", outside: str = "nearest") -> Stack:
     """``stack`` holds ``n_var`` variables of ``stack.n_lev // n_var`` model levels each, variables adjacent, top level first; the result
@@ -39,10 +48,7 @@ def interpolate_levels(stack: Stack, sp: torch.Tensor, A: Any, B: Any, targets_p
     if level_index is None:  # the whole model (R: q_height.py:44-54, the same assertion)
         assert A.numel() == n_lev + 1, f"model level AB-coefficients should have one more vertical level than the stack's {n_lev}"
     targets = _device_f64(targets_pa if isinstance(targets_pa, torch.Tensor) else list(targets_pa), stack.device).reshape(-1)
-    sp = sp.reshape(-1)
-    assert sp.numel() == stack.n_pts, (sp.numel(), stack.n_pts)
-    if sp.dtype != stack.dtype or not sp.is_contiguous():
-        sp = sp.to(stack.dtype).contiguous()
+    sp = _per_point(sp, stack.n_pts, stack.dtype, "sp")
     out = Stack.empty(stack.n_pts, n_var * targets.numel(), stack.dtype, stack.device, stack.layout)
     native_levels.interpolate(stack.data, out.data, sp, A, B, targets, n_pts=stack.n_pts, n_var=n_var, n_lev=n_lev, n_tgt=targets.numel(),
                               src_pitch=stack.pitch, out_pitch=out.pitch, layout=stack.layout, level_index=level_index, coordinate=coordinate,
@@ -64,16 +70,8 @@ def geopotential_on_model_levels(t: Stack, q: Stack, sp: torch.Tensor, zs: torch
     A, B = _device_f64(A, t.device), _device_f64(B, t.device)
     assert A.shape == B.shape, "A and B coefficients must have same shape"
     assert A.numel() >= t.n_lev + 1, f"model level AB-coefficients should have at least one more vertical level than the stack's {t.n_lev}"
-
-    def per_point(values: torch.Tensor, what: str) -> torch.Tensor:
-        values = values.reshape(-1)
-        assert values.numel() == t.n_pts, (what, values.numel(), t.n_pts)
-        if values.dtype != t.dtype or not values.is_contiguous():
-            values = values.to(t.dtype).contiguous()
-        return values
-
-    sp = per_point(sp, "sp")
-    zs = None if zs is None else per_point(zs, "zs")
+    sp = _per_point(sp, t.n_pts, t.dtype, "sp")
+    zs = None if zs is None else _per_point(zs, t.n_pts, t.dtype, "zs")
     out = Stack.empty(t.n_pts, t.n_lev, t.dtype, t.device, t.layout)
     native_geopotential.geopotential(t.data, q.data, sp, zs, A, B, out.data, n_pts=t.n_pts, n_lev=t.n_lev, t_pitch=t.pitch, q_pitch=q.pitch,
                                out_pitch=out.pitch, layout=t.layout)

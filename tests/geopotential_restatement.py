@@ -31,6 +31,8 @@ from typing import Optional
 import mpmath
 import numpy as np
 
+from hybrid_column_common import assert_same_bits as _assert_same_bits, bits_type, eta_table  # noqa: F401 - the tests reach them here
+
 RD, RV = 287.0597, 461.5250
 LN2 = 0.6931471805599453
 DEFECTS = ("alpha-only", "own-delta", "top-first", "dry", "zs-dropped", "first-ignored", "top-general")
@@ -186,17 +188,7 @@ def numpy_worst(case: GeoCase) -> float:
 
 
 # ---- the comparisons of the GPU test (plain functions: the host test drives them with planted defects) ------------------------------
-def bits_type(T):
-    return np.uint32 if np.dtype(T).itemsize == 4 else np.uint64
-
-
-def assert_same_bits(got: np.ndarray, want: np.ndarray, what: str) -> None:
-    """NaN exactly where the statement has NaN (which NaN is unspecified), the statement's bits everywhere else."""
-    assert got.dtype == want.dtype and got.shape == want.shape, (what, got.dtype, want.dtype, got.shape, want.shape)
-    gn, wn = np.isnan(got), np.isnan(want)
-    assert np.array_equal(gn, wn), f"{what}: NaN positions differ at (point, level) {np.argwhere(gn != wn)[:5].tolist()}"
-    same = (np.ascontiguousarray(got).view(bits_type(got.dtype)) == np.ascontiguousarray(want).view(bits_type(want.dtype))) | wn
-    assert same.all(), f"{what}: bits differ at (point, level) {np.argwhere(~same)[:5].tolist()}"
+assert_same_bits = functools.partial(_assert_same_bits, axes="(point, level)")
 
 
 def has_logarithm(case: GeoCase) -> bool:
@@ -266,12 +258,6 @@ def expand(a: Optional[np.ndarray], n_pts: int) -> Optional[np.ndarray]:
 
 
 # ---- cases -----------------------------------------------------------------------------------------------------------------------
-def eta_table(n_half: int, bend: float = 20000.0) -> tuple[np.ndarray, np.ndarray]:
-    """B = eta^2, A = bend eta (1 - eta), eta = k / (n_half - 1): the top half level at p = 0, the last one the ground (A = 0, B = 1)."""
-    eta = np.arange(n_half, dtype=np.float64) / np.float64(n_half - 1)
-    return np.float64(bend) * eta * (np.float64(1.0) - eta), eta * eta
-
-
 @functools.lru_cache(maxsize=None)
 def make_case(T, n_lev: int, kind: str = WHOLE, with_zs: bool = True, specials: bool = True) -> GeoCase:
     """N_COLUMNS random columns: t around 250 K, q in [0, 0.02], sp in [50 000, 105 000] Pa, zs in [-500, 30 000] with one strongly

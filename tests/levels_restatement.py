@@ -30,6 +30,7 @@ import mpmath
 import numpy as np
 
 import exact_statements as X
+from hybrid_column_common import assert_same_bits as _assert_same_bits, bits_type, eta_table  # noqa: F401 - the tests reach them here
 
 LINEAR, LOG = "linear", "log"
 NEAREST, MISSING = "nearest", "missing"
@@ -207,17 +208,7 @@ def errors(got: np.ndarray, value: np.ndarray, unit: np.ndarray, scale_to=None) 
 
 
 # ---- the comparisons of the GPU test (plain functions: the host test drives them with planted defects) ------------------------------
-def bits_type(T):
-    return np.uint32 if np.dtype(T).itemsize == 4 else np.uint64
-
-
-def assert_same_bits(got: np.ndarray, want: np.ndarray, what: str) -> None:
-    """NaN exactly where the statement has NaN (which NaN is unspecified), the statement's bits everywhere else."""
-    assert got.dtype == want.dtype and got.shape == want.shape, (what, got.dtype, want.dtype, got.shape, want.shape)
-    gn, wn = np.isnan(got), np.isnan(want)
-    assert np.array_equal(gn, wn), f"{what}: NaN positions differ at (point, variable, target) {np.argwhere(gn != wn)[:5].tolist()}"
-    same = (np.ascontiguousarray(got).view(bits_type(got.dtype)) == np.ascontiguousarray(want).view(bits_type(want.dtype))) | wn
-    assert same.all(), f"{what}: bits differ at (point, variable, target) {np.argwhere(~same)[:5].tolist()}"
+assert_same_bits = functools.partial(_assert_same_bits, axes="(point, variable, target)")
 
 
 def check_linear(compute, cases) -> None:
@@ -325,15 +316,6 @@ def exact_reference(case: LevelsCase, coordinate):
 
 
 # ---- cases -----------------------------------------------------------------------------------------------------------------------
-def eta_table(n_half: int, of: int | None = None, bend: float = 20000.0) -> tuple[np.ndarray, np.ndarray]:
-    """B = eta^2, A = bend eta (1 - eta), eta = k / of for k = 0 .. n_half - 1 (``of`` defaults to n_half - 1: the last half level is
-    the ground, A = 0 and B = 1 there; a larger ``of`` is a table cut off above the ground, with A[H - 1] != 0).  With ``bend`` = 150 000
-    the pressure DECREASES towards the ground wherever sp < 75 000 Pa: columns that are not monotone, which the statement counts whole."""
-    of = n_half - 1 if of is None else of
-    eta = np.arange(n_half, dtype=np.float64) / np.float64(of)
-    return np.float64(bend) * eta * (np.float64(1.0) - eta), eta * eta
-
-
 def plant_specials(x: np.ndarray) -> None:
     """NaN and +-inf in a few columns: at the top, at the bottom and (columns long enough) in between."""
     n_pts, n_var, n_lev = x.shape

@@ -17,11 +17,11 @@ import pytest
 
 from anemoi_transform_amd import native, native_geopotential, native_levels
 from anemoi_transform_amd.core import filter_registry
-from anemoi_transform_amd.fields import fieldlist_from_dicts
 from anemoi_transform_amd.filters import create_filter_by_name
 
 import geopotential_restatement as gr
 import vertical_restatement as vr
+from hybrid_column_common import fields
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -267,19 +267,6 @@ def test_geopotential_on_model_levels_checks_its_stacks_on_the_host():
 # ---- the filter --------------------------------------------------------------------------------------------------------------------
 AB = dict(A=[0.0, 2000.0, 4000.0, 0.0], B=[0.0, 0.1, 0.5, 1.0])  # three model levels
 NAME = "geopotential_on_model_levels"
-
-
-def fields(*specs, date=20260101):
-    """(param, levtype, levelist) specs as a FieldList of 6-point fields with a MARS namespace."""
-    lat, lon = np.linspace(50.0, 0.0, 6), np.linspace(0.0, 50.0, 6)
-    out = []
-    for param, levtype, levelist in specs:
-        spec = dict(values=np.full(6, 100000.0 if param in ("sp", "lnsp") else 250.0), latitudes=lat, longitudes=lon, param=param, levtype=levtype,
-                    date=date, time=0, step=0)
-        if levelist is not None:
-            spec["levelist"] = levelist
-        out.append(spec)
-    return fieldlist_from_dicts(out, mars=True)
 
 
 def test_the_filter_is_registered_and_checks_its_configuration():

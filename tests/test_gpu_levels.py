@@ -25,32 +25,11 @@ from anemoi_transform_amd.filters import create_filter_by_name
 from anemoi_transform_amd.grids import lookup
 from anemoi_transform_amd.stack import COLUMNS, FIELDS, Stack
 from anemoi_transform_amd.vertical import interpolate_levels
+from hybrid_column_common import CANARY, COLUMN_STORAGE, FIELD_STORAGE, WIDTHS, allocate
 
 pytestmark = pytest.mark.gpu
 
-WIDTHS = [pytest.param(np.float32, id="f32"), pytest.param(np.float64, id="f64")]
-# the 16-byte route; an odd pitch and an unaligned base for the scalar route; the field-major kernel, tight and with a pitch
-STORAGE = ("columns", "columns-pitch+1", "columns-base+1", "fields", "fields-pitch+3")
-CANARY = 7.25
-
-
-def allocate(rows: int, row_len: int, storage: str, dtype, dev, fill: float) -> torch.Tensor:
-    """A ``[rows, pitch]`` view, every element ``fill``: "pitch+1" is a pitch that is no multiple of the 16-byte vector, "base+1" keeps
-    the aligned pitch and starts one element into a larger allocation."""
-    per16 = 16 // np.dtype(dtype).itemsize
-    pitch = -(-max(row_len, 1) // per16) * per16
-    if storage == "columns-pitch+1":
-        pitch = pitch + 1
-    if storage == "fields":
-        pitch = row_len
-    if storage == "fields-pitch+3":
-        pitch = row_len + 3
-    off = 1 if storage == "columns-base+1" else 0
-    flat = torch.full((rows * pitch + per16 + off,), fill, dtype=torch.float32 if dtype is np.float32 else torch.float64, device=dev)
-    data = flat[off: off + rows * pitch].view(rows, pitch) if rows * pitch else flat[:0].view(rows, pitch)
-    if rows * pitch:
-        assert (data.data_ptr() % 16 != 0) == (off == 1)
-    return data
+STORAGE = COLUMN_STORAGE + FIELD_STORAGE
 
 
 def run_kernel(dev, case: lr.LevelsCase, storage: str, coordinate: str, outside: str) -> np.ndarray:

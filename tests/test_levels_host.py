@@ -26,14 +26,13 @@ import numpy as np
 import pytest
 
 from anemoi_transform_amd import native, native_levels
-from anemoi_transform_amd.fields import fieldlist_from_dicts
 from anemoi_transform_amd.filters import create_filter_by_name
 from anemoi_transform_amd.core import filter_registry
 
 import levels_restatement as lr
+from hybrid_column_common import WIDTHS, fields
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-WIDTHS = [pytest.param(np.float32, id="f32"), pytest.param(np.float64, id="f64")]
 ULPS_FILE = os.path.join(ROOT, "profiles", "levels_ulps.json")
 
 
@@ -271,19 +270,6 @@ def test_abi_argument_validation_without_a_gpu():
 
 # ---- the filter --------------------------------------------------------------------------------------------------------------------
 AB = dict(A=[0.0, 2000.0, 4000.0, 0.0], B=[0.0, 0.1, 0.5, 1.0])  # three model levels
-
-
-def fields(*specs, date=20260101):
-    """(param, levtype, levelist) specs as a FieldList of 6-point fields with a MARS namespace."""
-    lat, lon = np.linspace(50.0, 0.0, 6), np.linspace(0.0, 50.0, 6)
-    out = []
-    for param, levtype, levelist in specs:
-        spec = dict(values=np.full(6, 100000.0 if param in ("sp", "lnsp") else 250.0), latitudes=lat, longitudes=lon, param=param, levtype=levtype,
-                    date=date, time=0, step=0)
-        if levelist is not None:
-            spec["levelist"] = levelist
-        out.append(spec)
-    return fieldlist_from_dicts(out, mars=True)
 
 
 def test_the_filter_is_registered_and_checks_its_configuration():
