@@ -1,5 +1,5 @@
-// Host-side plumbing shared, as source, by the eight libraries (libatx, libatx_text, libatx_plan, libatx_mesh, libatx_missing,
-// libatx_stat, libatx_levels, libatx_geopotential): the
+// Host-side plumbing shared, as source, by the nine libraries (libatx, libatx_text, libatx_plan, libatx_mesh, libatx_missing,
+// libatx_stat, libatx_levels, libatx_geopotential, libatx_heights): the
 // calling thread's error message, the require-and-return macros and the grid of a one-lane-per-item launch.  Host code only, so a
 // companion library includes it without atx_common.hpp's device helpers.
 //

@@ -8,11 +8,16 @@ results are levels of a resident stack: ``ml_to_pl | regrid`` gathers 13 levels 
 
 The statement (include/atx_levels.h) is in-tree: linear in pressure or in its logarithm between the two full levels that bracket the
 target, the lowest level's value in the half layer above the ground, ``outside`` above the top full level and below the ground.  The
-``t`` / ``z`` extrapolations of IFS below the ground and height-level targets (which need the geopotential integral) are out of scope.
+``t`` / ``z`` extrapolations of IFS below the ground are out of scope; height-level targets are ``ml_to_hl``'s (below).
 
 ``geopotential_on_model_levels`` (below) is that integral: ``z`` is not archived on IFS model levels, so it is integrated hydrostatically
 from ``t``, ``q``, the surface pressure and the surface geopotential (``atx_geopotential_on_model_levels``, include/atx_geopotential.h),
-and ``ml_to_pl`` takes it to pressure levels as any other variable.  A height-level filter on top of it is not here yet.
+and ``ml_to_pl`` takes it to pressure levels as any other variable.
+
+``ml_to_hl`` (below) is the height-level filter on top of that integral: the model-level fields of a group at heights above the ground
+or above mean sea level (wind at 10 / 100 / 200 m, ``t`` and ``q`` at the height of an observation), through ``atx_heights_interpolate``
+(include/atx_heights.h) — the integral, the bracket search in it and the interpolation of every variable in ONE launch per group, without
+``z`` on model levels ever being written.
 """
 
 from __future__ import annotations
@@ -28,7 +33,8 @@ from ..core import Filter, filter_registry, say_once
 from ..fields import FieldList, fields_to_stack, new_field_from_stack
 from ..grouping import identity_of
 from ..stack import Stack
-from ..vertical import geopotential_on_model_levels, interpolate_levels
+from .. import native_heights
+from ..vertical import geopotential_on_model_levels, interpolate_levels, interpolate_to_heights
 from .domain import _one_field, _set_AB
 
 LOG = logging.getLogger(__name__)
@@ -302,4 +308,162 @@ class GeopotentialOnModelLevels(_HybridLevelFilter):
             out = self._integrate(group)
             for k, level in enumerate(group["levels"]):
                 result.append(new_field_from_stack(out, k, template=group["t"][k], metadata=dict(param=self.output, levtype="ml", levelist=level)))
+        return FieldList(result)
+
+
+HEIGHTS_PARITY_NOTE = ("ml_to_hl: the interpolation is an in-tree statement (include/atx_heights.h) — linear in the geopotential of the full "
+                       "levels, which is the hydrostatic integral of geopotential_on_model_levels, nearest or missing outside; the heights are "
+                       "geopotential heights z / g — and unpinned against earthkit-meteo, whose hybrid-to-height interpolation it resembles; "
+                       "the extrapolations of IFS below the ground are not applied")
+
+
+@filter_registry.register("ml_to_hl")
+class ModelToHeightLevels(_HybridLevelFilter):
+    """``levels``: the heights in metres (geopotential metres, ``z / g``), in the order the new fields are to come, above the ground
+    (``reference="ground"``) or above mean sea level (``"sea"``; only there may a level be negative).  ``model_level_AB`` as for
+    ``ml_to_pl``; ``temperature``, ``specific_humidity``, ``surface_pressure`` and ``surface_geopotential`` name the ``param`` of each
+    input of the hydrostatic integral — ``lnsp`` is not taken for the surface pressure (``lnsp_to_sp | ml_to_hl``), and the surface
+    geopotential is looked for under ``reference="sea"`` only: the group's ONE field of that param, of any levtype.  ``params``: only
+    these are interpolated (default: every param with ml fields, ``t`` and ``q`` among them).  ``outside``: ``"nearest"`` or
+    ``"missing"`` (NaN) above the top full level and below the ground.  An extension: the reference has no such filter.  The ``t``, the
+    ``q`` and every interpolated param of a group (the fields that share every MARS key but ``param``, ``levelist`` and ``levtype``) must
+    hold the same model levels, without a gap down to the lowest level of the table.  Every input passes through; the new fields have
+    ``levtype="hl"`` and ``levelist=<metres>``."""
+
+    def __init__(self, *, levels: Any = (10, 100, 200), model_level_AB: Any, reference: str = "ground", temperature: str = "t",
+                 specific_humidity: str = "q", surface_pressure: str = "sp", surface_geopotential: str = "z", params: Any = None,
+                 outside: str = "nearest") -> None:
+        if isinstance(levels, (int, float)):
+            levels = [levels]
+        try:
+            heights = [float(v) for v in levels]
+        except (TypeError, ValueError):
+            raise ValueError(f"ml_to_hl: levels must be heights in metres, got {levels!r}") from None
+        if not heights or not all(np.isfinite(v) for v in heights):
+            raise ValueError(f"ml_to_hl: levels must be a non-empty list of finite heights in metres, got {levels!r}")
+        self.levels = [_level_key(v) for v in heights]
+        if reference not in native_heights.REFERENCES:
+            raise ValueError(f"ml_to_hl: reference must be one of {', '.join(map(repr, native_heights.REFERENCES))}, got {reference!r}")
+        if reference == "ground" and any(float(v) < 0 for v in self.levels):
+            raise ValueError(f"ml_to_hl: levels must not be negative above the ground (reference='sea' takes heights below sea level), got {levels!r}")
+        if len(set(self.levels)) != len(self.levels):
+            raise ValueError(f"ml_to_hl: duplicate levels in {levels!r}")
+        if outside not in native_heights.OUTSIDE:
+            raise ValueError(f"ml_to_hl: outside must be one of {', '.join(map(repr, native_heights.OUTSIDE))}, got {outside!r}")
+        if len({temperature, specific_humidity, surface_pressure}) != 3:
+            raise ValueError(f"ml_to_hl: temperature, specific_humidity and surface_pressure must be three params, got {temperature!r}, "
+                             f"{specific_humidity!r}, {surface_pressure!r}")
+        self.reference, self.outside = reference, outside
+        self.temperature, self.specific_humidity = temperature, specific_humidity
+        self.surface_pressure, self.surface_geopotential = surface_pressure, surface_geopotential
+        self.params = None if params is None else ([params] if isinstance(params, str) else list(params))
+        self._set_table("ml_to_hl", model_level_AB)
+        self.heights_m = [float(v) for v in self.levels]
+        say_once(LOG, (type(self), "parity"), HEIGHTS_PARITY_NOTE)
+
+    def __repr__(self) -> str:
+        return f"ModelToHeightLevels(levels={self.levels}, reference={self.reference!r}, outside={self.outside!r})"
+
+    # ---- grouping: host bookkeeping, every ValueError before any launch ------------------------------------------------------------
+    def _plan(self, fields: list[Any]) -> tuple[list[Any], list[dict[str, Any]]]:
+        """``(passed through, [group])`` in first-seen order; a group: ``sp``, ``zs`` (``None`` above the ground), ``levels`` (top first),
+        the ``t`` / ``q`` fields in that order, ``ml``, ``{param: fields in that order}`` of what is interpolated, and each param's template."""
+        name, n_model, sea = self.name, len(self.A) - 1, self.reference == "sea"
+        groups: dict[Any, dict[str, Any]] = {}
+        for field in fields:
+            identity, taken = identity_of(field, ("param", "levelist", "levtype"), ("variable",))
+            group = groups.setdefault(identity, dict(sp=None, zs=[], lnsp=False, t={}, q={}, ml={}, templates={}))
+            param, on_ml = taken["param"], taken["levtype"] == "ml"
+            group["lnsp"] = group["lnsp"] or param == "lnsp"
+            if param == self.surface_pressure:
+                if group["sp"] is not None:
+                    raise ValueError(f"Duplicate component {param} for {identity}")
+                group["sp"] = field
+                continue
+            if param == "lnsp":  # (a model-level field in MARS, levelist 1: not a column)
+                continue
+            is_t_or_q = on_ml and param in (self.temperature, self.specific_humidity)
+            if sea and param == self.surface_geopotential and not is_t_or_q:  # any levtype: MARS keeps it as z, ml, levelist 1
+                group["zs"].append(field)
+                continue
+            if not on_ml:
+                continue
+            level = self._model_level(param, taken["levelist"])
+            if is_t_or_q:
+                members = group["t" if param == self.temperature else "q"]
+                if level in members:
+                    raise ValueError(f"Duplicate component {param} for {identity} and level {level}")
+                members[level] = field
+            if self.params is None or param in self.params:
+                members = group["ml"].setdefault(param, {})
+                if level in members:
+                    raise ValueError(f"Duplicate component {param} for {identity} and level {level}")
+                members[level] = field
+                group["templates"].setdefault(param, field)  # the param's first ml field of the input
+        plan = []
+        for identity, group in groups.items():
+            if not group["ml"]:
+                continue
+            for key, param in (("t", self.temperature), ("q", self.specific_humidity)):
+                if not group[key]:
+                    raise ValueError(f"{name}: no model-level fields of {param!r} for {sorted(identity)}")
+            levels, q_levels = sorted(group["t"]), sorted(group["q"])
+            if levels != q_levels:
+                raise ValueError(f"{name}: mixed level sets for {self.temperature} and {self.specific_humidity}: {levels} and {q_levels} "
+                                 f"(in {sorted(identity)})")
+            for param, members in group["ml"].items():
+                if sorted(members) != levels:
+                    raise ValueError(f"{name}: mixed level sets for {self.temperature} and {param}: {levels} and {sorted(members)} "
+                                     f"(in {sorted(identity)}; params= selects what is interpolated)")
+            missing = sorted(set(range(levels[0], n_model + 1)) - set(levels))
+            if missing:
+                raise ValueError(f"{name}: the levels {levels[0]} .. {levels[-1]} of {self.temperature} have a gap down to the lowest level "
+                                 f"{n_model} of the A / B table: missing levels {missing} (in {sorted(identity)})")
+            if group["sp"] is None:
+                raise self._no_surface_pressure(identity, group["lnsp"])
+            if sea and not group["zs"]:
+                raise ValueError(f"{name}: no surface geopotential {self.surface_geopotential!r} for the model-level fields of {sorted(identity)}")
+            if sea and len(group["zs"]) > 1:
+                raise ValueError(f"{name}: {len(group['zs'])} fields of the surface geopotential {self.surface_geopotential!r} for {sorted(identity)}, "
+                                 f"one is needed: if geopotential_on_model_levels made them, give that filter another output= (its default "
+                                 f"output takes the surface field's place), or name the surface field with surface_geopotential=")
+            plan.append(dict(identity=identity, sp=group["sp"], zs=group["zs"][0] if sea else None, levels=levels,
+                             t=[group["t"][v] for v in levels], q=[group["q"][v] for v in levels],
+                             ml={param: [members[v] for v in levels] for param, members in group["ml"].items()}, templates=group["templates"]))
+        return list(fields), plan
+
+    def _interpolate(self, group: dict[str, Any]) -> Any:
+        """One stack of the group's fields (one type: float32 only if every field is) — the variables, then t and q unless they are among
+        them, then sp and zs — its rows as views, one launch."""
+        n, params = len(group["levels"]), list(group["ml"])
+        rows = [f for param in params for f in group["ml"][param]]
+        first = {}
+        for key, param in (("t", self.temperature), ("q", self.specific_humidity)):
+            if param in params:
+                first[key] = params.index(param) * n
+            else:
+                first[key] = len(rows)
+                rows += group[key]
+        n_rows = len(rows)
+        stack = fields_to_stack([*rows, group["sp"]] + ([] if group["zs"] is None else [group["zs"]]))
+        if stack.layout == native.COLUMNS:
+            view = lambda a, b: Stack(stack.data[:, a:b], stack.n_pts, b - a, native.COLUMNS)  # noqa: E731
+        else:
+            view = lambda a, b: Stack(stack.data[a:b], stack.n_pts, b - a, native.FIELDS)  # noqa: E731
+        A, B = self._coefficients(stack.device)
+        zs = None if group["zs"] is None else stack.level_view(n_rows + 1)
+        return interpolate_to_heights(view(0, len(params) * n), view(first["t"], first["t"] + n), view(first["q"], first["q"] + n),
+                                      stack.level_view(n_rows), zs, A, B, self.heights_m, n_var=len(params), reference=self.reference,
+                                      outside=self.outside)
+
+    def forward(self, data: Any) -> FieldList:
+        passed, plan = self._plan(list(data))
+        result = list(passed)
+        n_tgt = len(self.levels)
+        for group in plan:
+            out = self._interpolate(group)
+            for v, param in enumerate(group["ml"]):
+                template = group["templates"][param]
+                for i, level in enumerate(self.levels):
+                    result.append(new_field_from_stack(out, v * n_tgt + i, template=template, metadata=dict(levtype="hl", levelist=level)))
         return FieldList(result)
