@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import native_geopotential, native_heights, native_levels
-from .stack import Stack
+from .stack import COLUMNS, Stack
 
 G = 9.80665  # m / s^2: metres of geopotential height to geopotential (``filters.pointwise.g_gravitational_acceleration``)
 
@@ -42,7 +42,9 @@ def interpolate_levels(stack: Stack, sp: torch.Tensor, A: Any, B: Any, targets_p
     order).  ``sp`` is the surface pressure of every point (Pa, a device tensor); ``A`` / ``B`` the half-level coefficients (host arrays
     or device tensors); ``level_index`` the rows' 0-based model levels where the stack holds a subset of the model (strictly increasing).
     ``coordinate``: ``"linear"`` or ``"log"`` in pressure; ``outside``: ``"nearest"`` or ``"missing"`` above the top full level and below
-    the ground.  One launch."""
+    the ground.  One launch — unless the column kernel refuses the stack because one point's ``n_var`` columns do not fit the LDS of a
+    workgroup (``NotImplementedError``): then the variables are halved, down to a single one, and each part is launched into its own
+    rows of the one result.  A variable's result does not depend on the others, so the bits are those of one launch."""
     if n_var < 1 or stack.n_lev % n_var:
         raise ValueError(f"a stack of {stack.n_lev} rows does not hold {n_var} variables of equally many levels")
     n_lev = stack.n_lev // n_var
@@ -54,9 +56,21 @@ def interpolate_levels(stack: Stack, sp: torch.Tensor, A: Any, B: Any, targets_p
     targets = _device_f64(targets_pa if isinstance(targets_pa, torch.Tensor) else list(targets_pa), stack.device).reshape(-1)
     sp = _per_point(sp, stack.n_pts, stack.dtype, "sp")
     out = Stack.empty(stack.n_pts, n_var * targets.numel(), stack.dtype, stack.device, stack.layout)
-    native_levels.interpolate(stack.data, out.data, sp, A, B, targets, n_pts=stack.n_pts, n_var=n_var, n_lev=n_lev, n_tgt=targets.numel(),
-                              src_pitch=stack.pitch, out_pitch=out.pitch, layout=stack.layout, level_index=level_index, coordinate=coordinate,
-                              outside=outside)
+    n_tgt = targets.numel()
+
+    def launch(first: int, count: int) -> None:
+        """Variables ``first .. first + count - 1``: views of the two column stacks that start at their rows and keep the pitch."""
+        src, dst = (stack.data[:, first * n_lev:], out.data[:, first * n_tgt:]) if first else (stack.data, out.data)
+        try:
+            native_levels.interpolate(src, dst, sp, A, B, targets, n_pts=stack.n_pts, n_var=count, n_lev=n_lev, n_tgt=n_tgt, src_pitch=stack.pitch,
+                                      out_pitch=out.pitch, layout=stack.layout, level_index=level_index, coordinate=coordinate, outside=outside)
+        except NotImplementedError:
+            if stack.layout != COLUMNS or count == 1:
+                raise
+            launch(first, count // 2)
+            launch(first + count // 2, count - count // 2)
+
+    launch(0, n_var)
     return out
 
 
