@@ -18,6 +18,10 @@ and ``ml_to_pl`` takes it to pressure levels as any other variable.
 or above mean sea level (wind at 10 / 100 / 200 m, ``t`` and ``q`` at the height of an observation), through ``atx_heights_interpolate``
 (include/atx_heights.h) — the integral, the bracket search in it and the interpolation of every variable in ONE launch per group, without
 ``z`` on model levels ever being written.
+
+``ml_to_pl_tz`` (below) is where ``t`` and ``z`` on pressure levels get what IFS gives them under the ground — the extrapolations that
+``ml_to_pl`` leaves out — and where ``msl`` comes from: ``atx_pltz_interpolate`` (include/atx_pltz.h), the integral, the bracket search in
+pressure, both variables and the mean sea level pressure in ONE launch per group.
 """
 
 from __future__ import annotations
@@ -33,8 +37,8 @@ from ..core import Filter, filter_registry, say_once
 from ..fields import FieldList, fields_to_stack, new_field_from_stack
 from ..grouping import identity_of
 from ..stack import Stack
-from .. import native_heights
-from ..vertical import geopotential_on_model_levels, interpolate_levels, interpolate_to_heights
+from .. import native_heights, native_pltz
+from ..vertical import geopotential_on_model_levels, interpolate_levels, interpolate_to_heights, t_z_on_pressure_levels
 from .domain import _one_field, _set_AB
 
 LOG = logging.getLogger(__name__)
@@ -466,4 +470,140 @@ class ModelToHeightLevels(_HybridLevelFilter):
                 template = group["templates"][param]
                 for i, level in enumerate(self.levels):
                     result.append(new_field_from_stack(out, v * n_tgt + i, template=template, metadata=dict(levtype="hl", levelist=level)))
+        return FieldList(result)
+
+
+PLTZ_PARITY_NOTE = ("ml_to_pl_tz: t and z on pressure levels, their extrapolations under the ground and msl are an in-tree statement "
+                    "(include/atx_pltz.h) — the ECMWF post-processing scheme as Trenberth, Berry and Buja (1993) write it, on the hydrostatic "
+                    "integral of geopotential_on_model_levels — and unpinned against IFS / MARS")
+
+#: how a COLUMNS stack is served by ``ml_to_pl_tz``: "columns" (the fused LDS-tile kernel on the stack as it is) or "fields" (relayout,
+#: the FIELDS kernel, relayout back).  Set to the route that measured faster (tools/pltz_bench.py, profiles/pltz_bench.json; DESIGN.md §3
+#: "Pressure-level t / z kernel"): O1280 x 137 -> 13 levels and msl on one MI355X, "columns" 8.08 / 8.87 ms (float32 / float64); the
+#: FIELDS kernel on stacks that already are field-major takes 16.5 / 19.9 ms, before any relayout is counted.
+PLTZ_COLUMNS_ROUTE = "columns"
+
+
+@filter_registry.register("ml_to_pl_tz")
+class ModelToPressureLevelsTZ(_HybridLevelFilter):
+    """Temperature and geopotential on pressure levels as IFS post-processes them — interpolated between the full levels, extrapolated
+    under the ground (Tibet, Greenland, Antarctica at 1000 / 925 / 850 / 700 hPa), where ``ml_to_pl`` writes the lowest level's value or
+    NaN — and the mean sea level pressure, from ``t``, ``q``, the surface pressure and the surface geopotential on model levels: what
+    MARS holds.  ONE launch per group (``atx_pltz_interpolate``, include/atx_pltz.h holds the statement); ``z`` on model levels is never
+    written.  An extension: the reference has no such filter.
+
+    ``levels``: the pressure levels in hPa, in the order the new fields are to come.  ``model_level_AB`` as for ``ml_to_pl``;
+    ``temperature``, ``specific_humidity``, ``surface_pressure`` and ``surface_geopotential`` name the ``param`` of each input — ``lnsp``
+    is not taken for the surface pressure (``lnsp_to_sp | ml_to_pl_tz``); the surface geopotential is the group's ONE field of that param,
+    of any levtype (MARS keeps it as ``z``, ``ml``, ``levelist=1``).  ``interpolation``: ``"linear"`` or ``"log"`` in pressure.  The
+    ``t`` and ``q`` fields of a group (the fields that share every MARS key but ``param``, ``levelist`` and ``levtype``) must hold the same
+    model levels, without a gap down to the lowest level of the table.  Every input passes through; the new fields are ``temperature``
+    and ``output_geopotential`` with ``levtype="pl"`` and, with ``msl=True``, ``msl`` with ``levtype="sfc"`` and no levelist.  For the
+    rest of a recipe, for which the lowest level's value IS what IFS gives: ``ml_to_pl_tz | ml_to_pl(params=["u", "v", "q", "w"])``."""
+
+    def __init__(self, *, levels: Any, model_level_AB: Any, temperature: str = "t", specific_humidity: str = "q", surface_pressure: str = "sp",
+                 surface_geopotential: str = "z", interpolation: str = "linear", msl: bool = True, output_geopotential: str = "z") -> None:
+        if isinstance(levels, (int, float)):
+            levels = [levels]
+        try:
+            self.levels = [_level_key(v) for v in levels]
+        except (TypeError, ValueError):
+            raise ValueError(f"ml_to_pl_tz: levels must be pressures in hPa, got {levels!r}") from None
+        if not self.levels or not all(np.isfinite(float(v)) and float(v) > 0 for v in self.levels):
+            raise ValueError(f"ml_to_pl_tz: levels must be a non-empty list of positive pressures in hPa, got {levels!r}")
+        if len(set(self.levels)) != len(self.levels):
+            raise ValueError(f"ml_to_pl_tz: duplicate levels in {levels!r}")
+        if interpolation not in native_pltz.COORDINATES:
+            raise ValueError(f"ml_to_pl_tz: interpolation must be one of {', '.join(map(repr, native_pltz.COORDINATES))}, got {interpolation!r}")
+        if len({temperature, specific_humidity, surface_pressure}) != 3:
+            raise ValueError(f"ml_to_pl_tz: temperature, specific_humidity and surface_pressure must be three params, got {temperature!r}, "
+                             f"{specific_humidity!r}, {surface_pressure!r}")
+        self.interpolation, self.msl, self.output_geopotential = interpolation, bool(msl), output_geopotential
+        self.temperature, self.specific_humidity = temperature, specific_humidity
+        self.surface_pressure, self.surface_geopotential = surface_pressure, surface_geopotential
+        self._set_table("ml_to_pl_tz", model_level_AB)
+        self.targets_pa = [float(v) * 100.0 for v in self.levels]
+        say_once(LOG, (type(self), "parity"), PLTZ_PARITY_NOTE)
+
+    def __repr__(self) -> str:
+        return f"ModelToPressureLevelsTZ(levels={self.levels}, interpolation={self.interpolation!r}, msl={self.msl})"
+
+    # ---- grouping: host bookkeeping, every ValueError before any launch ------------------------------------------------------------
+    def _plan(self, fields: list[Any]) -> tuple[list[Any], list[dict[str, Any]]]:
+        """``(passed through, [group])`` in first-seen order; a group: ``sp``, ``zs``, ``levels`` (top first) and the ``t`` / ``q`` fields
+        in that order."""
+        name, n_model = self.name, len(self.A) - 1
+        groups: dict[Any, dict[str, Any]] = {}
+        for field in fields:
+            identity, taken = identity_of(field, ("param", "levelist", "levtype"), ("variable",))
+            group = groups.setdefault(identity, dict(sp=None, zs=[], lnsp=False, t={}, q={}))
+            param = taken["param"]
+            group["lnsp"] = group["lnsp"] or param == "lnsp"
+            if param == self.surface_pressure:
+                if group["sp"] is not None:
+                    raise ValueError(f"Duplicate component {param} for {identity}")
+                group["sp"] = field
+            elif param in (self.temperature, self.specific_humidity) and taken["levtype"] == "ml":
+                level = self._model_level(param, taken["levelist"])
+                members = group["t" if param == self.temperature else "q"]
+                if level in members:
+                    raise ValueError(f"Duplicate component {param} for {identity} and level {level}")
+                members[level] = field
+            elif param == self.surface_geopotential:  # any levtype: MARS keeps it as z, ml, levelist 1
+                group["zs"].append(field)
+        plan = []
+        for identity, group in groups.items():
+            if not group["t"] and not group["q"]:
+                continue
+            for key, param in (("t", self.temperature), ("q", self.specific_humidity)):
+                if not group[key]:
+                    raise ValueError(f"{name}: no model-level fields of {param!r} for {sorted(identity)}")
+            levels, q_levels = sorted(group["t"]), sorted(group["q"])
+            if levels != q_levels:
+                raise ValueError(f"{name}: mixed level sets for {self.temperature} and {self.specific_humidity}: {levels} and {q_levels} "
+                                 f"(in {sorted(identity)})")
+            missing = sorted(set(range(levels[0], n_model + 1)) - set(levels))
+            if missing:
+                raise ValueError(f"{name}: the levels {levels[0]} .. {levels[-1]} of {self.temperature} have a gap down to the lowest level "
+                                 f"{n_model} of the A / B table: missing levels {missing} (in {sorted(identity)})")
+            if group["sp"] is None:
+                raise self._no_surface_pressure(identity, group["lnsp"])
+            if not group["zs"]:
+                raise ValueError(f"{name}: no surface geopotential {self.surface_geopotential!r} for the model-level fields of {sorted(identity)}")
+            if len(group["zs"]) > 1:
+                raise ValueError(f"{name}: {len(group['zs'])} fields of the surface geopotential {self.surface_geopotential!r} for {sorted(identity)}, "
+                                 f"one is needed: if geopotential_on_model_levels made them, give that filter another output= (its default "
+                                 f"output takes the surface field's place), or name the surface field with surface_geopotential=")
+            plan.append(dict(identity=identity, sp=group["sp"], zs=group["zs"][0], levels=levels, t=[group["t"][v] for v in levels],
+                             q=[group["q"][v] for v in levels]))
+        return list(fields), plan
+
+    def _interpolate(self, group: dict[str, Any]) -> Any:
+        """One stack of the group's 2 n + 2 fields (one type: float32 only if every field is), its t and q rows as two views, one launch."""
+        n = len(group["levels"])
+        stack = fields_to_stack([*group["t"], *group["q"], group["sp"], group["zs"]])
+        relayout = stack.layout == native.COLUMNS and PLTZ_COLUMNS_ROUTE == "fields"
+        if relayout:
+            stack = stack.to_layout(native.FIELDS)
+        if stack.layout == native.COLUMNS:
+            rows = lambda a, b: Stack(stack.data[:, a:b], stack.n_pts, b - a, native.COLUMNS)  # noqa: E731
+        else:
+            rows = lambda a, b: Stack(stack.data[a:b], stack.n_pts, b - a, native.FIELDS)  # noqa: E731
+        A, B = self._coefficients(stack.device)
+        out = t_z_on_pressure_levels(rows(0, n), rows(n, 2 * n), stack.level_view(2 * n), stack.level_view(2 * n + 1), A, B, self.targets_pa,
+                                     coordinate=self.interpolation, msl=self.msl)
+        return out.to_layout(native.COLUMNS) if relayout else out
+
+    def forward(self, data: Any) -> FieldList:
+        passed, plan = self._plan(list(data))
+        result = list(passed)
+        n_tgt = len(self.levels)
+        for group in plan:
+            out = self._interpolate(group)
+            template = group["t"][0]
+            for v, param in enumerate((self.temperature, self.output_geopotential)):
+                for i, level in enumerate(self.levels):
+                    result.append(new_field_from_stack(out, v * n_tgt + i, template=template, metadata=dict(param=param, levtype="pl", levelist=level)))
+            if self.msl:
+                result.append(new_field_from_stack(out, 2 * n_tgt, template=group["sp"], metadata=dict(param="msl", levtype="sfc")))
         return FieldList(result)

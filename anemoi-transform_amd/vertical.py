@@ -5,6 +5,8 @@ round trip — so ``interpolate_levels`` followed by a gather reads 13 levels pe
 surface geopotential: the variable IFS does not archive there, and the one ``interpolate_levels`` is most often asked for.
 ``interpolate_to_heights`` (``atx_heights_interpolate``, include/atx_heights.h) takes the variables of a model-level stack to heights above
 the ground or above the sea: that integral, the bracket search in it and the interpolation in one launch, without ``z`` in memory.
+``t_z_on_pressure_levels`` (``atx_pltz_interpolate``, include/atx_pltz.h) gives ``t`` and ``z`` on pressure levels with the IFS
+extrapolations under the ground, and ``msl``: the same integral, the bracket search in pressure and both results in one launch.
 """
 
 from __future__ import annotations
@@ -14,7 +16,7 @@ from typing import Any, Sequence
 import numpy as np
 import torch
 
-from . import native_geopotential, native_heights, native_levels
+from . import native_geopotential, native_heights, native_levels, native_pltz
 from .stack import COLUMNS, Stack
 
 G = 9.80665  # m / s^2: metres of geopotential height to geopotential (``filters.pointwise.g_gravitational_acceleration``)
@@ -129,4 +131,31 @@ def interpolate_to_heights(stack: Stack, t: Stack, q: Stack, sp: torch.Tensor, z
     native_heights.interpolate(stack.data, out.data, t.data, q.data, sp, zs, A, B, targets, n_pts=stack.n_pts, n_var=n_var, n_lev=n_lev,
                                n_tgt=targets.numel(), src_pitch=stack.pitch, t_pitch=t.pitch, q_pitch=q.pitch, out_pitch=out.pitch,
                                layout=stack.layout, reference=reference, outside=outside)
+    return out
+
+
+def t_z_on_pressure_levels(t: Stack, q: Stack, sp: torch.Tensor, zs: torch.Tensor, A: Any, B: Any, targets_pa: Sequence[float], *,
+                           coordinate: str = "linear", msl: bool = True) -> Stack:
+    """Temperature and geopotential at ``targets_pa`` (Pa, any order) with the IFS extrapolations under the ground, and the mean sea level
+    pressure (``atx_pltz_interpolate``, include/atx_pltz.h holds the statement).  ``t`` / ``q``: two stacks of the same shape, layout and
+    type, top level first, holding the LOWEST ``n_lev`` levels of the ``A`` / ``B`` table (the whole model, or a subset such as levels
+    60-137 that reaches the ground).  ``sp`` / ``zs``: the surface pressure (Pa) and the surface geopotential (m^2/s^2) of every point,
+    device tensors.  The result holds ``2 x len(targets_pa)`` rows in the layout and type of ``t`` — ``t`` at every target, then ``z`` at
+    every target — and with ``msl`` one more, the mean sea level pressure.  ``coordinate``: ``"linear"`` or ``"log"`` in pressure.  One
+    launch; the geopotential of the model levels is never written to memory."""
+    if (t.n_pts, t.n_lev, t.layout) != (q.n_pts, q.n_lev, q.layout):
+        raise ValueError(f"t and q differ in shape or layout: {t!r} and {q!r}")
+    if t.dtype != q.dtype:
+        raise ValueError(f"t and q differ in type: {t.dtype} and {q.dtype}")
+    coordinate = native_pltz.coordinate_code(coordinate)
+    if sp is None or zs is None:
+        raise ValueError("t and z on pressure levels need the surface pressure sp and the surface geopotential zs")
+    A, B = _device_f64(A, t.device), _device_f64(B, t.device)
+    assert A.shape == B.shape, "A and B coefficients must have same shape"
+    assert A.numel() >= t.n_lev + 1, f"model level AB-coefficients should have at least one more vertical level than the stack's {t.n_lev}"
+    targets = _device_f64(targets_pa if isinstance(targets_pa, torch.Tensor) else list(targets_pa), t.device).reshape(-1)
+    sp, zs = _per_point(sp, t.n_pts, t.dtype, "sp"), _per_point(zs, t.n_pts, t.dtype, "zs")
+    out = Stack.empty(t.n_pts, 2 * targets.numel() + (1 if msl else 0), t.dtype, t.device, t.layout)
+    native_pltz.interpolate(t.data, q.data, sp, zs, out.data, A, B, targets, n_pts=t.n_pts, n_lev=t.n_lev, n_tgt=targets.numel(), t_pitch=t.pitch,
+                            q_pitch=q.pitch, out_pitch=out.pitch, layout=t.layout, coordinate=coordinate, msl=msl)
     return out
