@@ -22,6 +22,11 @@ or above mean sea level (wind at 10 / 100 / 200 m, ``t`` and ``q`` at the height
 ``ml_to_pl_tz`` (below) is where ``t`` and ``z`` on pressure levels get what IFS gives them under the ground — the extrapolations that
 ``ml_to_pl`` leaves out — and where ``msl`` comes from: ``atx_pltz_interpolate`` (include/atx_pltz.h), the integral, the bracket search in
 pressure, both variables and the mean sea level pressure in ONE launch per group.
+
+``levels_to_coordinate`` and ``pl_to_hl`` (below) start from levels whose vertical coordinate is itself a field — pressure levels with
+``z`` archived on them, any levels with ``pt`` — where the filters above derive it from the surface pressure and the A / B table:
+``atx_coord_interpolate`` (include/atx_coord.h) reads the coordinate column of every point, checks that it is strictly monotone, and
+interpolates every variable of the group onto its surfaces in ONE launch per group.
 """
 
 from __future__ import annotations
@@ -37,8 +42,8 @@ from ..core import Filter, filter_registry, say_once
 from ..fields import FieldList, fields_to_stack, new_field_from_stack
 from ..grouping import identity_of
 from ..stack import Stack
-from .. import native_heights, native_pltz
-from ..vertical import geopotential_on_model_levels, interpolate_levels, interpolate_to_heights, t_z_on_pressure_levels
+from .. import native_coord, native_heights, native_pltz
+from ..vertical import G, geopotential_on_model_levels, interpolate_levels, interpolate_on_coordinate, interpolate_to_heights, t_z_on_pressure_levels
 from .domain import _one_field, _set_AB
 
 LOG = logging.getLogger(__name__)
@@ -607,3 +612,159 @@ class ModelToPressureLevelsTZ(_HybridLevelFilter):
             if self.msl:
                 result.append(new_field_from_stack(out, 2 * n_tgt, template=group["sp"], metadata=dict(param="msl", levtype="sfc")))
         return FieldList(result)
+
+
+COORD_PARITY_NOTE = ("levels_to_coordinate / pl_to_hl: the interpolation is an in-tree statement (include/atx_coord.h) — linear in the coordinate "
+                     "field between the two levels that bracket the target, nearest or missing outside, NaN where a point's coordinate column "
+                     "is not strictly monotone — and unpinned against earthkit-meteo, whose interpolation on a monotone coordinate it resembles")
+
+
+@filter_registry.register("levels_to_coordinate")
+class LevelsToCoordinate(Filter):
+    """Every param of ``levtype`` in a group (the fields that share every MARS key but ``param``, ``levelist`` and ``levtype``) — or the
+    ``params`` named — at the surfaces ``coordinate == levels[i]``, where ``coordinate`` is a param of the same group on the same levels:
+    ``pt`` for isentropes, archived ``z`` for geopotential surfaces.  The coordinate of every point is read from memory
+    (``atx_coord_interpolate``, include/atx_coord.h holds the statement): it may ascend or descend with ``levelist``, per point, and a
+    point where it does neither gets NaN.  The group's levels are sorted by ``levelist`` before stacking, so ordinary data is monotone.
+    ``outside``: ``"nearest"`` or ``"missing"`` (NaN) beyond the column's two ends.  ONE launch per group; the new fields are levels of
+    one resident stack per group, float32 only if every input of the group is, with ``levtype=out_levtype`` (default: the coordinate's
+    name) and ``levelist=levels[i]``.  Every input passes through.  An extension: the reference has no such filter."""
+
+    name = "levels_to_coordinate"
+
+    def __init__(self, *, coordinate: str = "pt", levels: Any, levtype: str = "pl", out_levtype: str | None = None, params: Any = None,
+                 outside: str = "nearest") -> None:
+        self._configure(coordinate, levels, levtype, coordinate if out_levtype is None else out_levtype, params, outside)
+        self.targets = [float(v) for v in self.levels]
+
+    def _configure(self, coordinate: str, levels: Any, levtype: str, out_levtype: str, params: Any, outside: str) -> None:
+        name = self.name
+        if isinstance(levels, (int, float)):
+            levels = [levels]
+        try:
+            values = [float(v) for v in levels]
+        except (TypeError, ValueError):
+            raise ValueError(f"{name}: levels must be numbers, got {levels!r}") from None
+        if not values or not all(np.isfinite(v) for v in values):
+            raise ValueError(f"{name}: levels must be a non-empty list of finite numbers, got {levels!r}")
+        self.levels = [_level_key(v) for v in values]
+        if len(set(self.levels)) != len(self.levels):
+            raise ValueError(f"{name}: duplicate levels in {levels!r}")
+        if outside not in native_coord.OUTSIDE:
+            raise ValueError(f"{name}: outside must be one of {', '.join(map(repr, native_coord.OUTSIDE))}, got {outside!r}")
+        self.coordinate, self.levtype, self.out_levtype, self.outside = coordinate, levtype, out_levtype, outside
+        self.params = None if params is None else ([params] if isinstance(params, str) else list(params))
+        if self.params is not None and coordinate in self.params:
+            raise ValueError(f"{name}: the coordinate {coordinate!r} is not one of the params it is interpolated on")
+        self.surface, self.surface_role = None, None  # (pl_to_hl: the param of the one sfc field, and "offset" or "floor")
+        say_once(LOG, (LevelsToCoordinate, "parity"), COORD_PARITY_NOTE)
+
+    def __repr__(self) -> str:
+        return f"{type(self).__name__}(coordinate={self.coordinate!r}, levels={self.levels}, levtype={self.levtype!r}, outside={self.outside!r})"
+
+    # ---- grouping: host bookkeeping, every ValueError before any launch ------------------------------------------------------------
+    def _plan(self, fields: list[Any]) -> tuple[list[Any], list[dict[str, Any]]]:
+        """``(passed through, [group])`` in first-seen order; a group: ``levels`` (sorted by levelist), ``coord`` (the coordinate's fields
+        in that order), ``by_param`` (``{param: fields in that order}``), each param's template and ``surface`` (a field or ``None``)."""
+        name = self.name
+        groups: dict[Any, dict[str, Any]] = {}
+        for field in fields:
+            identity, taken = identity_of(field, ("param", "levelist", "levtype"), ("variable",))
+            group = groups.setdefault(identity, dict(coord={}, by_param={}, templates={}, surface=[]))
+            param, levtype = taken["param"], taken["levtype"]
+            if self.surface is not None and param == self.surface and levtype == "sfc":
+                group["surface"].append(field)
+                continue
+            if levtype != self.levtype or not (param == self.coordinate or self.params is None or param in self.params):
+                continue
+            try:
+                level = _level_key(taken["levelist"])
+            except (TypeError, ValueError):
+                raise ValueError(f"{name}: field {param} of levtype {levtype!r} has levelist {taken['levelist']!r}") from None
+            members = group["coord"] if param == self.coordinate else group["by_param"].setdefault(param, {})
+            if level in members:
+                raise ValueError(f"Duplicate component {param} for {identity} and level {level}")
+            members[level] = field
+            if param != self.coordinate:
+                group["templates"].setdefault(param, field)  # the param's first field of the input
+        plan = []
+        for identity, group in groups.items():
+            if not group["by_param"]:
+                continue
+            first, levels = next((p, sorted(m, key=float)) for p, m in group["by_param"].items())
+            for param, members in group["by_param"].items():
+                if sorted(members, key=float) != levels:
+                    raise ValueError(f"{name}: mixed level sets for {first} and {param}: {levels} and {sorted(members, key=float)} "
+                                     f"(in {sorted(identity)}; params= selects what is interpolated)")
+            missing = [v for v in levels if v not in group["coord"]]
+            if missing:
+                raise ValueError(f"{name}: the coordinate {self.coordinate!r} has no field on levels {missing} of levtype {self.levtype!r}, "
+                                 f"which {first} has (in {sorted(identity)})")
+            if len(group["surface"]) > 1:
+                raise ValueError(f"{name}: {len(group['surface'])} sfc fields of the surface geopotential {self.surface!r} for {sorted(identity)}, "
+                                 f"one is needed")
+            if self.surface_role == "offset" and not group["surface"]:
+                raise ValueError(f"{name}: no sfc field of the surface geopotential {self.surface!r} for {sorted(identity)}: heights above the "
+                                 f"ground need it (reference='sea' does not)")
+            plan.append(dict(identity=identity, levels=levels, coord=[group["coord"][v] for v in levels], templates=group["templates"],
+                             by_param={param: [members[v] for v in levels] for param, members in group["by_param"].items()},
+                             surface=group["surface"][0] if group["surface"] else None))
+        return list(fields), plan
+
+    def _interpolate(self, group: dict[str, Any]) -> tuple[Any, torch.Tensor]:
+        """One stack of the group's fields (one type: float32 only if every field is) — the variables, the coordinate, the surface field —
+        its rows as views, one launch."""
+        n, params = len(group["levels"]), list(group["by_param"])
+        rows = [f for param in params for f in group["by_param"][param]] + group["coord"]
+        stack = fields_to_stack(rows + ([] if group["surface"] is None else [group["surface"]]))
+        if stack.layout == native.COLUMNS:
+            view = lambda a, b: Stack(stack.data[:, a:b], stack.n_pts, b - a, native.COLUMNS)  # noqa: E731
+        else:
+            view = lambda a, b: Stack(stack.data[a:b], stack.n_pts, b - a, native.FIELDS)  # noqa: E731
+        surface = None if group["surface"] is None else stack.level_view(len(rows))
+        return interpolate_on_coordinate(view(0, len(params) * n), view(len(params) * n, len(rows)), self.targets, n_var=len(params),
+                                         offset=surface if self.surface_role == "offset" else None,
+                                         floor=surface if self.surface_role == "floor" else None, outside=self.outside)
+
+    def forward(self, data: Any) -> FieldList:
+        passed, plan = self._plan(list(data))
+        result = list(passed)
+        n_tgt = len(self.levels)
+        unusable = None
+        for group in plan:
+            out, bad = self._interpolate(group)
+            count = bad.sum(dtype=torch.int64)
+            unusable = count if unusable is None else unusable + count
+            for v, param in enumerate(group["by_param"]):
+                template = group["templates"][param]
+                for i, level in enumerate(self.levels):
+                    result.append(new_field_from_stack(out, v * n_tgt + i, template=template, metadata=dict(levtype=self.out_levtype, levelist=level)))
+        if unusable is not None and int(unusable) > 0:  # (one read of one number per call, after every launch is queued)
+            LOG.warning("%s: the coordinate %r is not strictly monotone at %d points of %d groups: every result there is NaN", self.name,
+                        self.coordinate, int(unusable), len(plan))
+        return FieldList(result)
+
+
+@filter_registry.register("pl_to_hl")
+class PressureToHeightLevels(LevelsToCoordinate):
+    """``levels_to_coordinate`` spelled for heights: every param of ``levtype`` in a group at ``levels`` metres (geopotential metres,
+    ``z / g``; the targets the kernel sees are ``float64(h) * 9.80665``), from the ``geopotential`` param on the same levels — what ERA5
+    and every dataset on pressure levels archive, so hub-height wind is ``pl_to_hl(levels=[100], params=["u", "v"])``.
+    ``reference="ground"``: above the ground — the group's ONE ``sfc`` field of ``surface_geopotential`` is added to every target of a
+    point.  ``reference="sea"``: above mean sea level; where that field is present a height under the ground is NaN, and only under
+    this reference may a level be negative.  ``levtype="ml"`` works the same way on geopotential that is on model levels:
+    ``geopotential_on_model_levels | pl_to_hl(levtype="ml")``.  The new fields have ``levtype="hl"`` and ``levelist=<metres>``; the rest
+    is ``levels_to_coordinate``'s."""
+
+    name = "pl_to_hl"
+
+    def __init__(self, *, levels: Any = (10, 100, 200), reference: str = "ground", geopotential: str = "z", surface_geopotential: str = "z",
+                 levtype: str = "pl", params: Any = None, outside: str = "nearest") -> None:
+        if reference not in ("ground", "sea"):
+            raise ValueError(f"pl_to_hl: reference must be one of 'ground', 'sea', got {reference!r}")
+        self._configure(geopotential, list(levels) if isinstance(levels, tuple) else levels, levtype, "hl", params, outside)
+        if reference == "ground" and any(float(v) < 0 for v in self.levels):
+            raise ValueError(f"pl_to_hl: levels must not be negative above the ground (reference='sea' takes heights below sea level), got {levels!r}")
+        self.reference, self.geopotential = reference, geopotential
+        self.surface, self.surface_role = surface_geopotential, "offset" if reference == "ground" else "floor"
+        self.targets = list(np.array([float(v) for v in self.levels], dtype=np.float64) * np.float64(G))

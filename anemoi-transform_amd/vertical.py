@@ -7,6 +7,8 @@ surface geopotential: the variable IFS does not archive there, and the one ``int
 the ground or above the sea: that integral, the bracket search in it and the interpolation in one launch, without ``z`` in memory.
 ``t_z_on_pressure_levels`` (``atx_pltz_interpolate``, include/atx_pltz.h) gives ``t`` and ``z`` on pressure levels with the IFS
 extrapolations under the ground, and ``msl``: the same integral, the bracket search in pressure and both results in one launch.
+``interpolate_on_coordinate`` (``atx_coord_interpolate``, include/atx_coord.h) takes the variables of ANY stack of levels to surfaces of a
+second stack's values — ``z`` on pressure levels to heights, ``pt`` to isentropes: the coordinate column of every point is read, not derived.
 """
 
 from __future__ import annotations
@@ -16,7 +18,7 @@ from typing import Any, Sequence
 import numpy as np
 import torch
 
-from . import native_geopotential, native_heights, native_levels, native_pltz
+from . import native_coord, native_geopotential, native_heights, native_levels, native_pltz
 from .stack import COLUMNS, Stack
 
 G = 9.80665  # m / s^2: metres of geopotential height to geopotential (``filters.pointwise.g_gravitational_acceleration``)
@@ -159,3 +161,49 @@ def t_z_on_pressure_levels(t: Stack, q: Stack, sp: torch.Tensor, zs: torch.Tenso
     native_pltz.interpolate(t.data, q.data, sp, zs, out.data, A, B, targets, n_pts=t.n_pts, n_lev=t.n_lev, n_tgt=targets.numel(), t_pitch=t.pitch,
                             q_pitch=q.pitch, out_pitch=out.pitch, layout=t.layout, coordinate=coordinate, msl=msl)
     return out
+
+
+def interpolate_on_coordinate(stack: Stack, coord: Stack, targets: Sequence[float], *, n_var: int = 1, offset: torch.Tensor | None = None,
+                              floor: torch.Tensor | None = None, outside: str = "nearest") -> tuple[Stack, torch.Tensor]:
+    """``stack`` holds ``n_var`` variables of ``stack.n_lev // n_var`` levels each, variables adjacent; ``coord`` holds the coordinate of
+    every level at every point — the same levels, points, layout and type — strictly ascending or strictly descending along each point's
+    column, in either direction per point.  The result holds ``n_var x len(targets)`` rows in the layout and type of ``stack``: row
+    ``v * n_tgt + t`` is variable ``v`` where the coordinate equals ``targets[t]`` (float64, any order), linear in the coordinate between
+    the two levels that bracket it (``atx_coord_interpolate``, include/atx_coord.h holds the statement).  ``offset``: one value per point
+    added to every target ("above the ground": the surface geopotential); ``floor``: one value per point under which a target is NaN
+    ("above the sea but under the ground"); both device tensors or ``None``.  ``outside``: ``"nearest"`` or ``"missing"`` beyond the
+    column's two ends.  Returns ``(result, bad)``: ``bad`` is a uint8 device vector, 1 where a point's coordinate column is not strictly
+    monotone (a NaN, an equal pair, a turn) and every result of the point is NaN.  One launch — unless the column kernel refuses the
+    stack because one point's ``n_var`` columns do not fit the LDS of a workgroup (``NotImplementedError``): then the variables are
+    halved, down to a single one, and each part is launched into its own rows of the one result, as ``interpolate_levels`` does.  A
+    variable's result does not depend on the others, so the bits are those of one launch."""
+    if n_var < 1 or stack.n_lev % n_var:
+        raise ValueError(f"a stack of {stack.n_lev} rows does not hold {n_var} variables of equally many levels")
+    n_lev = stack.n_lev // n_var
+    if (coord.n_pts, coord.n_lev, coord.layout) != (stack.n_pts, n_lev, stack.layout):
+        raise ValueError(f"the coordinate does not hold the {n_lev} levels, the points or the layout of the variables: {coord!r} and {stack!r}")
+    if coord.dtype != stack.dtype:
+        raise ValueError(f"the variables and the coordinate differ in type: {stack.dtype} and {coord.dtype}")
+    outside = native_coord.outside_code(outside)
+    targets = _device_f64(targets if isinstance(targets, torch.Tensor) else list(targets), stack.device).reshape(-1)
+    offset = None if offset is None else _per_point(offset, stack.n_pts, stack.dtype, "offset")
+    floor = None if floor is None else _per_point(floor, stack.n_pts, stack.dtype, "floor")
+    n_tgt = targets.numel()
+    out = Stack.empty(stack.n_pts, n_var * n_tgt, stack.dtype, stack.device, stack.layout)
+    bad = torch.zeros(stack.n_pts, dtype=torch.uint8, device=stack.device)  # (zeros: no targets, no launch, nothing unusable reported)
+
+    def launch(first: int, count: int) -> None:
+        """Variables ``first .. first + count - 1``: views of the two column stacks that start at their rows and keep the pitch."""
+        src, dst = (stack.data[:, first * n_lev:], out.data[:, first * n_tgt:]) if first else (stack.data, out.data)
+        try:
+            native_coord.interpolate(src, coord.data, dst, targets, n_pts=stack.n_pts, n_var=count, n_lev=n_lev, n_tgt=n_tgt, src_pitch=stack.pitch,
+                                     coord_pitch=coord.pitch, out_pitch=out.pitch, layout=stack.layout, offset=offset, floor=floor, bad=bad,
+                                     outside=outside)
+        except NotImplementedError:
+            if stack.layout != COLUMNS or count == 1:
+                raise
+            launch(first, count // 2)
+            launch(first + count // 2, count - count // 2)
+
+    launch(0, n_var)
+    return out, bad
