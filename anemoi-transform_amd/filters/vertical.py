@@ -27,6 +27,10 @@ pressure, both variables and the mean sea level pressure in ONE launch per group
 ``z`` archived on them, any levels with ``pt`` — where the filters above derive it from the surface pressure and the A / B table:
 ``atx_coord_interpolate`` (include/atx_coord.h) reads the coordinate column of every point, checks that it is strictly monotone, and
 interpolates every variable of the group onto its surfaces in ONE launch per group.
+
+``vertical_integral`` (below) does not move values between levels, it REDUCES the column: total column water vapour, the integrated
+vapour transport, the mass-weighted mean of a layer, on model levels or on pressure levels — ``atx_integral_columns``
+(include/atx_integral.h), one launch per group.
 """
 
 from __future__ import annotations
@@ -42,8 +46,9 @@ from ..core import Filter, filter_registry, say_once
 from ..fields import FieldList, fields_to_stack, new_field_from_stack
 from ..grouping import identity_of
 from ..stack import Stack
-from .. import native_coord, native_heights, native_pltz
-from ..vertical import G, geopotential_on_model_levels, interpolate_levels, interpolate_on_coordinate, interpolate_to_heights, t_z_on_pressure_levels
+from .. import native_coord, native_heights, native_integral, native_pltz
+from ..vertical import (G, geopotential_on_model_levels, integrate_columns, interpolate_levels, interpolate_on_coordinate, interpolate_to_heights,
+                        t_z_on_pressure_levels)
 from .domain import _one_field, _set_AB
 
 LOG = logging.getLogger(__name__)
@@ -768,3 +773,151 @@ class PressureToHeightLevels(LevelsToCoordinate):
         self.reference, self.geopotential = reference, geopotential
         self.surface, self.surface_role = surface_geopotential, "offset" if reference == "ground" else "floor"
         self.targets = list(np.array([float(v) for v in self.levels], dtype=np.float64) * np.float64(G))
+
+
+INTEGRAL_PARITY_NOTE = ("vertical_integral: the column integral is an in-tree statement (include/atx_integral.h) — on model levels the finite-volume "
+                        "sum over the layers between half levels, on pressure levels the trapezoid between the levels above the ground and "
+                        "the lowest of them held down to the surface pressure, summed in blocks of 8 levels — and unpinned against "
+                        "earthkit-meteo / IFS")
+
+#: how a COLUMNS stack is served by ``vertical_integral``, per levtype: "columns" (the LDS-tile kernel on the stack as it is) or "fields"
+#: (relayout, then the FIELDS kernel, then relayout back).  Set to the route that measured faster (tools/integral_bench.py,
+#: profiles/integral_bench.json; DESIGN.md §3 "Column-integral kernel"), float32 / float64 on one MI355X: O1280 x 137 model levels, three
+#: outputs, "columns" 6.44 / 9.26 ms against 10.3 / 15.3 ms with the two relayouts; 0.25 degrees x 13 pressure levels, three outputs and
+#: a layer mean, "columns" 0.427 / 0.520 ms against 0.332 / 0.406 ms; run-to-run 8.6 / 5.8 %.
+INTEGRAL_COLUMNS_ROUTE = {"ml": "columns", "pl": "fields"}
+
+
+@filter_registry.register("vertical_integral")
+class VerticalIntegral(_HybridLevelFilter):
+    """Column integrals and layer means of a group (the fields that share every MARS key but ``param``, ``levelist`` and ``levtype``):
+    ``outputs={"tcwv": "q", "viwve": ["q", "u"], "viwvn": ["q", "v"]}`` names each new field and the param — or the two params whose
+    product — it integrates: ``1/g`` times the pressure integral (``kind="integral"``) or the pressure-weighted mean (``kind="mean"``),
+    over the whole column or over each of ``layers=[[850, 500], …]`` (hPa, either order).  ``levtype="ml"``: hybrid model levels with
+    ``model_level_AB`` as for ``ml_to_pl`` — the levels of a group must be one run of the table without a gap, which need not reach the
+    ground; ``levtype="pl"``: pressure levels, no table — levels under the ground weigh nothing, whatever they hold.  Every param of
+    ``outputs`` must hold the same levels, and the group exactly one ``surface_pressure`` field (Pa; ``lnsp`` is not taken in its place:
+    ``lnsp_to_sp | vertical_integral``).  ONE launch per group (``atx_integral_columns``, include/atx_integral.h holds the statement); the
+    new fields — ``param=<output name>``, with ``layers`` ``<name>_<top>_<bottom>`` in hPa as given, ``levtype="sfc"`` — are levels of one
+    resident stack per group, float32 only if every input is.  Every input passes through.  An extension: the reference has no such
+    filter."""
+
+    def __init__(self, *, outputs: Any, levtype: str = "ml", model_level_AB: Any = None, surface_pressure: str = "sp", layers: Any = None,
+                 kind: str = "integral") -> None:
+        self.name = "vertical_integral"
+        if levtype not in ("ml", "pl"):
+            raise ValueError(f"vertical_integral: levtype must be 'ml' or 'pl', got {levtype!r}")
+        if (levtype == "ml") != (model_level_AB is not None):
+            raise ValueError("vertical_integral: levtype='ml' needs model_level_AB, levtype='pl' takes no table")
+        if kind not in native_integral.KINDS:
+            raise ValueError(f"vertical_integral: kind must be one of {', '.join(map(repr, native_integral.KINDS))}, got {kind!r}")
+        if not isinstance(outputs, dict) or not outputs:
+            raise ValueError(f"vertical_integral: outputs must be a non-empty dict of name -> param or [param, param], got {outputs!r}")
+        self.outputs: dict[str, tuple[str, ...]] = {}
+        for name, factors in outputs.items():
+            factors = (factors,) if isinstance(factors, str) else tuple(factors)
+            if len(factors) not in (1, 2) or not all(isinstance(p, str) for p in factors):
+                raise ValueError(f"vertical_integral: output {name!r} must name one param or two, got {outputs[name]!r}")
+            self.outputs[str(name)] = factors
+        self.params = list(dict.fromkeys(p for factors in self.outputs.values() for p in factors))  # first named first
+        if surface_pressure in self.params:
+            raise ValueError(f"vertical_integral: the surface pressure {surface_pressure!r} is not one of the params it weighs")
+        self.terms = [(self.params.index(f[0]), self.params.index(f[1]) if len(f) == 2 else -1) for f in self.outputs.values()]
+        self.layers, self.bounds_pa = None, None
+        if layers is not None:
+            try:
+                self.layers = [(_level_key(a), _level_key(b)) for a, b in layers]
+            except (TypeError, ValueError):
+                raise ValueError(f"vertical_integral: layers must be pairs of pressures in hPa, got {layers!r}") from None
+            if not self.layers or not all(np.isfinite(float(v)) and float(v) >= 0 for pair in self.layers for v in pair) or any(a == b for a, b in self.layers):
+                raise ValueError(f"vertical_integral: layers must be a non-empty list of pairs of two different pressures in hPa, got {layers!r}")
+            self.bounds_pa = [(min(float(a), float(b)) * 100.0, max(float(a), float(b)) * 100.0) for a, b in self.layers]
+        self.levtype, self.kind, self.surface_pressure = levtype, kind, surface_pressure
+        if levtype == "ml":
+            self._set_table(self.name, model_level_AB)
+        say_once(LOG, (type(self), "parity"), INTEGRAL_PARITY_NOTE)
+
+    def __repr__(self) -> str:
+        return f"VerticalIntegral(outputs={self.outputs}, levtype={self.levtype!r}, layers={self.layers}, kind={self.kind!r})"
+
+    def output_names(self) -> list[str]:
+        """The params of the new fields in the order of the result's rows: output by output, layer by layer."""
+        if self.layers is None:
+            return list(self.outputs)
+        return [f"{name}_{a}_{b}" for name in self.outputs for a, b in self.layers]
+
+    # ---- grouping: host bookkeeping, every ValueError before any launch ------------------------------------------------------------
+    def _plan(self, fields: list[Any]) -> tuple[list[Any], list[dict[str, Any]]]:
+        """``(passed through, [group])`` in first-seen order; a group: ``sp``, ``levels`` (top first) and ``by_param``, the fields of every
+        param of ``outputs`` in that order."""
+        name = self.name
+        groups: dict[Any, dict[str, Any]] = {}
+        for field in fields:
+            identity, taken = identity_of(field, ("param", "levelist", "levtype"), ("variable",))
+            group = groups.setdefault(identity, dict(sp=[], lnsp=False, by_param={}))
+            param = taken["param"]
+            group["lnsp"] = group["lnsp"] or param == "lnsp"
+            if param == self.surface_pressure:
+                group["sp"].append(field)
+            elif param in self.params and taken["levtype"] == self.levtype:
+                if self.levtype == "ml":
+                    level = self._model_level(param, taken["levelist"])
+                else:
+                    try:
+                        level = _level_key(taken["levelist"])
+                    except (TypeError, ValueError):
+                        raise ValueError(f"{name}: pressure-level field {param} has levelist {taken['levelist']!r}") from None
+                members = group["by_param"].setdefault(param, {})
+                if level in members:
+                    raise ValueError(f"Duplicate component {param} for {identity} and level {level}")
+                members[level] = field
+        plan = []
+        for identity, group in groups.items():
+            if not group["by_param"]:
+                continue
+            first = next(iter(group["by_param"]))
+            levels = sorted(group["by_param"][first], key=float)
+            for param in self.params:
+                held = sorted(group["by_param"].get(param, {}), key=float)
+                if held != levels:
+                    raise ValueError(f"{name}: mixed level sets for {first} and {param}: {levels} and {held} (in {sorted(identity)})")
+            if self.levtype == "ml":
+                missing = sorted(set(range(levels[0], levels[-1] + 1)) - set(levels))
+                if missing:
+                    raise ValueError(f"{name}: the levels {levels[0]} .. {levels[-1]} of {first} are not one run of the A / B table: missing "
+                                     f"levels {missing} (in {sorted(identity)})")
+            if not group["sp"]:
+                raise self._no_surface_pressure(identity, group["lnsp"])
+            if len(group["sp"]) > 1:
+                raise ValueError(f"Duplicate component {self.surface_pressure} for {identity}")
+            plan.append(dict(identity=identity, sp=group["sp"][0], levels=levels,
+                             by_param={param: [group["by_param"][param][v] for v in levels] for param in self.params}))
+        return list(fields), plan
+
+    def _integrate(self, group: dict[str, Any]) -> Any:
+        """One stack of the group's fields (one type: float32 only if every field is) — the variables, then sp — one launch."""
+        levels, n = group["levels"], len(group["levels"])
+        rows = [f for param in self.params for f in group["by_param"][param]]
+        stack = fields_to_stack([*rows, group["sp"]])
+        relayout = stack.layout == native.COLUMNS and INTEGRAL_COLUMNS_ROUTE[self.levtype] == "fields"
+        if relayout:
+            stack = stack.to_layout(native.FIELDS)
+        data = stack.data[:, :len(rows)] if stack.layout == native.COLUMNS else stack.data[:len(rows)]
+        variables = Stack(data, stack.n_pts, len(rows), stack.layout)
+        if self.levtype == "ml":
+            A, B = (c[levels[0] - 1:levels[-1] + 1] for c in self._coefficients(stack.device))
+            table = dict(A=A, B=B)
+        else:
+            table = dict(levels_pa=[float(v) * 100.0 for v in levels])
+        out = integrate_columns(variables, stack.level_view(len(rows)), self.terms, self.bounds_pa, n_var=len(self.params), kind=self.kind, **table)
+        return out.to_layout(native.COLUMNS) if relayout else out
+
+    def forward(self, data: Any) -> FieldList:
+        passed, plan = self._plan(list(data))
+        result = list(passed)
+        names = self.output_names()
+        for group in plan:
+            out = self._integrate(group)
+            for row, name in enumerate(names):
+                result.append(new_field_from_stack(out, row, template=group["sp"], metadata=dict(param=name, levtype="sfc")))
+        return FieldList(result)

@@ -9,6 +9,8 @@ the ground or above the sea: that integral, the bracket search in it and the int
 extrapolations under the ground, and ``msl``: the same integral, the bracket search in pressure and both results in one launch.
 ``interpolate_on_coordinate`` (``atx_coord_interpolate``, include/atx_coord.h) takes the variables of ANY stack of levels to surfaces of a
 second stack's values — ``z`` on pressure levels to heights, ``pt`` to isentropes: the coordinate column of every point is read, not derived.
+``integrate_columns`` (``atx_integral_columns``, include/atx_integral.h) REDUCES the columns: ``1/g`` times the pressure integral of a
+variable or of a product of two, or the pressure-weighted mean of a layer, on model levels or on pressure levels.
 """
 
 from __future__ import annotations
@@ -18,7 +20,7 @@ from typing import Any, Sequence
 import numpy as np
 import torch
 
-from . import native_coord, native_geopotential, native_heights, native_levels, native_pltz
+from . import native_coord, native_geopotential, native_heights, native_integral, native_levels, native_pltz
 from .stack import COLUMNS, Stack
 
 G = 9.80665  # m / s^2: metres of geopotential height to geopotential (``filters.pointwise.g_gravitational_acceleration``)
@@ -207,3 +209,41 @@ def interpolate_on_coordinate(stack: Stack, coord: Stack, targets: Sequence[floa
 
     launch(0, n_var)
     return out, bad
+
+
+def integrate_columns(stack: Stack, sp: torch.Tensor, terms: Sequence[Any], bounds_pa: Sequence[Sequence[float]] | None, *, n_var: int, A: Any = None,
+                      B: Any = None, levels_pa: Any = None, kind: str = "integral") -> Stack:
+    """``stack`` holds ``n_var`` variables of ``stack.n_lev // n_var`` levels each, variables adjacent, top level first.  ``terms``: what is
+    integrated — a variable's index, or a pair ``(v1, v2)`` for the product of two (``q u`` for the vapour transport).  ``bounds_pa``: the
+    layers ``(top, bottom)`` in Pa, ``0 <= top < bottom``; ``None`` is the whole column, ``[(0, inf)]``.  ``A`` / ``B``: the ``n_lev + 1``
+    half-level coefficients of the rows (hybrid model levels: a run of the model's table), or ``levels_pa``: the ``n_lev`` pressures of
+    the rows, strictly increasing (pressure levels; levels under the ground weigh nothing and may hold NaN).  ``kind``: ``"integral"``,
+    ``1/g`` times the pressure integral, or ``"mean"``, the pressure-weighted mean of the layer (NaN where the layer is empty).  The
+    result holds ``len(terms) x len(bounds)`` rows in the layout and type of ``stack``: row ``t * n_bnd + b`` is term ``t`` over bound
+    ``b`` (``atx_integral_columns``, include/atx_integral.h holds the statement).  One launch; a column stack whose rows, weights and block
+    sums of ONE point exceed the LDS of a workgroup raises ``ValueError`` before any launch — splitting it is the caller's."""
+    if n_var < 1 or stack.n_lev % n_var:
+        raise ValueError(f"a stack of {stack.n_lev} rows does not hold {n_var} variables of equally many levels")
+    n_lev = stack.n_lev // n_var
+    kind = native_integral.kind_code(kind)
+    pairs = [(int(t), -1) if isinstance(t, (int, np.integer)) else (int(t[0]), int(t[1]) if len(t) > 1 else -1) for t in terms]
+    bounds = [(0.0, float("inf"))] if bounds_pa is None else [(float(top), float(bottom)) for top, bottom in bounds_pa]
+    if (levels_pa is None) == (A is None or B is None):
+        raise ValueError("integrate_columns: either A and B (hybrid model levels) or levels_pa (pressure levels)")
+    if levels_pa is None:
+        A, B = _device_f64(A, stack.device), _device_f64(B, stack.device)
+        if not A.numel() == B.numel() == n_lev + 1:
+            raise ValueError(f"integrate_columns: A and B must hold the {n_lev + 1} half levels of the stack's {n_lev} levels, got {A.numel()} and {B.numel()}")
+    else:
+        host = np.asarray(levels_pa.cpu() if isinstance(levels_pa, torch.Tensor) else levels_pa, dtype=np.float64).reshape(-1)
+        if host.size != n_lev or not (np.diff(host) > 0).all() or not np.isfinite(host).all():
+            raise ValueError(f"integrate_columns: levels_pa must be {n_lev} strictly increasing pressures, got {host.tolist()}")
+        levels_pa = _device_f64(host, stack.device)
+    sp = _per_point(sp, stack.n_pts, stack.dtype, "sp")
+    out = Stack.empty(stack.n_pts, len(pairs) * len(bounds), stack.dtype, stack.device, stack.layout)
+    try:
+        native_integral.columns(stack.data, sp, out.data, pairs, bounds, n_pts=stack.n_pts, n_var=n_var, n_lev=n_lev, src_pitch=stack.pitch,
+                                out_pitch=out.pitch, layout=stack.layout, A=A, B=B, levels_pa=levels_pa, kind=kind)
+    except NotImplementedError as refused:  # (raised by the library's validation: nothing was launched)
+        raise ValueError(f"integrate_columns: {refused}") from None
+    return out
