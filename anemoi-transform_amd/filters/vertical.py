@@ -31,6 +31,10 @@ interpolates every variable of the group onto its surfaces in ONE launch per gro
 ``vertical_integral`` (below) does not move values between levels, it REDUCES the column: total column water vapour, the integrated
 vapour transport, the mass-weighted mean of a layer, on model levels or on pressure levels — ``atx_integral_columns``
 (include/atx_integral.h), one launch per group.
+
+``crossing_level`` and ``extremum_level`` (below) SEARCH the column, which need not be monotone: the freezing level where there are
+inversions, the dynamic tropopause, cloud base and top, the jet level — ``atx_search_columns`` (include/atx_search.h), one launch per
+group.
 """
 
 from __future__ import annotations
@@ -48,7 +52,7 @@ from ..grouping import identity_of
 from ..stack import Stack
 from .. import native_coord, native_heights, native_integral, native_pltz
 from ..vertical import (G, geopotential_on_model_levels, integrate_columns, interpolate_levels, interpolate_on_coordinate, interpolate_to_heights,
-                        t_z_on_pressure_levels)
+                        search_columns, t_z_on_pressure_levels)
 from .domain import _one_field, _set_AB
 
 LOG = logging.getLogger(__name__)
@@ -921,3 +925,195 @@ class VerticalIntegral(_HybridLevelFilter):
             for row, name in enumerate(names):
                 result.append(new_field_from_stack(out, row, template=group["sp"], metadata=dict(param=name, levtype="sfc")))
         return FieldList(result)
+
+
+SEARCH_PARITY_NOTE = ("crossing_level / extremum_level: the search is an in-tree statement (include/atx_search.h) — the first step from the ground "
+                      "or from the top at which the search param crosses the value, linear inside the step; the first level of the extremum — "
+                      "and unpinned against earthkit-meteo and IFS, whose freezing level (deg0l) has further rules for a second warm layer")
+
+#: how a COLUMNS stack is served by ``crossing_level`` / ``extremum_level``, per levtype: "columns" (the LDS-tile kernel with the
+#: wave-cooperative search on the stack as it is) or "fields" (relayout, then the FIELDS kernel, then relayout back).  Set to the route
+#: that measured faster (tools/search_bench.py, profiles/search_bench.json; DESIGN.md §3 "Column-search kernel"), float32 / float64 on
+#: one MI355X, z, u, v out: O1280 x 137 model levels, the 273.15 K crossing "columns" 4.68 / 7.59 ms against 7.58 / 13.5 ms with the
+#: relayouts, the maximum 5.23 / 8.12 against 8.44 / 14.3 ms; 0.25 degrees x 13 pressure levels, 0.293 / 0.349 against 0.265 / 0.327 ms
+#: and 0.282 / 0.329 against 0.254 / 0.351 ms — differences of 10 % under a run-to-run spread of 13 - 19 %: no route is shown faster
+#: there, and the stack stays as it is.  Height levels were not measured.
+SEARCH_COLUMNS_ROUTE = {"ml": "columns", "pl": "columns", "hl": "columns"}
+
+LEVELIST = "levelist"  # the reserved source of an output: the levelist at the answer, interpolated as a variable is
+
+
+class _ColumnSearch(Filter):
+    """What ``crossing_level`` and ``extremum_level`` share: a group is the fields that share every MARS key but ``param``, ``levelist``
+    and ``levtype``; its ``search`` param and every source of ``outputs`` on ``levtype`` must hold the same levels, which are sorted by
+    ``levelist`` before stacking.  ``start``: the end of the column the scan starts from — the ground is the largest ``levelist`` on
+    ``pl`` and ``ml``, the smallest on ``hl``.  ONE launch per group; the new fields (``levtype="sfc"``) are levels of one resident stack
+    per group, float32 only if every input is.  Every input passes through."""
+
+    name = "column_search"
+
+    def _configure(self, search: str, outputs: Any, levtype: str, start: str, count: Any) -> None:
+        name = self.name
+        if levtype not in SEARCH_COLUMNS_ROUTE:
+            raise ValueError(f"{name}: levtype must be one of {', '.join(map(repr, SEARCH_COLUMNS_ROUTE))}, got {levtype!r}")
+        if start not in ("ground", "top"):
+            raise ValueError(f"{name}: start must be one of 'ground', 'top', got {start!r}")
+        if not isinstance(outputs, dict) or not all(isinstance(k, str) and isinstance(v, str) for k, v in outputs.items()):
+            raise ValueError(f"{name}: outputs must be a dict of name -> param (or 'levelist'), got {outputs!r}")
+        if count is not None and not isinstance(count, str):
+            raise ValueError(f"{name}: count must name the new field, got {count!r}")
+        if not outputs and count is None:
+            raise ValueError(f"{name}: no outputs and no count: nothing would be written")
+        if count is not None and count in outputs:
+            raise ValueError(f"{name}: the count {count!r} is also one of the outputs")
+        self.search, self.outputs, self.levtype, self.start, self.count = search, dict(outputs), levtype, start, count
+        self.variables = [source for source in self.outputs.values() if source != LEVELIST]  # one per output that is not the levelist
+        self.with_levelist = LEVELIST in self.outputs.values()
+        # ground last on pl / ml (the rows are sorted by levelist), first on hl
+        ground_first = levtype == "hl"
+        self.direction = "forward" if (start == "ground") == ground_first else "backward"
+        self.values: list[Any] = []
+        say_once(LOG, (_ColumnSearch, "parity"), SEARCH_PARITY_NOTE)
+
+    def output_names(self) -> list[str]:
+        """The params of the new fields in their order: output by output, value by value, then the count's."""
+        names = list(self.outputs) + ([] if self.count is None else [self.count])
+        if len(self.values) <= 1:
+            return names
+        return [f"{name}_{value}" for name in names for value in self.values]
+
+    # ---- grouping: host bookkeeping, every ValueError before any launch ------------------------------------------------------------
+    def _plan(self, fields: list[Any]) -> tuple[list[Any], list[dict[str, Any]]]:
+        """``(passed through, [group])`` in first-seen order; a group: ``levels`` (sorted by levelist) and ``by_param``, the fields of
+        the search param and of every source in that order."""
+        name, wanted = self.name, {self.search, *self.variables}
+        groups: dict[Any, dict[str, dict[Any, Any]]] = {}
+        for field in fields:
+            identity, taken = identity_of(field, ("param", "levelist", "levtype"), ("variable",))
+            group = groups.setdefault(identity, {})
+            if taken["levtype"] != self.levtype or taken["param"] not in wanted:
+                continue
+            try:
+                level = _level_key(taken["levelist"])
+            except (TypeError, ValueError):
+                raise ValueError(f"{name}: field {taken['param']} of levtype {self.levtype!r} has levelist {taken['levelist']!r}") from None
+            members = group.setdefault(taken["param"], {})
+            if level in members:
+                raise ValueError(f"Duplicate component {taken['param']} for {identity} and level {level}")
+            members[level] = field
+        plan = []
+        for identity, group in groups.items():
+            if not group:
+                continue
+            if self.search not in group:
+                raise ValueError(f"{name}: no fields of the search param {self.search!r} on levtype {self.levtype!r} for {sorted(identity)}")
+            levels = sorted(group[self.search], key=float)
+            for param in self.variables:
+                if param not in group:
+                    raise ValueError(f"{name}: no fields of the output param {param!r} on levtype {self.levtype!r} for {sorted(identity)}")
+                if sorted(group[param], key=float) != levels:
+                    raise ValueError(f"{name}: mixed level sets for {self.search} and {param}: {levels} and {sorted(group[param], key=float)} "
+                                     f"(in {sorted(identity)})")
+            plan.append(dict(identity=identity, levels=levels, by_param={param: [members[v] for v in levels] for param, members in group.items()}))
+        return list(fields), plan
+
+    def _search(self, group: dict[str, Any]) -> tuple[Any, int]:
+        """One stack of the group's fields (one type: float32 only if every field is) — a variable per output, then the search column —
+        its rows as views, one launch; the count, where asked, goes into the spare rows of the result.  Returns the result and the rows
+        of the kernel's own outputs."""
+        n, n_var = len(group["levels"]), len(self.variables)
+        stack = fields_to_stack([f for param in self.variables for f in group["by_param"][param]] + group["by_param"][self.search])
+        relayout = stack.layout == native.COLUMNS and SEARCH_COLUMNS_ROUTE[self.levtype] == "fields"
+        if relayout:
+            stack = stack.to_layout(native.FIELDS)
+        if stack.layout == native.COLUMNS:
+            view = lambda a, b: Stack(stack.data[:, a:b], stack.n_pts, b - a, native.COLUMNS)  # noqa: E731
+        else:
+            view = lambda a, b: Stack(stack.data[a:b], stack.n_pts, b - a, native.FIELDS)  # noqa: E731
+        n_tgt = max(1, len(self.values))
+        out, counted = search_columns(view(0, n_var * n) if n_var else None, view(n_var * n, (n_var + 1) * n), self.values, n_var=n_var,
+                                      direction=self.direction, mode=self.mode, count=self.count is not None,
+                                      level_values=[float(v) for v in group["levels"]] if self.with_levelist else None,
+                                      spare_rows=n_tgt if self.count is not None else 0)
+        rows = (n_var + self.with_levelist) * n_tgt
+        if counted is not None:
+            for t in range(n_tgt):
+                out.level_view(rows + t).copy_(counted[:, t])
+        return (out.to_layout(native.COLUMNS) if relayout else out), rows
+
+    def forward(self, data: Any) -> FieldList:
+        passed, plan = self._plan(list(data))
+        result = list(passed)
+        n_tgt = max(1, len(self.values))
+        variable_row = {}
+        for name, source in self.outputs.items():  # the kernel's rows: the variables in the order of outputs, the levelist last
+            variable_row[name] = len(self.variables) if source == LEVELIST else len([k for k in variable_row if self.outputs[k] != LEVELIST])
+        names = self.output_names()
+        for group in plan:
+            out, rows = self._search(group)
+            first = [variable_row[name] * n_tgt for name in self.outputs] + ([] if self.count is None else [rows])
+            for i, name in enumerate(names):
+                source = ([*self.outputs.values()] + [LEVELIST])[i // n_tgt]
+                template = group["by_param"][self.search if source == LEVELIST else source][0]
+                result.append(new_field_from_stack(out, first[i // n_tgt] + i % n_tgt, template=template,
+                                                   metadata=dict(param=name, levtype="sfc", levelist=None)))
+        return FieldList(result)
+
+
+@filter_registry.register("crossing_level")
+class CrossingLevel(_ColumnSearch):
+    """The first level, from the ground or from the top, at which ``search`` crosses each of ``values``, and what ``outputs`` name there:
+    ``crossing_level(search="t", values=[273.15], outputs={"deg0l": "z"})`` is the height of the freezing level where the column has
+    inversions, which ``levels_to_coordinate`` refuses; ``search="pv", values=[2e-6], start="top", outputs={"ptrop": "levelist"}`` the
+    dynamic tropopause; a ``cc`` threshold from either end cloud base and cloud top.  ``sense``: ``"rising"`` / ``"falling"`` ALONG THE
+    SCAN (from ``start``), or ``"any"``.  An output's source is a param of the group on the same levels, or ``"levelist"``; every output
+    is linear in ``search`` inside the step that crosses, NaN where no step does.  With several ``values`` the new fields are
+    ``<name>_<value>``.  ``count="name"``: one more field, the number of crossings of the asked sense in the whole column (255 at most).
+    An extension: the reference has no such filter."""
+
+    name = "crossing_level"
+    SENSES = {"any": "any", "rising": "up", "falling": "down"}
+
+    def __init__(self, *, search: str = "t", values: Any = (273.15,), start: str = "ground", sense: str = "any", outputs: Any = None,
+                 levtype: str = "pl", count: Any = None) -> None:
+        if sense not in self.SENSES:
+            raise ValueError(f"{self.name}: sense must be one of {', '.join(map(repr, self.SENSES))}, got {sense!r}")
+        self._configure(search, {} if outputs is None else outputs, levtype, start, count)
+        if isinstance(values, (int, float)):
+            values = [values]
+        try:
+            numbers = [float(v) for v in values]
+        except (TypeError, ValueError):
+            raise ValueError(f"{self.name}: values must be numbers, got {values!r}") from None
+        if not numbers or not all(np.isfinite(v) for v in numbers):
+            raise ValueError(f"{self.name}: values must be a non-empty list of finite numbers, got {values!r}")
+        self.values = [_level_key(v) for v in numbers]
+        if len(set(self.values)) != len(self.values):
+            raise ValueError(f"{self.name}: duplicate values in {values!r}")
+        self.sense, self.mode = sense, self.SENSES[sense]
+
+    def __repr__(self) -> str:
+        return f"CrossingLevel(search={self.search!r}, values={self.values}, start={self.start!r}, sense={self.sense!r}, levtype={self.levtype!r})"
+
+
+@filter_registry.register("extremum_level")
+class ExtremumLevel(_ColumnSearch):
+    """The level of the maximum (``kind="maximum"``) or minimum of ``search`` over a column, the first from ``start`` among equals, NaN
+    levels apart, and what ``outputs`` name there, copied: ``extremum_level(search="ws", outputs={"zjet": "z", "ujet": "u"})`` is the
+    jet level.  An output's source is a param of the group on the same levels, or ``"levelist"``.  ``count="name"``: one more field, the
+    number of levels equal to the extremum.  It takes no ``values``.  An extension: the reference has no such filter."""
+
+    name = "extremum_level"
+    KINDS = {"maximum": "max", "minimum": "min"}
+
+    def __init__(self, *, search: str = "ws", kind: str = "maximum", start: str = "ground", outputs: Any = None, levtype: str = "pl",
+                 count: Any = None, values: Any = None) -> None:
+        if values is not None:
+            raise ValueError(f"{self.name}: an extremum takes no values, got {values!r} (crossing_level does)")
+        if kind not in self.KINDS:
+            raise ValueError(f"{self.name}: kind must be one of {', '.join(map(repr, self.KINDS))}, got {kind!r}")
+        self._configure(search, {} if outputs is None else outputs, levtype, start, count)
+        self.kind, self.mode = kind, self.KINDS[kind]
+
+    def __repr__(self) -> str:
+        return f"ExtremumLevel(search={self.search!r}, kind={self.kind!r}, start={self.start!r}, levtype={self.levtype!r})"

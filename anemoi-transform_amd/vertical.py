@@ -11,6 +11,9 @@ extrapolations under the ground, and ``msl``: the same integral, the bracket sea
 second stack's values — ``z`` on pressure levels to heights, ``pt`` to isentropes: the coordinate column of every point is read, not derived.
 ``integrate_columns`` (``atx_integral_columns``, include/atx_integral.h) REDUCES the columns: ``1/g`` times the pressure integral of a
 variable or of a product of two, or the pressure-weighted mean of a layer, on model levels or on pressure levels.
+``search_columns`` (``atx_search_columns``, include/atx_search.h) SEARCHES the columns, which need not be monotone: the first step from
+either end at which a search variable crosses a value — the freezing level, the dynamic tropopause, cloud base — or the level of its
+maximum or minimum — the jet level — and the variables of a stack there.
 """
 
 from __future__ import annotations
@@ -20,7 +23,7 @@ from typing import Any, Sequence
 import numpy as np
 import torch
 
-from . import native_coord, native_geopotential, native_heights, native_integral, native_levels, native_pltz
+from . import native_coord, native_geopotential, native_heights, native_integral, native_levels, native_pltz, native_search
 from .stack import COLUMNS, Stack
 
 G = 9.80665  # m / s^2: metres of geopotential height to geopotential (``filters.pointwise.g_gravitational_acceleration``)
@@ -247,3 +250,65 @@ def integrate_columns(stack: Stack, sp: torch.Tensor, terms: Sequence[Any], boun
     except NotImplementedError as refused:  # (raised by the library's validation: nothing was launched)
         raise ValueError(f"integrate_columns: {refused}") from None
     return out
+
+
+def search_columns(stack: Stack | None, search: Stack, targets: Sequence[float] | None, *, n_var: int = 1, direction: str = "forward",
+                   mode: str = "any", level_values: Any = None, count: bool = False, spare_rows: int = 0) -> tuple[Stack | None, torch.Tensor | None]:
+    """``stack`` holds ``n_var`` variables of ``stack.n_lev // n_var`` levels each, variables adjacent (``None`` with ``n_var=0``);
+    ``search`` holds the search variable of every level at every point — the same levels, points, layout and type.  Nothing about a
+    column is checked: it may rise, fall, turn and hold NaN.  ``direction``: ``"forward"`` reads row 0 first, ``"backward"`` the last row.
+    ``mode``: ``"up"`` / ``"down"`` / ``"any"`` — the FIRST step in that order at which the search variable crosses ``targets[t]``
+    (float64, any order) rising, falling or either way along the scan, every variable linear in the search variable inside the step;
+    NaN where nothing crosses — or ``"max"`` / ``"min"``: the first level in that order of the column's extremum over what is not NaN,
+    its values copied (one result; ``targets`` is ignored).  ``level_values``: one number per level, the same for every point (pressures,
+    level numbers): one more variable, the last of the result.  The result holds ``(n_var + 1 if level_values) x n_tgt`` rows in the
+    layout and type of ``search``: row ``v * n_tgt + t`` is variable ``v`` at ``targets[t]`` (``None`` where there is no such row).
+    ``count=True``: also a uint8 device tensor ``[n_pts, n_tgt]``, the steps of the asked kind in the whole column (the rows equal to
+    the extremum), saturating at 255 — 0: nothing crosses, above 1: the first is not the only one (``atx_search_columns``,
+    include/atx_search.h holds the statement).  One launch — unless the column kernel refuses the stack because one point's ``n_var``
+    columns do not fit the LDS of a workgroup (``NotImplementedError``): then the variables are halved, down to a single one, and each
+    part is launched into its own rows of the one result, as ``interpolate_on_coordinate`` does.  A variable's result does not depend on
+    the others, so the bits are those of one launch.  ``spare_rows``: that many more rows at the end of the result, left unwritten for the
+    caller (the filters keep the count there, so that a group's new fields are levels of one stack)."""
+    n_lev = search.n_lev
+    if n_var < 0 or (n_var == 0) != (stack is None) or (stack is not None and stack.n_lev != n_var * n_lev):
+        raise ValueError(f"search_columns: {n_var} variables of the search column's {n_lev} levels are not the stack {stack!r}")
+    if stack is not None and ((stack.n_pts, stack.layout) != (search.n_pts, search.layout) or stack.dtype != search.dtype):
+        raise ValueError(f"search_columns: the variables and the search column differ in points, layout or type: {stack!r} and {search!r}")
+    direction, mode = native_search.direction_code(direction), native_search.mode_code(mode)
+    extremum = mode in (native_search.MAX, native_search.MIN)
+    if extremum:
+        targets, n_tgt = None, 1
+    else:
+        targets = _device_f64(targets if isinstance(targets, torch.Tensor) else list(targets), search.device).reshape(-1)
+        n_tgt = targets.numel()
+    if level_values is not None:
+        level_values = _device_f64(level_values, search.device).reshape(-1)
+        if level_values.numel() != n_lev:
+            raise ValueError(f"search_columns: level_values must hold the {n_lev} levels of the search column, got {level_values.numel()}")
+    n_out = n_var + (level_values is not None)
+    if n_out == 0 and not count:
+        raise ValueError("search_columns: no variable, no level_values and no count: nothing would be written")
+    n_pts, columns = search.n_pts, search.layout == COLUMNS
+    out = Stack.empty(n_pts, n_out * n_tgt + spare_rows, search.dtype, search.device, search.layout) if n_out + spare_rows else None
+    counted = torch.zeros(n_pts * n_tgt, dtype=torch.uint8, device=search.device) if count else None  # (zeros: no targets, no launch)
+
+    def launch(first: int, n: int) -> None:
+        """Variables ``first .. first + n - 1``: views of the two column stacks that start at their rows and keep the pitch; the part
+        that holds the last variable takes level_values, whose rows follow it, and the first part the count."""
+        src = None if stack is None else (stack.data[:, first * n_lev:] if first else stack.data)
+        dst = None if not n_out else (out.data[:, first * n_tgt:] if first else out.data)
+        try:
+            native_search.columns(src, search.data, dst, targets, n_pts=n_pts, n_var=n, n_lev=n_lev, n_tgt=n_tgt, src_pitch=0 if stack is None else stack.pitch,
+                                  search_pitch=search.pitch, out_pitch=0 if out is None else out.pitch, layout=search.layout, direction=direction,
+                                  mode=mode, level_values=level_values if first + n == n_var else None, count=counted if first == 0 else None)
+        except NotImplementedError:
+            if not columns or n <= 1:
+                raise
+            launch(first, n // 2)
+            launch(first + n // 2, n - n // 2)
+
+    launch(0, n_var)
+    if counted is not None:
+        counted = counted.view(n_pts, n_tgt) if columns else counted.view(n_tgt, n_pts).t()
+    return out, counted
