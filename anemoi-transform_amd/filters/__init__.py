@@ -14,6 +14,7 @@ Registered names:
                   levels_to_coordinate, pl_to_hl             (levels to surfaces of a coordinate param, filters/vertical.py)
                   vertical_integral                          (column integrals and layer means, filters/vertical.py)
                   crossing_level, extremum_level             (the first crossing of a column, its extremum, filters/vertical.py)
+                  parcel_ascent                              (CAPE, CIN and the LCL of a lifted parcel, filters/vertical.py)
   tabular         irregular_to_grid, assign_to_grid, superob (observation tables onto a grid, filters/tabular.py)
                   add_forcings, add_azimuth, add_msg_angles, radiance_to_brightness_temperature, add_healpix,
                   fill_orography, geopotential_to_height_tabular, apply_column_transformations

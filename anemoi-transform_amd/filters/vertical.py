@@ -35,6 +35,10 @@ vapour transport, the mass-weighted mean of a layer, on model levels or on press
 ``crossing_level`` and ``extremum_level`` (below) SEARCH the column, which need not be monotone: the freezing level where there are
 inversions, the dynamic tropopause, cloud base and top, the jet level — ``atx_search_columns`` (include/atx_search.h), one launch per
 group.
+
+``parcel_ascent`` (below) FOLLOWS an air parcel through the column of ``t`` and ``q``: CAPE, CIN and the lifting condensation level of
+the lowest or of the most unstable parcel, on model levels or on pressure levels — ``atx_parcel_columns`` (include/atx_parcel.h), one
+launch per group.
 """
 
 from __future__ import annotations
@@ -50,9 +54,9 @@ from ..core import Filter, filter_registry, say_once
 from ..fields import FieldList, fields_to_stack, new_field_from_stack
 from ..grouping import identity_of
 from ..stack import Stack
-from .. import native_coord, native_heights, native_integral, native_pltz
+from .. import native_coord, native_heights, native_integral, native_parcel, native_pltz
 from ..vertical import (G, geopotential_on_model_levels, integrate_columns, interpolate_levels, interpolate_on_coordinate, interpolate_to_heights,
-                        search_columns, t_z_on_pressure_levels)
+                        lift_parcels, search_columns, t_z_on_pressure_levels)
 from .domain import _one_field, _set_AB
 
 LOG = logging.getLogger(__name__)
@@ -1117,3 +1121,89 @@ class ExtremumLevel(_ColumnSearch):
 
     def __repr__(self) -> str:
         return f"ExtremumLevel(search={self.search!r}, kind={self.kind!r}, start={self.start!r}, levtype={self.levtype!r})"
+
+
+PARCEL_PARITY_NOTE = ("parcel_ascent: the ascent is an in-tree statement (include/atx_parcel.h) — Bolton's T_L and theta_e, the pseudo-adiabat of "
+                      "constant theta_e solved per level, trapezoids of the virtual-temperature buoyancy in ln p split at its zeros — and unpinned "
+                      "against earthkit-meteo, metpy and IFS, whose cape follows parcel rules of its own")
+
+#: how a COLUMNS stack is served by ``parcel_ascent``, per levtype: "columns" (the LDS-tile kernel with a lane per (point, level) on the
+#: stack as it is) or "fields" (relayout, then the FIELDS kernel, then relayout back).  Set to the route that measured faster
+#: (tools/parcel_bench.py, profiles/parcel_bench.json; DESIGN.md §3 "Parcel kernel"), float32 / float64 on one MI355X, the lowest parcel:
+#: O1280 x 137 model levels "columns" 97.0 / 92.8 ms against 57.0 / 60.2 ms with the relayouts; 0.25 degrees x 13 pressure levels 1.99 /
+#: 2.00 against 1.60 / 1.62 ms — differences of 20 - 41 % over a run-to-run spread of 0.1 - 2.4 %.  In the field-major kernel the 64 lanes
+#: of a wave stand at ONE level, so a level below the LCL skips its Newton steps for the whole wave; in the column kernel a wave holds
+#: levels of both kinds and runs them for all.  The most unstable parcel was not measured.
+PARCEL_COLUMNS_ROUTE = {"ml": "fields", "pl": "fields"}
+
+
+@filter_registry.register("parcel_ascent")
+class ParcelAscent(_HybridLevelFilter):
+    """CAPE, CIN and the lifting condensation level of a group (the fields that share every MARS key but ``param``, ``levelist`` and
+    ``levtype``): ``outputs={"cape": "cape", "cin": "cin", "plcl": "plcl"}`` names, for each of ``cape``, ``cin`` (J / kg, <= 0, NaN where
+    the parcel is nowhere buoyant), ``plcl`` (Pa), ``tlcl`` (K) and ``pstart`` (Pa) that is wanted, the param of the new field.
+    ``parcel="lowest"``: the parcel of the lowest level above the ground; ``"most-unstable"``: of the level of the largest theta_e in the
+    lowest ``depth`` hPa.  Levels above ``top`` hPa take no part.  ``levtype="ml"``: hybrid model levels with ``model_level_AB`` as for
+    ``ml_to_pl`` — the levels of a group must be one run of the table without a gap; ``levtype="pl"``: pressure levels, no table — levels
+    under the ground take no part, whatever they hold.  ``temperature`` and ``specific_humidity`` must hold the same levels, and the
+    group exactly one ``surface_pressure`` field (Pa; ``lnsp`` is not taken in its place: ``lnsp_to_sp | parcel_ascent``).  ONE launch per
+    group (``atx_parcel_columns``, include/atx_parcel.h holds the statement); the new fields, ``levtype="sfc"``, are levels of one resident
+    stack per group, float32 only if every input is.  Every input passes through.  An extension: the reference has no such filter."""
+
+    def __init__(self, *, outputs: Any = None, levtype: str = "pl", model_level_AB: Any = None, temperature: str = "t", specific_humidity: str = "q",
+                 surface_pressure: str = "sp", parcel: str = "lowest", depth: float = 300, top: float = 50) -> None:
+        self.name = "parcel_ascent"
+        if levtype not in ("ml", "pl"):
+            raise ValueError(f"parcel_ascent: levtype must be 'ml' or 'pl', got {levtype!r}")
+        if (levtype == "ml") != (model_level_AB is not None):
+            raise ValueError("parcel_ascent: levtype='ml' needs model_level_AB, levtype='pl' takes no table")
+        if parcel not in native_parcel.PARCELS:
+            raise ValueError(f"parcel_ascent: parcel must be one of {', '.join(map(repr, native_parcel.PARCELS))}, got {parcel!r}")
+        outputs = {"cape": "cape", "cin": "cin", "plcl": "plcl"} if outputs is None else outputs
+        if not isinstance(outputs, dict) or not outputs or not all(isinstance(v, str) for v in outputs.values()):
+            raise ValueError(f"parcel_ascent: outputs must be a non-empty dict of output -> param, got {outputs!r}")
+        unknown = [name for name in outputs if name not in native_parcel.OUTPUTS]
+        if unknown:
+            raise ValueError(f"parcel_ascent: unknown outputs {unknown}: the outputs are {', '.join(native_parcel.OUTPUTS)}")
+        if not (np.isfinite(float(depth)) and float(depth) >= 0 and np.isfinite(float(top)) and float(top) >= 0):
+            raise ValueError(f"parcel_ascent: depth and top must be pressures in hPa, >= 0, got {depth!r} and {top!r}")
+        self.outputs = {str(k): v for k, v in outputs.items()}
+        self.params = [temperature, specific_humidity]
+        if surface_pressure in self.params or temperature == specific_humidity:
+            raise ValueError(f"parcel_ascent: temperature, specific_humidity and surface_pressure must be three params, got {self.params + [surface_pressure]}")
+        self.levtype, self.parcel, self.surface_pressure = levtype, parcel, surface_pressure
+        self.depth_pa, self.top_pa = float(depth) * 100.0, float(top) * 100.0
+        if levtype == "ml":
+            self._set_table(self.name, model_level_AB)
+        say_once(LOG, (type(self), "parity"), PARCEL_PARITY_NOTE)
+
+    def __repr__(self) -> str:
+        return f"ParcelAscent(outputs={self.outputs}, levtype={self.levtype!r}, parcel={self.parcel!r})"
+
+    _plan = VerticalIntegral._plan  # the same groups: every param on the same levels, one run of the table, one surface pressure
+
+    def _lift(self, group: dict[str, Any]) -> Any:
+        """One stack of the group's fields (one type: float32 only if every field is) — t, then q, then sp — one launch."""
+        levels, n = group["levels"], len(group["levels"])
+        stack = fields_to_stack([*(f for param in self.params for f in group["by_param"][param]), group["sp"]])
+        relayout = stack.layout == native.COLUMNS and PARCEL_COLUMNS_ROUTE[self.levtype] == "fields"
+        if relayout:
+            stack = stack.to_layout(native.FIELDS)
+        rows = lambda first: stack.data[:, first:first + n] if stack.layout == native.COLUMNS else stack.data[first:first + n]  # noqa: E731
+        t, q = (Stack(rows(first), stack.n_pts, n, stack.layout) for first in (0, n))
+        if self.levtype == "ml":
+            A, B = (c[levels[0] - 1:levels[-1] + 1] for c in self._coefficients(stack.device))
+            table = dict(A=A, B=B)
+        else:
+            table = dict(levels_pa=[float(v) * 100.0 for v in levels])
+        out = lift_parcels(t, q, stack.level_view(2 * n), parcel=self.parcel, depth_pa=self.depth_pa, top_pa=self.top_pa, outputs=tuple(self.outputs), **table)
+        return out.to_layout(native.COLUMNS) if relayout else out
+
+    def forward(self, data: Any) -> FieldList:
+        passed, plan = self._plan(list(data))
+        result = list(passed)
+        for group in plan:
+            out = self._lift(group)
+            for row, param in enumerate(self.outputs.values()):
+                result.append(new_field_from_stack(out, row, template=group["sp"], metadata=dict(param=param, levtype="sfc")))
+        return FieldList(result)

@@ -14,6 +14,8 @@ variable or of a product of two, or the pressure-weighted mean of a layer, on mo
 ``search_columns`` (``atx_search_columns``, include/atx_search.h) SEARCHES the columns, which need not be monotone: the first step from
 either end at which a search variable crosses a value — the freezing level, the dynamic tropopause, cloud base — or the level of its
 maximum or minimum — the jet level — and the variables of a stack there.
+``lift_parcels`` (``atx_parcel_columns``, include/atx_parcel.h) FOLLOWS a parcel through the columns of ``t`` and ``q``: CAPE, CIN and the
+lifting condensation level of the lowest or of the most unstable parcel, on model levels or on pressure levels.
 """
 
 from __future__ import annotations
@@ -23,7 +25,7 @@ from typing import Any, Sequence
 import numpy as np
 import torch
 
-from . import native_coord, native_geopotential, native_heights, native_integral, native_levels, native_pltz, native_search
+from . import native_coord, native_geopotential, native_heights, native_integral, native_levels, native_parcel, native_pltz, native_search
 from .stack import COLUMNS, Stack
 
 G = 9.80665  # m / s^2: metres of geopotential height to geopotential (``filters.pointwise.g_gravitational_acceleration``)
@@ -312,3 +314,49 @@ def search_columns(stack: Stack | None, search: Stack, targets: Sequence[float] 
     if counted is not None:
         counted = counted.view(n_pts, n_tgt) if columns else counted.view(n_tgt, n_pts).t()
     return out, counted
+
+
+def lift_parcels(t: Stack, q: Stack, sp: torch.Tensor, *, A: Any = None, B: Any = None, levels_pa: Any = None, parcel: str = "lowest",
+                 depth_pa: float = 30000.0, top_pa: float = 5000.0, outputs: Sequence[str] = native_parcel.OUTPUTS) -> Stack:
+    """``t`` and ``q`` hold the same levels of temperature (K) and specific humidity (kg / kg), top level first, in one layout and type —
+    two stacks, or two views of one.  ``A`` / ``B``: the ``n_lev + 1`` half-level coefficients of the rows (hybrid model levels), or
+    ``levels_pa``: the ``n_lev`` pressures of the rows, strictly increasing (pressure levels; levels under the ground take no part and may
+    hold NaN).  ``parcel``: ``"lowest"``, the lowest level that takes part, or ``"most-unstable"``, the level of the largest theta_e within
+    ``depth_pa`` of it; levels above ``top_pa`` take no part.  The result holds one row per name of ``outputs`` — of ``cape``, ``cin``
+    (<= 0; NaN where no step holds a positive area), ``plcl``, ``tlcl``, ``pstart`` — in the layout and type of ``t``
+    (``atx_parcel_columns``, include/atx_parcel.h holds the statement).  One launch; a column stack whose levels of ONE point exceed the
+    LDS of a workgroup raises ``ValueError`` before any launch."""
+    names = tuple(outputs)
+    unknown = [name for name in names if name not in native_parcel.OUTPUTS]
+    if unknown or not names:
+        raise ValueError(f"lift_parcels: outputs must be some of {', '.join(native_parcel.OUTPUTS)}, got {list(outputs)}")
+    if (t.n_pts, t.n_lev, t.layout, t.dtype) != (q.n_pts, q.n_lev, q.layout, q.dtype):
+        raise ValueError(f"lift_parcels: t and q differ in shape, layout or type: {t} and {q}")
+    n_lev = t.n_lev
+    if (levels_pa is None) == (A is None or B is None):
+        raise ValueError("lift_parcels: either A and B (hybrid model levels) or levels_pa (pressure levels)")
+    if levels_pa is None:
+        A, B = _device_f64(A, t.device), _device_f64(B, t.device)
+        if not A.numel() == B.numel() == n_lev + 1:
+            raise ValueError(f"lift_parcels: A and B must hold the {n_lev + 1} half levels of the stack's {n_lev} levels, got {A.numel()} and {B.numel()}")
+    else:
+        host = np.asarray(levels_pa.cpu() if isinstance(levels_pa, torch.Tensor) else levels_pa, dtype=np.float64).reshape(-1)
+        if host.size != n_lev or not (np.diff(host) > 0).all() or not np.isfinite(host).all():
+            raise ValueError(f"lift_parcels: levels_pa must be {n_lev} strictly increasing pressures, got {host.tolist()}")
+        levels_pa = _device_f64(host, t.device)
+    sp = _per_point(sp, t.n_pts, t.dtype, "sp")
+    out = Stack.empty(t.n_pts, len(native_parcel.OUTPUTS), t.dtype, t.device, t.layout)
+    try:
+        native_parcel.columns(t.data, q.data, sp, out.data, n_pts=t.n_pts, n_lev=n_lev, t_pitch=t.pitch, q_pitch=q.pitch, out_pitch=out.pitch,
+                              layout=t.layout, A=A, B=B, levels_pa=levels_pa, parcel=parcel, depth_pa=depth_pa, top_pa=top_pa)
+    except NotImplementedError as refused:  # (raised by the library's validation: nothing was launched)
+        raise ValueError(f"lift_parcels: {refused}") from None
+    if names == native_parcel.OUTPUTS:
+        return out
+    rows = torch.tensor([native_parcel.OUTPUTS.index(name) for name in names], device=t.device)
+    chosen = Stack.empty(t.n_pts, len(names), t.dtype, t.device, t.layout)
+    if t.layout == COLUMNS:
+        chosen.data[:, :len(names)] = out.data[:, rows]
+    else:
+        chosen.data[:, :t.n_pts] = out.data[rows, :t.n_pts]
+    return chosen
